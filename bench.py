@@ -3,7 +3,7 @@
 bench.py - raw patches/s (forward + backward + Adam) of the imaging channel  UNet ISP -> manipulations -> codec -> FAN
 at 256x256 RGB (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c4|c2|c3|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload c4|c2|c3|c5] [--dump-outputs DIR] [--full]
 
 N > 1 without a torch.distributed environment: bench.py re-launches itself as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -22,11 +22,18 @@ Workloads (BASELINE.json configs):
 A "step" = one training step on a synthetic batch already resident in HBM.  Weak scaling: every rank processes its own B
 units.  Rank 0 prints ONE JSON line.
 
-Timing: W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides (max over ranks) -> `value`.
-HIP events recorded between five equal blocks of the same K steps give `config.block_ms_per_step` (their median is reported
-next to the contract figure; no extra host synchronisation inside the timed region).
+Timing: W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides (max over ranks) -> `value`,
+`ms_per_step` = wall milliseconds of one timed step.  HIP events recorded between five equal blocks of the same K steps give
+`config.block_ms_per_step` (their median is reported next to the contract figure; no extra host synchronisation inside the
+timed region).
 
-Extra objects on the line:
+A plain run does only what the headline needs: set up, warm up (incl. the choice of launch path below), time the K steps,
+write the outputs if asked, print the line.  --dump-outputs DIR: after the timed steps, what the timed path computed in its
+last step, as DIR/<name>.npy (float32 / float64) - the values the step returned (`loss`, `loss_<part>`) and the weights of
+every model it trains after its update (`<model>.<parameter>`, '/' -> '.'); a fixed, seeded sample of each if they exceed
+64 MB together.  Inputs and initial weights are seeded: the same arguments give the same inputs in every run.
+
+--full adds everything else below (each extra still subject to its own --no-* switch).  Extra objects on a --full line:
   roofline     - the workload's dominant kernel timed live with HIP events on the launch stream: algorithmic FLOPs of one
                  launch / average launch time against the dense MFMA peak of the compute dtype; traffic = HBM bytes per launch
                  from the committed PMC passes (profiles/*pmc_dominant_kernel.json: 2 x FETCH_SIZE + WRITE_SIZE, separate
@@ -35,7 +42,7 @@ Extra objects on the line:
                  sizes; the host's thread count is reported) of the SAME step on a bounded sample: 2 warm-up steps, median of
                  >= 5 timed steps
 --dtype bf16 (default) = throughput mode: bf16 MFMA operands, float32 accumulation, float32 master weights / optimizer.
---dtype f32 = parity mode (exact float32 MFMA; the mode the 1e-4 parity tests run in).  At N = 1 the default c4 run also
+--dtype f32 = parity mode (exact float32 MFMA; the mode the 1e-4 parity tests run in).  At N = 1 a --full c4 run also
 times parity-mode steps (top-level f32_mode_* keys, `roofline_f32`) and runs the trained-parity leg (trained_parity(): one
 seeded recipe - NIP pre-training, FAN warm-up, joint training, fixed step counts - run entirely in bf16 and entirely in float32
 from the same initial weights) to report accuracy / PSNR parity of the throughput mode on held-out patches.
@@ -88,6 +95,14 @@ class Workload(object):
     def finish(self):
         pass
 
+    def trained_models(self):
+        """[(name, model)] of every model the step updates: their weights after the last step are part of its result."""
+        return []
+
+    def step_count(self):
+        """Adam's step count as the eager path keeps it."""
+        raise NotImplementedError
+
     def flush(self):
         """Issue whatever a step left for the next one (the workflow's pipelined FAN update); a no-op otherwise."""
         wf = getattr(self, 'wf', None)
@@ -130,6 +145,12 @@ class ChannelJPEG(Workload):
     def finish(self):
         self.wf.check_nan()
 
+    def trained_models(self):
+        return [('nip', self.wf.nip), ('fan', self.wf.fan)]
+
+    def step_count(self):
+        return self.wf._step
+
     def dominant(self, dev):
         return time_conv5_dominant(dev, 5 * self.batch)
 
@@ -152,6 +173,9 @@ class ChannelDCN(ChannelJPEG):
 
     def step_args(self):
         return dict(lambda_nip=0.1, lambda_dcn=0.1, learning_rate=1e-4)
+
+    def trained_models(self):
+        return [('nip', self.wf.nip), ('dcn', self.wf.codec), ('fan', self.wf.fan)]
 
     def dominant(self, dev):
         return time_conv3_dominant(dev, 5 * self.batch)
@@ -178,6 +202,12 @@ class TrainDCN(Workload):
             return self.runner.step
         return self.eager
 
+    def trained_models(self):
+        return [('dcn', self.dcn)]
+
+    def step_count(self):
+        return self.dcn._model.step
+
     def dominant(self, dev):
         return time_conv3_dominant(dev, self.batch)
 
@@ -202,6 +232,12 @@ class TrainNIP(Workload):
             self.graph = True
             return self.runner.step
         return self.eager
+
+    def trained_models(self):
+        return [('nip', self.nip)]
+
+    def step_count(self):
+        return self.nip._model.step
 
     def dominant(self, dev):
         return time_unet_dominant(dev, self.batch, self.raw_patch)
@@ -614,6 +650,45 @@ def trained_parity(wl, dev, pre, warm, joint, joint_lr=5e-5):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(wl, last):
+    """What the timed path computed in its last step -> {name: float32 / float64 ndarray}: the values the step returned (the
+    workflow's (loss, {'ce', 'nip', 'dcn'}), a model's loss or its dict) and the weights of every model it updated."""
+    if isinstance(last, tuple):
+        items = [('loss', last[0])] + [('loss_' + k, v) for k, v in last[1].items()]
+    elif isinstance(last, dict):
+        items = list(last.items())
+    else:
+        items = [('loss', last)]
+    out = {}
+    for name, v in items:
+        if v is None or (isinstance(v, float) and np.isnan(v)):          # a part this configuration does not have
+            continue
+        out[name] = np.asarray(v)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    for prefix, model in wl.trained_models():
+        for k, v in model.state_dict().items():
+            out[prefix + '.' + k.replace('/', '.').replace(':', '_')] = np.asarray(v)
+    return {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in out.items()}
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array; if they exceed `limit` together, a fixed seeded sample of each (sorted flat indices,
+    the same share of every array)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(20240601)
+    for name in sorted(arrays):
+        a = arrays[name]
+        if total > limit and a.size > 1:
+            keep = max(1, int(a.size * (limit - (1 << 20)) / total))     # 1 MB left for the .npy headers
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -630,12 +705,12 @@ def main():
     ap.add_argument('--parity-steps', type=int, default=600,
                     help='joint training steps of the trained-parity leg (0 = skip); the NIP is pre-trained for 2.5 x as many '
                          'steps first, the FAN warmed up for half as many; run once entirely in bf16 and once entirely in f32')
-    ap.add_argument('--no-side-workloads', action='store_true', help='skip the short c2 / c3 / c5 runs of the default c4 line')
+    ap.add_argument('--no-side-workloads', action='store_true', help='skip the short c2 / c3 / c5 runs of a --full c4 line')
     ap.add_argument('--run-ahead', type=int, default=3,
                     help='steps the launching thread may be ahead of the GPU in the timed loop (0 = unbounded), see RunAhead')
     ap.add_argument('--stall-probe', action='store_true',
                     help='diagnostic: per-step host times of the timed loop + a Python stack dump of any step that takes > 150 ms')
-    ap.add_argument('--no-dp1-nccl', action='store_true', help='skip the one-rank RCCL leg (dp1_nccl_*) of the default c4 line')
+    ap.add_argument('--no-dp1-nccl', action='store_true', help='skip the one-rank RCCL leg (dp1_nccl_*) of a --full c4 line')
     ap.add_argument('--no-graph', dest='graph', action='store_false',
                     help='launch every kernel of the timed steps eagerly (default at N = 1: the step is ALSO captured into a HIP '
                          'graph - same kernels, same order, one launch call per step - and whichever of the two launch paths '
@@ -644,6 +719,13 @@ def main():
     ap.add_argument('--backend', default=None, help='torch.distributed backend (default: nccl = RCCL); gloo is for a '
                                                      'functional check of the N>1 path on a one-GPU box')
     ap.add_argument('--single-device', action='store_true', help='functional check only: every rank uses cuda:0')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure as well: roofline (dominant kernel, power), eager host cost, HBM '
+                         'fractions, the float32 parity-mode legs, the trained-parity leg, configs 2 / 3 / 5, the one-rank RCCL '
+                         'step and the CPU baseline (each still subject to its --no-* switch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (returned losses, updated weights) as '
+                         'DIR/<name>.npy, float32 / float64, at most 64 MB in all')
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--cpu-budget', type=float, default=20.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -704,6 +786,10 @@ def main():
             launch_modes[name] = min(launch_modes.get(name, 1e30), 1e3 * (time.perf_counter() - t_m) / max(args.warmup, 5))
         if launch_modes['eager'] < launch_modes['graph']:
             step, wl.graph = wl.eager, False
+        else:
+            # a captured step counts Adam's steps itself and the eager probe steps did not advance that count: continue from
+            # theirs, so that the timed steps compute the same whichever launch path won
+            wl.runner.t = wl.step_count()
     nblk = 5 if args.steps >= 5 else 1
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(nblk + 1)]
     edges = [round(i * args.steps / nblk) for i in range(nblk + 1)]
@@ -739,13 +825,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:        # before any --full leg steps the model again
+        dump_outputs(step_outputs(wl, last), args.dump_outputs)
 
     line = None
     if rank == 0:
         ms = 1e3 * dt / args.steps
         value = world * wl.batch * args.steps / dt
         blocks = [marks[i].elapsed_time(marks[i + 1]) / max(edges[i + 1] - edges[i], 1) for i in range(nblk)]
-        dom = wl.dominant(dev)
+        dom = wl.dominant(dev) if args.full else None
         peak = F32_MFMA_PEAK_TFLOPS if args.dtype == 'f32' else BF16_MFMA_PEAK_TFLOPS
         if isinstance(last, tuple):
             loss = float(last[0])
@@ -764,7 +852,7 @@ def main():
             cfg['stall_probe_slowest_host_steps'] = [[int(j), round(host_step_ms[j], 2)] for j in order]
         if launch_modes is not None:
             cfg['launch_mode_warmup_ms_per_step'] = {k: round(v, 4) for k, v in launch_modes.items()}
-        if world == 1 and getattr(wl, 'graph', False):
+        if args.full and world == 1 and getattr(wl, 'graph', False):
             # what the data-parallel step (always eager: the RCCL launches stay outside a captured graph) costs the host per
             # step: CPU time of this thread issuing 10 eager steps, and their wall time, next to the replayed figure above
             torch.cuda.synchronize()
@@ -774,7 +862,7 @@ def main():
             cfg['eager_host_cpu_ms_per_step'] = 1e2 * (time.thread_time() - c_e)
             torch.cuda.synchronize()
             cfg['eager_ms_per_step'] = 1e2 * (time.perf_counter() - t_e)
-        if wl.hbm_bytes_per_unit is not None:
+        if args.full and wl.hbm_bytes_per_unit is not None:
             # SURVEY 8d compulsory-traffic model of the whole step against 8 TB/s: one kernel per reference op
             # (343.8 MB bf16 / 687.5 MB f32 per raw patch) and the fused figure (141.9 / 283.8 MB)
             per = wl.hbm_bytes_per_unit[0 if args.dtype == 'bf16' else 1]
@@ -796,12 +884,13 @@ def main():
             'value': value, 'unit': 'patches/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': ms, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype,
             'data': 'synthetic (natural-image-like RAW/RGB pairs, random-init weights)', 'config': cfg,
-            'roofline': {'bound': 'mfma', 'achieved': dom['tflops'], 'peak': peak, 'unit': 'TFLOP/s',
-                         'frac': dom['tflops'] / peak, 'traffic': dom['traffic'], 'kernel': dom['kernel'],
-                         'ms_per_launch': dom['ms_per_launch'], 'flops_per_launch': dom['flops_per_launch'],
-                         'traffic_source': dom.get('traffic_source'), 'power': dom.get('power')},
         }
-        if world == 1 and args.dtype == 'bf16' and not args.no_parity_mode and wl.key in ('c4', 'c5'):
+        if dom is not None:
+            line['roofline'] = {'bound': 'mfma', 'achieved': dom['tflops'], 'peak': peak, 'unit': 'TFLOP/s',
+                                'frac': dom['tflops'] / peak, 'traffic': dom['traffic'], 'kernel': dom['kernel'],
+                                'ms_per_launch': dom['ms_per_launch'], 'flops_per_launch': dom['flops_per_launch'],
+                                'traffic_source': dom.get('traffic_source'), 'power': dom.get('power')}
+        if args.full and world == 1 and args.dtype == 'bf16' and not args.no_parity_mode and wl.key in ('c4', 'c5'):
             _ops.set_compute('f32')                           # same step, exact float32 MFMA (the parity-test mode), eager
             for _ in range(2):
                 wl.eager()
@@ -840,7 +929,8 @@ def main():
                 line['parity_same_weights_decision_agreement'] = x['decision_agreement_with_bf16_mode']
                 cfg['mode_parity_after_training'] = par
                 _ops.set_compute(args.dtype)
-        if world == 1 and args.dtype == 'bf16' and wl.key == 'c4' and not args.no_parity_mode and not args.no_side_workloads:
+        if args.full and world == 1 and args.dtype == 'bf16' and wl.key == 'c4' and not args.no_parity_mode and \
+                not args.no_side_workloads:
             # configs 2, 3 and 5 of BASELINE.json on the same line (flat scalars: the driver's parser keeps those): 30 timed steps each
             for key in ('c2', 'c3', 'c5'):
                 try:
@@ -881,14 +971,15 @@ def main():
             except Exception as e:
                 line['c2_psnr_error'] = repr(e)[:200]
             _ops.set_compute(args.dtype)
-        if world == 1 and args.dtype == 'bf16' and wl.key == 'c4' and not args.no_dp1_nccl and not args.no_parity_mode:
+        if args.full and world == 1 and args.dtype == 'bf16' and wl.key == 'c4' and not args.no_dp1_nccl and \
+                not args.no_parity_mode:
             # the data-parallel step through RCCL on this one GPU: a one-rank nccl group with the collectives
             # forced - gradient buckets, NaN-flag reduction - next to the plain eager step of the same process
             try:
                 line.update(dp1_nccl_leg(wl))
             except Exception as e:
                 line['dp1_nccl_error'] = repr(e)[:200]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line['cpu_baseline'] = cpu_baseline(wl.key, args.raw_patch)
         line['launch_path'] = 'hip_graph_replay' if cfg['hip_graph'] else 'eager_launches'
     if world > 1:

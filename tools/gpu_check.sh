@@ -13,12 +13,12 @@ for ST in "$@"; do
   case $ST in
     tests) timeout 900 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; note "pytest rc=$?"; tail -15 $OUT/pytest.log ;;
     tests:*) timeout 900 python -m pytest tests -m gpu -q -k "${ST#tests:}" > $OUT/pytest_k.log 2>&1; note "pytest -k rc=$?"; tail -30 $OUT/pytest_k.log ;;
-    c4) timeout 500 python bench.py > $OUT/bench_c4.json 2> $OUT/bench_c4.err; note "bench c4 rc=$?"; tail -c 1500 $OUT/bench_c4.json ;;
+    c4) timeout 500 python bench.py --full > $OUT/bench_c4.json 2> $OUT/bench_c4.err; note "bench c4 rc=$?"; tail -c 1500 $OUT/bench_c4.json ;;
     c4nocpu) timeout 300 python bench.py --no-cpu-baseline --no-parity-mode > $OUT/bench_c4_nocpu.json 2> $OUT/bench_c4_nocpu.err; note "bench c4 (no cpu) rc=$?"; head -c 400 $OUT/bench_c4_nocpu.json ;;
     c4old) NIMG_OLD_FRONTEND=1 timeout 300 python bench.py --no-cpu-baseline --no-parity-mode > $OUT/bench_c4_old.json 2> $OUT/bench_c4_old.err; note "bench c4 (old front end) rc=$?"; head -c 400 $OUT/bench_c4_old.json ;;
     c4eager) timeout 300 python bench.py --no-graph --no-cpu-baseline --no-parity-mode > $OUT/bench_c4_eager.json 2> $OUT/bench_c4_eager.err; note "bench c4 eager rc=$?"; head -c 400 $OUT/bench_c4_eager.json ;;
-    c3) timeout 400 python bench.py --workload c3 --steps 50 > $OUT/bench_c3.json 2> $OUT/bench_c3.err; note "bench c3 rc=$?"; tail -c 900 $OUT/bench_c3.json ;;
-    c5) timeout 400 python bench.py --workload c5 --steps 50 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; note "bench c5 rc=$?"; tail -c 900 $OUT/bench_c5.json ;;
+    c3) timeout 400 python bench.py --full --workload c3 --steps 50 > $OUT/bench_c3.json 2> $OUT/bench_c3.err; note "bench c3 rc=$?"; tail -c 900 $OUT/bench_c3.json ;;
+    c5) timeout 400 python bench.py --full --workload c5 --steps 50 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; note "bench c5 rc=$?"; tail -c 900 $OUT/bench_c5.json ;;
     n2) timeout 300 python bench.py --gpus 2 --backend gloo --single-device --steps 5 --warmup 2 --batch 16 --no-cpu-baseline \
           > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err; note "bench n2 gloo rc=$?" ;;
     prof) (cd /tmp && NIMG_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o c4 -- \

@@ -1,6 +1,7 @@
-mkdir -p gpurun_out/r04_zb
+D=${1:?usage: tools/probe_host2.sh <output dir>}
+mkdir -p $D
 grep -E "nr_throttled|nr_periods" /sys/fs/cgroup/cpu.stat
-python bench.py --steps 1500 --warmup 10 --no-cpu-baseline --no-parity-mode --no-dp1-nccl --no-graph > gpurun_out/r04_zb/run.json 2> gpurun_out/r04_zb/run.err &
+python bench.py --full --steps 1500 --warmup 10 --no-cpu-baseline --no-parity-mode --no-dp1-nccl --no-graph > $D/run.json 2> $D/run.err &
 BP=$!
 for i in 1 2 3 4 5 6 7 8 9 10 11 12; do
   sleep 2
@@ -8,8 +9,8 @@ for i in 1 2 3 4 5 6 7 8 9 10 11 12; do
   top -H -b -n 1 -w 200 2>/dev/null | sed -n 7,16p | cut -c1-150
 done
 wait $BP
-python - <<'PY'
-import json
-d = json.loads(open('gpurun_out/r04_zb/run.json').read().strip().split('\n')[-1])
+python - $D/run.json <<'PY'
+import json, sys
+d = json.loads(open(sys.argv[1]).read().strip().split('\n')[-1])
 print('%.0f patches/s  %.3f ms  ring %.3f host_cpu %.2f' % (d['value'], d['ms_per_step'], d['roofline']['ms_per_launch'], d['config'].get('host_cpu_ms_per_step', 0)))
 PY

@@ -4,7 +4,7 @@
 OUT=$1; N=$2; shift 2
 mkdir -p $OUT
 for i in $(seq 1 $N); do
-  python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-parity-mode "$@" > $OUT/run_$i.json 2> $OUT/run_$i.err
+  python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-parity-mode "$@" > $OUT/run_$i.json 2> $OUT/run_$i.err
   python - $OUT/run_$i.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split('\n')[-1])
