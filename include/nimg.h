@@ -54,8 +54,9 @@ extern "C" {
 
 /* library / ABI version, bumped on any change of an existing entry point's signature or data layout (3: nimg_conv2d_fwd_bf16_res
  * gained out_bf16_copy and stride; 5: the arg-max of nimg_conv1_pool_fwd_c4 / nimg_conv1_wgrad_c4 / nimg_conv1_dgrad_pooled is 2 bits
- * per value).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was written against. */
-#define NIMG_ABI_VERSION 5
+ * per value; 6: the nimg_l3ic_* bitstream entry points).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
+ * written against. */
+#define NIMG_ABI_VERSION 6
 int nimg_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -644,6 +645,37 @@ int nimg_gamma_fwd(const float* x, float* y, long count, float gamma, void* stre
 int nimg_gamma_bwd(const float* x, const float* dy, float* dx, long count, float gamma, void* stream);
 int nimg_median_fwd(const float* x, float* y, uint8_t* sel, int n, int h, int w, int kernel, void* stream);
 int nimg_median_bwd(const float* dy, const uint8_t* sel, float* dx, int n, int h, int w, int kernel, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * l3ic bitstream of the learned codec - replaces the per-layer host coding of compression/codec.py:87-185 (compress) and
+ * :188-265 (decompress).  The container is the reference's; a compressed layer holds interleaved rANS instead of FSE
+ * (format: DESIGN.md "l3ic bitstream").  A stream is one feature layer of one image: n_sym = h * w codebook indices.
+ *   quantise  z (n,h,w,c) float32 -> idx (n,c,h*w) uint8, the nearest codebook entry as scipy.cluster.vq.vq finds it on
+ *             float32 (squared difference, ties to the lower index); *err |= 1 for a non-finite value (zero *err first).
+ *             codebook_size <= 256.
+ *   encode    idx (n_streams, n_sym) uint8 -> out: the payloads of all streams back to back (capacity n_streams * n_sym),
+ *             lengths[n_streams] their byte counts (a payload starts at the sum of the lengths before it).  hist / freq
+ *             (optional, [n_streams][256] uint32) receive each stream's histogram and normalised frequencies.  4 <= n_sym
+ *             <= 65535.  The workspace (nimg_l3ic_workspace_bytes) holds one worst-case slot per stream.
+ *   decode    the payload of stream s = image s / c, layer s % c at data + offsets[s], lengths[s] bytes -> codebook[index]
+ *             written into z (n,h,w,c) float32; err[s] = NIMG_L3IC_E_* bits (0 = valid).  No read leaves a payload. */
+#define NIMG_L3IC_E_READ 1      /* a read past the end of the payload (truncated stream, or longer than a RAW layer) */
+#define NIMG_L3IC_E_LANES 2     /* lane count outside 1..64 */
+#define NIMG_L3IC_E_RANGE 4     /* first symbol > last symbol, or either has a zero frequency */
+#define NIMG_L3IC_E_SYMBOL 8    /* a symbol index >= codebook_size */
+#define NIMG_L3IC_E_FREQ 16     /* frequencies do not sum to 4096 */
+#define NIMG_L3IC_E_VARINT 32   /* a frequency longer than 2 bytes */
+#define NIMG_L3IC_E_ODD 64      /* odd number of word bytes */
+#define NIMG_L3IC_E_UNUSED 128  /* words left over after the last symbol */
+#define NIMG_L3IC_E_STATE 256   /* a final decoder state other than 2^16 */
+#define NIMG_L3IC_E_RLE 512     /* an RLE count other than n_sym */
+size_t nimg_l3ic_workspace_bytes(int n_streams, int n_sym);
+int nimg_l3ic_quantise(const float* z, const float* codebook, int codebook_size, uint8_t* idx, int* err, int n, int h,
+                       int w, int c, void* stream);
+int nimg_l3ic_encode(const uint8_t* idx, int n_streams, int n_sym, uint8_t* out, uint32_t* lengths, uint32_t* hist,
+                     uint32_t* freq, void* workspace, size_t workspace_bytes, void* stream);
+int nimg_l3ic_decode(const uint8_t* data, const uint32_t* offsets, const uint32_t* lengths, const float* codebook,
+                     int codebook_size, float* z, uint32_t* err, int n, int h, int w, int c, void* stream);
 
 #ifdef __cplusplus
 }

@@ -180,6 +180,10 @@ PROTOTYPES = {
     'nimg_median_fwd': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     'nimg_median_bwd': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     'nimg_sparse_axis_apply': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'nimg_l3ic_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'nimg_l3ic_quantise': (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
+    'nimg_l3ic_encode': (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    'nimg_l3ic_decode': (c_int, [P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
 }
 
 ERRORS = {-1: 'NIMG_ERR_ARG (invalid argument / unsupported configuration)',
@@ -189,7 +193,7 @@ ERRORS = {-1: 'NIMG_ERR_ARG (invalid argument / unsupported configuration)',
 _lib = None
 
 
-ABI_VERSION = 5         # include/nimg.h NIMG_ABI_VERSION
+ABI_VERSION = 6         # include/nimg.h NIMG_ABI_VERSION
 TICKET_BYTES = 64 * 1024        # include/nimg.h NIMG_TICKET_BYTES
 
 

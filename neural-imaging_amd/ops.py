@@ -2173,3 +2173,54 @@ def pad2d(x, pad, mode='REFLECT'):
     y = torch.empty((n, h + 2 * pad, w + 2 * pad, c), dtype=torch.float32, device=x.device)
     _lib.call('nimg_pad2d', _p(x), _p(y), n, h, w, c, pad, PAD_MODES[mode], _stream())
     return y
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# l3ic bitstream of the learned codec (compression/codec.py; include/nimg.h nimg_l3ic_*)
+L3IC_ERRORS = {1: 'read past the end of the payload', 2: 'lane count outside 1..64', 4: 'bad symbol range',
+               8: 'symbol index beyond the codebook', 16: 'frequencies do not sum to 4096',
+               32: 'frequency longer than 2 bytes', 64: 'odd number of word bytes', 128: 'unused words',
+               256: 'final state other than 2^16', 512: 'RLE count other than the layer size'}
+
+
+def l3ic_quantise(z, codebook):
+    """(n,h,w,c) float32 latent -> ((n,c,h*w) uint8 codebook indices, (1,) int32 flag: non-zero = a non-finite value)."""
+    _f32(z, codebook)
+    n, h, w, c = z.shape
+    idx = torch.empty((n, c, h * w), dtype=torch.uint8, device=z.device)
+    err = torch.zeros((1,), dtype=torch.int32, device=z.device)
+    _lib.call('nimg_l3ic_quantise', _p(z), _p(codebook), codebook.numel(), _p(idx), _p(err), n, h, w, c, _stream())
+    return idx, err
+
+
+def l3ic_encode(idx, want_stats=False):
+    """Streams idx (..., n_sym) uint8 -> (payloads back to back (uint8, capacity streams * n_sym), lengths (streams,) int32,
+    histograms and normalised frequencies (streams, 256) int32 if want_stats else None)."""
+    _chk(idx)
+    if idx.dtype != torch.uint8:
+        raise RuntimeError('l3ic_encode needs uint8 indices, got {}'.format(idx.dtype))
+    n_sym = idx.shape[-1]
+    streams = idx.numel() // n_sym
+    out = torch.empty(streams * n_sym, dtype=torch.uint8, device=idx.device)
+    lengths = torch.empty(streams, dtype=torch.int32, device=idx.device)
+    hist = freq = None
+    if want_stats:
+        hist = torch.empty((streams, 256), dtype=torch.int32, device=idx.device)
+        freq = torch.empty((streams, 256), dtype=torch.int32, device=idx.device)
+    ws = torch.empty(int(_lib.load().nimg_l3ic_workspace_bytes(streams, n_sym)), dtype=torch.uint8, device=idx.device)
+    _lib.call('nimg_l3ic_encode', _p(idx), streams, n_sym, _p(out), _p(lengths), _p(hist), _p(freq), _p(ws), ws.numel(),
+              _stream())
+    return out, lengths, hist, freq
+
+
+def l3ic_decode(data, offsets, lengths, codebook, shape):
+    """Payload bytes (uint8) with per-stream offsets / lengths (int32, stream = image * c + layer) -> (the (n,h,w,c) float32
+    latent codebook[index], (n*c,) int32 error words, include/nimg.h NIMG_L3IC_E_*)."""
+    _chk(data, offsets, lengths)
+    _f32(codebook)
+    n, h, w, c = shape
+    z = torch.empty((n, h, w, c), dtype=torch.float32, device=data.device)
+    err = torch.empty((n * c,), dtype=torch.int32, device=data.device)
+    _lib.call('nimg_l3ic_decode', _p(data), _p(offsets), _p(lengths), _p(codebook), codebook.numel(), _p(z), _p(err), n, h, w,
+              c, _stream())
+    return z, err

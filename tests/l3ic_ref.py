@@ -1,0 +1,210 @@
+"""
+Plain-Python restatement of the l3ic bitstream ("l3ic bitstream"): frequency normalisation, interleaved rANS
+encode / decode of one layer, the RLE / RAW / rANS layer dispatch and the container.  Test infrastructure: it pins the
+format the HIP kernels (neural-imaging_amd/csrc/l3ic.hip) write and read; the package never imports it.
+"""
+import struct
+
+import numpy as np
+
+M_BITS = 12
+M = 1 << M_BITS                 # probability scale
+LOW = 1 << 16                   # state interval [2^16, 2^32)
+
+
+class FormatError(Exception):
+    pass
+
+
+def lanes_for(n_sym):
+    """L = min(64, largest power of two <= max(1, n_sym // 2048))"""
+    q, lanes = max(1, n_sym // 2048), 1
+    while lanes * 2 <= q:
+        lanes *= 2
+    return min(64, lanes)
+
+
+def normalise(counts):
+    """Integer frequency normalisation to a sum of exactly 4096 (f > 0 <=> count > 0)."""
+    c = [int(v) for v in counts]
+    n = sum(c)
+    f = [max(1, v * M // n) if v > 0 else 0 for v in c]
+    total = sum(f)
+    if total < M:
+        f[c.index(max(c))] += M - total                 # largest count, lowest index on ties
+    while total > M:
+        best = max((v for v in f if v > 1))
+        f[f.index(best)] -= 1                           # largest f among f > 1, lowest index on ties
+        total -= 1
+    return f
+
+
+def _cum(f):
+    out, acc = [], 0
+    for v in f:
+        out.append(acc)
+        acc += v
+    return out
+
+
+def _varint(v):
+    return bytes([v]) if v < 128 else bytes([(v & 0x7f) | 0x80, v >> 7])
+
+
+def table_bytes(f):
+    nz = [i for i, v in enumerate(f) if v]
+    return sum(1 if v < 128 else 2 for v in f[nz[0]:nz[-1] + 1])
+
+
+def rans_encode(sym, k=256, lanes=None):
+    """rANS payload of one layer (sym: sequence of indices < k).  lanes=None: the encoder rule."""
+    sym = [int(s) for s in sym]
+    n = len(sym)
+    counts = [0] * max(k, max(sym) + 1)
+    for s in sym:
+        counts[s] += 1
+    f = normalise(counts)
+    cum = _cum(f)
+    lanes = lanes_for(n) if lanes is None else lanes
+    nz = [i for i, v in enumerate(f) if v]
+    a, b = nz[0], nz[-1]
+    x = [LOW] * lanes
+    steps = (n + lanes - 1) // lanes
+    per_step = []
+    for t in range(steps - 1, -1, -1):
+        words = []
+        for lane in range(lanes):
+            i = t * lanes + lane
+            if i >= n:
+                continue
+            s = sym[i]
+            fs = f[s]
+            if x[lane] >= fs << 20:
+                words.append(x[lane] & 0xffff)
+                x[lane] >>= 16
+            x[lane] = ((x[lane] // fs) << M_BITS) + x[lane] % fs + cum[s]
+        per_step.append(words)
+    words = [w for step in reversed(per_step) for w in step]
+    out = bytearray([lanes, a, b])
+    for v in f[a:b + 1]:
+        out += _varint(v)
+    out += struct.pack('<{}I'.format(lanes), *x)
+    out += struct.pack('<{}H'.format(len(words)), *words)
+    return bytes(out)
+
+
+def rans_decode(payload, n_sym, k=256):
+    """Inverse of rans_encode; raises FormatError where the device decoder sets an error flag."""
+    p = bytes(payload)
+    if len(p) < 3:
+        raise FormatError('truncated header')
+    lanes, a, b = p[0], p[1], p[2]
+    if not 1 <= lanes <= 64:
+        raise FormatError('lane count {}'.format(lanes))
+    if a > b or b >= k:
+        raise FormatError('symbol range {}..{}'.format(a, b))
+    f, pos = [0] * 256, 3
+    for s in range(a, b + 1):
+        if pos >= len(p):
+            raise FormatError('truncated table')
+        v = p[pos]
+        pos += 1
+        if v & 0x80:
+            if pos >= len(p):
+                raise FormatError('truncated table')
+            v2 = p[pos]
+            pos += 1
+            if v2 & 0x80:
+                raise FormatError('varint longer than 2 bytes')
+            v = (v & 0x7f) | (v2 << 7)
+        f[s] = v
+    if sum(f) != M:
+        raise FormatError('frequency sum {}'.format(sum(f)))
+    if f[a] == 0 or f[b] == 0:
+        raise FormatError('symbol range {}..{} ends on a zero frequency'.format(a, b))
+    cum = _cum(f)
+    slot_sym = np.repeat(np.arange(256), f)
+    if pos + 4 * lanes > len(p):
+        raise FormatError('truncated states')
+    x = list(struct.unpack_from('<{}I'.format(lanes), p, pos))
+    pos += 4 * lanes
+    if (len(p) - pos) % 2:
+        raise FormatError('odd word bytes')
+    words = struct.unpack_from('<{}H'.format((len(p) - pos) // 2), p, pos)
+    out = np.zeros(n_sym, np.uint8)
+    wp = 0
+    for t in range((n_sym + lanes - 1) // lanes):
+        for lane in range(lanes):
+            i = t * lanes + lane
+            if i >= n_sym:
+                break
+            slot = x[lane] & (M - 1)
+            s = int(slot_sym[slot])
+            out[i] = s
+            x[lane] = f[s] * (x[lane] >> M_BITS) + slot - cum[s]
+            if x[lane] < LOW:
+                if wp >= len(words):
+                    raise FormatError('stream exhausted')
+                x[lane] = (x[lane] << 16) | words[wp]
+                wp += 1
+    if wp != len(words):
+        raise FormatError('{} unused words'.format(len(words) - wp))
+    if any(v != LOW for v in x):
+        raise FormatError('final state')
+    return out
+
+
+def encode_layer(sym, k=256):
+    """The payload the encoder picks: RLE (one symbol), else rANS if strictly shorter than n_sym, else RAW."""
+    sym = np.asarray(sym, np.uint8).ravel()
+    n = sym.size
+    if np.all(sym == sym[0]):
+        return struct.pack('<HB', n, int(sym[0]))
+    r = rans_encode(sym, k)
+    return r if len(r) < n else sym.tobytes()
+
+
+def decode_layer(payload, n_sym, k=256):
+    if len(payload) > n_sym:
+        raise FormatError('payload longer than a raw layer')
+    if len(payload) == n_sym:
+        out = np.frombuffer(payload, np.uint8).copy()
+        if out.size and int(out.max()) >= k:
+            raise FormatError('symbol out of range')
+        return out
+    if len(payload) == 3:
+        count, s = struct.unpack('<HB', payload)
+        if count != n_sym or s >= k:
+            raise FormatError('RLE layer')
+        return np.full(n_sym, s, np.uint8)
+    return rans_decode(payload, n_sym, k)
+
+
+def pack_container(h, w, payloads):
+    out = bytearray([h, w, len(payloads)])
+    out += struct.pack('<H', 2 * len(payloads))
+    out += struct.pack('<{}H'.format(len(payloads)), *[len(p) for p in payloads])
+    for p in payloads:
+        out += p
+    return bytes(out)
+
+
+def parse_container(stream):
+    h, w, n = stream[0], stream[1], stream[2]
+    (nl,) = struct.unpack_from('<H', stream, 3)
+    if nl != 2 * n:
+        raise FormatError('coded layer lengths are not supported')
+    lengths = struct.unpack_from('<{}H'.format(n), stream, 5)
+    pos, payloads = 5 + 2 * n, []
+    for ln in lengths:
+        payloads.append(bytes(stream[pos:pos + ln]))
+        pos += ln
+    if pos != len(stream):
+        raise FormatError('container length')
+    return h, w, n, payloads
+
+
+def ideal_bits(sym, f):
+    """sum_i -log2(f[s_i] / 4096)"""
+    p = np.asarray(f, np.float64)[np.asarray(sym, np.int64)] / M
+    return float(-np.log2(p).sum())
