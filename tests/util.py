@@ -147,3 +147,93 @@ def collect_from_workers(make_procs, n_results, timeout, attempts=3):
                 p.kill()
             p.join(timeout=30)
     raise RuntimeError('workers did not answer in {} attempt(s); exit codes of the last one: {}'.format(attempts, last))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# exact-arithmetic tests (tests/test_gpu_exact.py, tests/test_exact_helpers.py): bf16 x bf16 products are exact in float32 and
+# float32 sums of integers are exact in any order while the sum of the absolute terms stays below 2^24 - so on small-integer
+# operands every kernel, whatever its tiling or summation order, must reproduce the float64 oracle bit for bit.
+EXACT_SUM_LIMIT = float(1 << 24)
+BF16_INT_LIMIT = 256.0                     # every integer of magnitude <= 256 is a bf16 value
+
+
+def ternary(shape, seed, p=0.25):
+    """float32 values in {-1, 0, +1}, non-zero with probability p (operands of the cases whose result is stored as bf16)."""
+    rng = np.random.default_rng(seed)
+    nz = rng.random(size=shape) < p
+    sign = rng.integers(0, 2, size=shape) * 2 - 1
+    return (nz * sign).astype(np.float32)
+
+
+def small_ints(shape, seed, m=3):
+    """float32 uniform integers in [-m, m] (operands of the cases whose result is stored as float32)."""
+    return np.random.default_rng(seed).integers(-m, m + 1, size=shape).astype(np.float32)
+
+
+def bf16_rne(a):
+    """float64 array of `a` (float32) rounded to bfloat16, round-to-nearest-even (torch's conversion)."""
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32))).to(torch.bfloat16).double().numpy()
+
+
+def assert_exact(got, ref64, what=''):
+    """got == ref64 in every element (compared as float64); on failure: the count and the first few (index, got, want)."""
+    got = np.asarray(got).astype(np.float64)
+    ref64 = np.asarray(ref64, np.float64)
+    assert got.shape == ref64.shape, '{}: shape {} != {}'.format(what, got.shape, ref64.shape)
+    if np.array_equal(got, ref64):
+        return
+    bad = np.argwhere(~(got == ref64))
+    first = ['{} got {!r} want {!r}'.format(tuple(int(v) for v in i), float(got[tuple(i)]), float(ref64[tuple(i)]))
+             for i in bad[:8]]
+    lo, hi = bad.min(axis=0), bad.max(axis=0)
+    raise AssertionError('{}: {} of {} elements differ (index box {} .. {}); first: {}'.format(
+        what, len(bad), got.size, tuple(int(v) for v in lo), tuple(int(v) for v in hi), '; '.join(first)))
+
+
+def assert_exact_conditions(abs_sum, ref64, stores_bf16, scale=1.0, what=''):
+    """The two conditions under which a case is exact, asserted on the reference alone: (a) the same operation on the absolute
+    operands (`abs_sum`, float64) stays below 2^24 (in units of `scale`, a power of two); (b) where the kernel stores bf16,
+    max|ref| <= 256 * scale."""
+    a = float(np.asarray(abs_sum, np.float64).max()) / scale
+    assert a < EXACT_SUM_LIMIT, '{}: sum of |terms| {} reaches 2^24 - the case is not exact'.format(what, a)
+    if stores_bf16:
+        b = float(np.abs(np.asarray(ref64, np.float64)).max()) / scale
+        assert b <= BF16_INT_LIMIT, '{}: max|ref| {} > 256 - not every value is a bf16 number'.format(what, b)
+
+
+def lrelu_f32(v64, alpha=0.2):
+    """LeakyReLU as the kernels compute it: ONE float32 multiply on the (exactly representable) float32 value; -> float32."""
+    v = np.asarray(v64, np.float64).astype(np.float32)
+    assert np.array_equal(v.astype(np.float64), np.asarray(v64, np.float64)), 'pre-activation is not a float32 value'
+    return np.where(v > 0, v, np.float32(alpha) * v).astype(np.float32)
+
+
+def mask_f32(v64, mask, alpha=0.2):
+    """v * LeakyReLU'(mask) as the kernels compute it: one float32 multiply by 1 or float32(alpha)."""
+    v = np.asarray(v64, np.float64).astype(np.float32)
+    return np.where(np.asarray(mask) > 0, v, np.float32(alpha) * v).astype(np.float32)
+
+
+def pool_windows(act):
+    """(n, h, w, c) -> (n, h/2, w/2, c, 4): the 2x2 windows in the order (0,0), (0,1), (1,0), (1,1)."""
+    act = np.asarray(act)
+    n, h, w, c = act.shape
+    return act.reshape(n, h // 2, 2, w // 2, 2, c).transpose(0, 1, 3, 5, 2, 4).reshape(n, h // 2, w // 2, c, 4)
+
+
+def first_max_pool(act, last=False):
+    """(pooled, arg-max) of MaxPool2D(2) with the FIRST maximum winning a tie (np.argmax); last=True: the wrong rule, for the
+    self-test of the exact tests."""
+    win = pool_windows(act)
+    idx = (3 - np.argmax(win[..., ::-1], axis=-1)) if last else np.argmax(win, axis=-1)
+    return win.max(axis=-1), idx.astype(np.uint8)
+
+
+def unpool(gp, idx):
+    """Route a pooled gradient (n, h/2, w/2, c) to the arg-max position of each 2x2 window -> (n, h, w, c)."""
+    gp, idx = np.asarray(gp), np.asarray(idx)
+    n, hp, wp, c = gp.shape
+    dz = np.zeros((n, 2 * hp, 2 * wp, c), gp.dtype)
+    for pos in range(4):
+        dz[:, pos >> 1::2, pos & 1::2, :] = np.where(idx == pos, gp, 0)
+    return dz
