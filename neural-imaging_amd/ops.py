@@ -1328,9 +1328,10 @@ def head_fused_ok(x, cout):
                 x.shape[0] > 0 and _lib.load().nimg_head_fused_ok(int(x.shape[1] * x.shape[2]), int(cout)))
 
 
-def head_fwd(x, w, b, want_mask=True):
+def head_fwd(x, w, b, want_mask=True, alpha=None):
     """x (N,H,W,C) bf16, w (1,1,C,C), b (C) -> gap (N,C) float32, mask (N*H*W, C/32), mask_p (N, H*W/32, C): int32 sign bits of
-    the activation in the two layouts the backward kernels read (or None, None)."""
+    the activation in the two layouts the backward kernels read (or None, None).  alpha (here and in head_wgrad / head_dgrad /
+    head_dact): slope of the LeakyReLU, default 0.2."""
     _chk(x, w, b)
     n, h, wd, c = x.shape
     gap = torch.empty((n, c), dtype=torch.float32, device=x.device)
@@ -1338,12 +1339,12 @@ def head_fwd(x, w, b, want_mask=True):
     if want_mask:           # the same sign bits twice: channel-major words per pixel (input gradient), pixel-major per channel (weights)
         mask = torch.empty((n * h * wd, c // 32), dtype=torch.int32, device=x.device)
         mask_p = torch.empty((n, h * wd // 32, c), dtype=torch.int32, device=x.device)
-    _lib.call('nimg_head_fwd', _p(x), _p(weights_bf16(w, 0)), _p(b), _p(mask), _p(mask_p), _p(gap), n, h * wd, c, LRELU_ALPHA,
-              _stream())
+    _lib.call('nimg_head_fwd', _p(x), _p(weights_bf16(w, 0)), _p(b), _p(mask), _p(mask_p), _p(gap), n, h * wd, c,
+              LRELU_ALPHA if alpha is None else float(alpha), _stream())
     return gap, mask, mask_p
 
 
-def head_wgrad(x, mask_p, dlogits, wdense, dw, db=None, accumulate=False):
+def head_wgrad(x, mask_p, dlogits, wdense, dw, db=None, accumulate=False, alpha=None):
     """Weight (+ bias) gradient of the fused head's 1x1 layer from its bf16 input and the pixel-major sign words."""
     _chk(x, mask_p, dlogits, wdense)
     _f32(dw, db)
@@ -1351,7 +1352,7 @@ def head_wgrad(x, mask_p, dlogits, wdense, dw, db=None, accumulate=False):
     need = _lib.load().nimg_head_wgrad_workspace_bytes(n, c)
     ws = _ws_current(x.device).get(need, x.device)
     _lib.call('nimg_head_wgrad', _p(x), _p(mask_p), _p(dlogits), _p(wdense), dlogits.shape[1], _p(dw), _p(db), n, h * wd, c,
-              LRELU_ALPHA, 1 if accumulate else 0, _p(ws), ws.numel(), _stream())
+              LRELU_ALPHA if alpha is None else float(alpha), 1 if accumulate else 0, _p(ws), ws.numel(), _stream())
     return dw
 
 
@@ -1382,7 +1383,7 @@ def fan_dense_bwd(gap, dlogits, loss_per, loss_scale, dw, db):
     return loss
 
 
-def head_dgrad(mask, dlogits, wdense, w, in_mask, shape):
+def head_dgrad(mask, dlogits, wdense, w, in_mask, shape, alpha=None):
     """Gradient at the INPUT of the fused head's 1x1 layer, bf16 (N,H,W,C): from the classifier's dlogits, the activation's sign
     bits and (optionally) the bf16 tensor whose sign gates the LeakyReLU of the layer below."""
     _chk(mask, dlogits, wdense, w, in_mask)
@@ -1391,16 +1392,17 @@ def head_dgrad(mask, dlogits, wdense, w, in_mask, shape):
     if in_mask is not None and (not _is_bf16(in_mask) or tuple(in_mask.shape) != tuple(shape)):
         raise RuntimeError('head_dgrad: the mask tensor is the bf16-stored input of the 1x1 layer')
     _lib.call('nimg_head_dgrad', _p(mask), _p(dlogits), _p(wdense), dlogits.shape[1], _p(weights_bf16(w, 1)), _p(in_mask), _p(dx),
-              n, h * wd, c, LRELU_ALPHA, _stream())
+              n, h * wd, c, LRELU_ALPHA if alpha is None else float(alpha), _stream())
     return dx
 
 
-def head_dact(mask, dlogits, wdense, shape):
+def head_dact(mask, dlogits, wdense, shape, alpha=None):
     """Gradient at the fused head's 1x1 pre-activation as a bf16 tensor (N,H,W,C) - what its weight gradient reads."""
     _chk(mask, dlogits, wdense)
     n, h, wd, c = shape
     dact = torch.empty((n, h, wd, c), dtype=torch.bfloat16, device=mask.device)
-    _lib.call('nimg_head_dact', _p(mask), _p(dlogits), _p(wdense), dlogits.shape[1], _p(dact), n, h * wd, c, LRELU_ALPHA, _stream())
+    _lib.call('nimg_head_dact', _p(mask), _p(dlogits), _p(wdense), dlogits.shape[1], _p(dact), n, h * wd, c,
+              LRELU_ALPHA if alpha is None else float(alpha), _stream())
     return dact
 
 

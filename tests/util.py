@@ -388,3 +388,68 @@ def redraw_near_half(x, value_of, seed, width=1e-3, lo=0.05, hi=0.95):
             return x
         x[bad] = (lo + (hi - lo) * rng.random(int(bad.sum()))).astype(np.float32)
     raise AssertionError('could not move every element away from the rounding ties')
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# exact-arithmetic tests of the tail of the training step (tests/test_gpu_tail_exact.py, tests/tail_cases.py,
+# tests/test_tail_helpers.py): losses, sums, FAN head, Adam, latent.
+F32_UNIT_ROUNDOFF = 2.0 ** -24
+F32_MIN_NORMAL = float(np.finfo(np.float32).tiny)
+
+
+def odd_part(n):
+    """n / (the largest power of two dividing n)."""
+    n = int(n)
+    assert n > 0
+    return n // (n & -n)
+
+
+def is_f32(a64):
+    """Every element of the float64 array is a float32 number (nothing would round on a float32 store)."""
+    a64 = np.asarray(a64, np.float64)
+    return np.array_equal(a64.astype(np.float32).astype(np.float64), a64)
+
+
+def assert_no_denormals(*arrays, what=''):
+    """No operand or intermediate may be a float32 denormal: every non-zero magnitude is at least 2^-126."""
+    for i, a in enumerate(arrays):
+        a = np.abs(np.asarray(a, np.float64))
+        nz = a[a != 0]
+        assert nz.size == 0 or float(nz.min()) >= F32_MIN_NORMAL, '{}: array {} holds a float32 denormal ({})'.format(what, i, nz.min())
+
+
+def pixel_pairs(shape, seed, j=None, jmax=127):
+    """(a, b, j): float32 pixels a = ka / 256, b = kb / 256 in [0, 1] with ka - kb = j, |j| <= jmax (drawn uniformly unless
+    given): a - b = j / 256, 255 (a - b) and 255 a - 255 b are exact in float32."""
+    rng = np.random.default_rng(seed)
+    if j is None:
+        j = rng.integers(-jmax, jmax + 1, size=shape)
+    j = np.asarray(j, np.int64)
+    assert np.abs(j).max(initial=0) <= 127
+    lo, hi = np.maximum(0, -j), np.minimum(256, 256 - j)                   # kb in [lo, hi] keeps ka = kb + j inside [0, 256]
+    kb = lo + np.floor(rng.random(size=j.shape) * (hi - lo + 1)).astype(np.int64)
+    ka = kb + j
+    assert ka.min(initial=0) >= 0 and ka.max(initial=0) <= 256 and kb.min(initial=0) >= 0 and kb.max(initial=0) <= 256
+    return (ka * PIXEL_GRID).astype(np.float32), (kb * PIXEL_GRID).astype(np.float32), j
+
+
+def depth_to_space2(q):
+    """(n, h, w, 4 c) -> (n, 2 h, 2 w, c), the inverse of oracle.tfops.space_to_depth(x, 2): channel (2 pr + pc) c + ch of block
+    (y, x) is pixel (2 y + pr, 2 x + pc), channel ch."""
+    q = np.asarray(q)
+    n, h, w, c4 = q.shape
+    c = c4 // 4
+    return q.reshape(n, h, w, 2, 2, c).transpose(0, 1, 3, 2, 4, 5).reshape(n, 2 * h, 2 * w, c)
+
+
+def space_to_depth2(x):
+    x = np.asarray(x)
+    n, h2, w2, c = x.shape
+    return x.reshape(n, h2 // 2, 2, w2 // 2, 2, c).transpose(0, 1, 3, 2, 4, 5).reshape(n, h2 // 2, w2 // 2, 4 * c)
+
+
+def pack_bits(bits, axis_len=32):
+    """(..., 32) booleans -> (...) int32 words, bit j of a word = element j."""
+    bits = np.asarray(bits).astype(np.uint64)
+    assert bits.shape[-1] == axis_len == 32
+    return (bits << np.arange(32, dtype=np.uint64)).sum(axis=-1).astype(np.uint32).view(np.int32)
