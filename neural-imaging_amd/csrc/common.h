@@ -512,5 +512,20 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace nimg
 
+// ---- functions that cross translation units without being part of the ABI: declared here once, for definer and callers ----
 // zeroed counter words bound to `stream` by nimg_bind_tickets (pointwise.hip), or null when fewer than `words` are bound
 extern "C" unsigned* nimg_internal_tickets(hipStream_t stream, size_t words);
+// wgrad5.hip: slabs written (0 = not its shape, -1 = launch error)
+int nimg_internal_wgrad5_alltaps(const void* in, int cin, const void* g, const unsigned char* idx, int cout, float* partial,
+                                 float* db_partial, int n, int h, int wd, int max_slabs, hipStream_t stream);
+// wgrad3.hip: same contract for the UNet's 3x3 layers (bf16 input(s) and output gradient)
+int nimg_internal_wgrad3_alltaps(const void* in1, int c1, const void* in2, int c2, const void* dz, int cout, float* partial,
+                                 float* db_partial, int n, int h, int wd, int max_slabs, hipStream_t stream, float* dw, float* db,
+                                 int accumulate, const void* pre);
+// conv_small.hip: the tiny-filter weight gradient and its workspace; the few-output-channel forward of nimg_conv2d_fwd
+size_t nimg_internal_wgrad_tiny_bytes(int ks, int cin, int cout);
+int nimg_internal_conv_wgrad_tiny(const float* in, const float* dz, float* dw, int cin, int cout, int n, int h, int wd,
+                                  int ks, int pad, int pad_mode, int accumulate, void* workspace, hipStream_t s, bool bf16_ok);
+int nimg_internal_conv_fewout(const float* in, int cin, const float* w, const float* bias, float* out, int cout, int n,
+                              int h, int wd, int ks, int pad_t, int pad_l, int pad_mode, int hout, int wout,
+                              hipStream_t s);

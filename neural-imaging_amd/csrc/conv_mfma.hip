@@ -18,11 +18,6 @@
 //   the output over two tensors (dgrad of a concat input).
 #include "common.h"
 
-// defined in conv_small.hip
-int nimg_internal_conv_fewout(const float* in, int cin, const float* w, const float* bias, float* out, int cout, int n,
-                              int h, int wd, int ks, int pad_t, int pad_l, int pad_mode, int hout, int wout,
-                              hipStream_t s);
-
 namespace {
 
 using namespace nimg;

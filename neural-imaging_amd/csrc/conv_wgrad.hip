@@ -14,12 +14,6 @@
 // reduces the slabs in a fixed order (deterministic; no float atomics) and also produces the bias gradient.
 #include "common.h"
 
-// defined in conv_small.hip
-size_t nimg_internal_wgrad_tiny_bytes(int ks, int cin, int cout);
-int nimg_internal_conv_wgrad_tiny(const float* in, const float* dz, float* dw, int cin, int cout, int n, int h, int wd,
-                                  int ks, int pad, int pad_mode, int accumulate, void* workspace, hipStream_t s, bool bf16_ok);
-
-
 namespace {
 
 using namespace nimg;

@@ -1,7 +1,7 @@
 // Input gradient of the FAN's fused 5x5 conv + LeakyReLU + MaxPool layers (models/forensics.py:69-77 under tape.gradient) on the
 // STRUCTURED-SPARSITY matrix instruction, throughput mode.  The gradient arriving at such a layer is the 2x2 un-pooling of the
 // pooled gradient g (N, H/2, W/2, Cout): of the four pixels of a pooling window exactly one - the arg-max - carries a channel's
-// value.  conv5_ring_kernel<TN, UNP> (conv_bf16.hip) builds that un-pooled tile in LDS and multiplies the zeros; here
+// value.  conv5_ring_kernel<TN, UNP> (conv_bf16_ring.h) builds that un-pooled tile in LDS and multiplies the zeros; here
 //     din[2a + ey][2b + ex][ci] = sum over the 3 x 3 pooled neighbours (wy, wx), co, window positions (py, px) of
 //         [g[a + wy - 1][b + wx - 1][co] if arg-max == 2 py + px]  x  w[ky][kx][ci][co],
 //         ky = ey + 4 - 2 wy - py,  kx = ex + 4 - 2 wx - px   (0 outside 0..4),

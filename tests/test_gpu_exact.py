@@ -14,8 +14,8 @@ and the arg-max of a pooling window (first maximum on ties) is determined exactl
    max|got - ref| <= 2e-5 max|ref|, bf16 outputs |got - ref| <= 2^-8 |ref| + 2e-5 max|ref| per element - what accumulating in
    less than float32 would break and small integers cannot see.
 
-Kernel reached by each test id (read off the dispatch - ops.conv2d, conv_bf16.hip dispatch_b_t / launch_conv_b, wgrad_bf16_impl,
-wgrad3.hip, wgrad5.hip; it rests on that reading, no kernel trace of the module has been taken).  The 64-channel
+Kernel reached by each test id (read off the dispatch - ops.conv2d, conv_bf16_tile.h dispatch_b_t / launch_conv_b, conv_bf16.hip
+wgrad_bf16_impl, wgrad3.hip, wgrad5.hip; it rests on that reading, no kernel trace of the module has been taken).  The 64-channel
 tiles and with them conv5_ring_kernel<128|64> need >= 384 workgroups of 64 channels (ids ending in -384wg); below that the
 dispatch takes the 32-channel tile, which is what the FAN layer shapes at n = 1 reach (ids tile16buf-tn32-k5-*).
 
