@@ -133,7 +133,8 @@ int nimg_convt2x2_fwd(const float* x, const float* w, const float* bias, float* 
 /* MaxPool2D 2x2 (pipelines.py:197 SAME, forensics.py:70 VALID; identical on even sizes).  Odd sizes follow VALID: y is
  * (n, h/2, w/2, c) with the last row / column dropped, and the backward pass leaves it a zero gradient. */
 int nimg_maxpool2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
-/* dz = (route dp to the FIRST arg-max of each window) [+ add] [* LeakyReLU'(yact)]; add may alias dz */
+/* dz = (route dp to the FIRST arg-max of each window) [+ add] [* LeakyReLU'(yact)]; add may alias dz.  At an odd h or w add must
+ * be null or dz itself (NIMG_ERR_ARG otherwise): the dropped row / column then holds 0, or add [* LeakyReLU'(yact)]. */
 int nimg_maxpool2_bwd(const float* dp, const float* yact, const float* add, float* dz, int n, int h, int w, int c,
                       int apply_lrelu_mask, float alpha, void* stream);
 /* The same two passes on bf16-stored tensors (UNet activations / gradients in throughput mode: pipelines.py:197 and its

@@ -721,40 +721,40 @@ __global__ void sum_final_kernel(const double* __restrict__ partial, int nblocks
 extern "C" {
 
 int nimg_affine(const float* x, float* y, long count, float a, float b, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     hipLaunchKernelGGL(affine_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, a, b);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 
 int nimg_lrelu_fwd(const float* x, float* y, long count, float alpha, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     hipLaunchKernelGGL(lrelu_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, alpha);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 
 int nimg_tanh_fwd(const float* x, float* y, long count, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     hipLaunchKernelGGL(tanh_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 
 int nimg_tanh_bwd(const float* dy, const float* y, float* dx, long count, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!dy || !y || !dx || count < 0) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     hipLaunchKernelGGL(tanh_bwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 
 int nimg_clip01(const float* x, float* y, long count, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     hipLaunchKernelGGL(clip01_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;

@@ -257,6 +257,26 @@ __global__ void maxpool2_bwd_kernel(const float* __restrict__ dp, const float* _
     }
 }
 
+// VALID pooling of an odd size with the skip gradient added in place (add == dz) under the LeakyReLU' mask: the last row
+// and / or column lies in no window, so the kernel above never visits it - its gradient is add * lrelu'(yact).
+__global__ void maxpool2_bwd_border_kernel(const float* __restrict__ yact, float* __restrict__ dz, int n, int h, int w, int c,
+                                           float alpha) {
+    const long rowpart = (h & 1) ? (long)w * c : 0;                 // the last row, every column
+    const long colpart = (w & 1) ? (long)(h & ~1) * c : 0;          // the last column of the rows that are in a window
+    const long per = rowpart + colpart, total = (long)n * per;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long im = i / per, r = i % per;
+        long o;
+        if (r < rowpart) {
+            o = ((im * h + (h - 1)) * w) * c + r;
+        } else {
+            const long q = r - rowpart;
+            o = ((im * h + q / c) * w + (w - 1)) * c + q % c;
+        }
+        dz[o] *= yact[o] > 0.f ? 1.0f : alpha;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Conv2DTranspose(k=2,s=2): out[n,2y+i,2x+j,co] = sum_ci in[n,y,x,ci] * w[i,j,co,ci] + b[co]
 // One workgroup: 16 input pixels x 64 output channels x the 4 taps, Cin streamed through LDS in chunks of 32.
@@ -372,6 +392,9 @@ __global__ void d2s_clip3_bwd_kernel(const float* __restrict__ dy, float* __rest
         dst[2] = make_float4(scale * b1.x, scale * b1.y, scale * b2.x, scale * b2.y);
     }
 }
+// The 32-bit loops below advance an unsigned index by up to 2048 * 256 per trip: a float4 count within one grid stride of 2^32
+// would wrap to a value below total4 and never end, so the dispatch keeps them a whole stride away from 2^32.
+constexpr long D2S_CLIP4_STRIDE = 2048L * 256;
 // co % 4 == 0 (the codec's 128- and 64-channel layers, models/compression.py:233,245): 16-byte granules never straddle a
 // channel block, 32-bit index arithmetic - the per-element forms run at 1.5 TB/s on their 64-bit divisions.
 // Forward: one thread per OUTPUT granule (stores coalesced; loads are runs of co floats).  Backward: per INPUT-gradient granule.
@@ -885,9 +908,16 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const float* __restri
         wt1[tid] = s;
     }
     __syncthreads();
+    // The float32 table sums to 1 - 6e-9 and the outer product of its row sums to 1 - 1.2e-8: on flat regions that residue,
+    // divided by c2, moved the result by 1e-6 (constant images p, q must give (2pq + c1) / (p^2 + q^2 + c1)).  The Gaussian
+    // factor is therefore normalised here, in double; the uniform factor 1 / WIN is left as it is.
+    double wsum = 0.0;
+#pragma unroll
+    for (int k = 0; k < WIN; ++k) wsum += wt1[k];
+    const double wnorm = mode == 0 ? 1.0 : 1.0 / wsum;
     double wt[WIN];
 #pragma unroll
-    for (int k = 0; k < WIN; ++k) wt[k] = wt1[k];
+    for (int k = 0; k < WIN; ++k) wt[k] = wt1[k] * wnorm;
     double sum = 0.0;
     for (int t = blk; t < ntiles; t += blocks_per_image) {
         const int ch = t % c, tile = t / c, ty0 = (tile / tiles_x) * T, tx0 = (tile % tiles_x) * T;
@@ -996,6 +1026,11 @@ int nimg_maxpool2_bwd(const float* dp, const float* yact, const float* add, floa
     if ((h & 1) || (w & 1)) {            /* VALID pooling of an odd size: the dropped last row / column gets no gradient */
         if (add && add != dz) return NIMG_ERR_ARG;
         if (!add && hipMemsetAsync(dz, 0, (size_t)n * h * w * c * sizeof(float), s) != hipSuccess) return NIMG_ERR_LAUNCH;
+        if (add && apply_lrelu_mask) {   /* in place: the dropped elements hold add and still owe the LeakyReLU' factor */
+            const long border = (long)n * (((h & 1) ? (long)w * c : 0) + ((w & 1) ? (long)(h & ~1) * c : 0));
+            hipLaunchKernelGGL(maxpool2_bwd_border_kernel, dim3(grid_for(border)), dim3(256), 0, s, yact, dz, n, h, w, c, alpha);
+            NIMG_CHECK_LAUNCH();
+        }
     }
     if (c % 4 == 0)
         hipLaunchKernelGGL(maxpool2_bwd_kernel<4>, dim3(grid_for((long)n * (h / 2) * (w / 2) * (c / 4))), dim3(256),
@@ -1083,7 +1118,7 @@ int nimg_d2s_clip_fwd(const float* x, float* y, int n, int h, int w, int cout, f
         NIMG_CHECK_LAUNCH();
         return NIMG_OK;
     }
-    if ((cout & 3) == 0 && (long)n * h * w * cout < (1L << 32)) {
+    if ((cout & 3) == 0 && (long)n * h * w * cout < (1L << 32) - D2S_CLIP4_STRIDE) {
         hipLaunchKernelGGL(d2s_clip4_fwd_kernel, dim3(grid_for((long)n * h * w * cout)), dim3(256), 0, (hipStream_t)stream,
                            (const float4*)x, (float4*)y, (unsigned)((long)n * h * w * cout), (unsigned)h, (unsigned)w,
                            (unsigned)(cout >> 2), scale, shift, clip);
@@ -1106,7 +1141,7 @@ int nimg_d2s_clip_bwd(const float* dy, float* dx, int n, int h, int w, int cout,
         NIMG_CHECK_LAUNCH();
         return NIMG_OK;
     }
-    if ((cout & 3) == 0 && (long)n * h * w * cout < (1L << 32)) {
+    if ((cout & 3) == 0 && (long)n * h * w * cout < (1L << 32) - D2S_CLIP4_STRIDE) {
         hipLaunchKernelGGL(d2s_clip4_bwd_kernel, dim3(grid_for((long)n * h * w * cout)), dim3(256), 0, (hipStream_t)stream,
                            (const float4*)dy, (float4*)dx, (unsigned)((long)n * h * w * cout), (unsigned)h, (unsigned)w,
                            (unsigned)(cout >> 2), scale);
@@ -1120,8 +1155,8 @@ int nimg_d2s_clip_bwd(const float* dy, float* dx, int n, int h, int w, int cout,
 }
 
 int nimg_lrelu_bwd(const float* dy, const float* yact, float* dz, long count, float alpha, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!dy || !yact || !dz || count < 0) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     hipLaunchKernelGGL(lrelu_bwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, dy, yact, dz,
                        count, alpha);
     NIMG_CHECK_LAUNCH();
@@ -1129,16 +1164,16 @@ int nimg_lrelu_bwd(const float* dy, const float* yact, float* dz, long count, fl
 }
 
 int nimg_add(const float* a, const float* b, float* out, long count, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!a || !b || !out || count < 0) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     hipLaunchKernelGGL(add_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, a, b, out, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 
 int nimg_add_n(const float* const* inputs, int n_inputs, float* out, long count, void* stream) {
+    if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!inputs || !out || n_inputs < 2 || n_inputs > 6 || count < 0 || (count & 3)) return NIMG_ERR_ARG;
-    if (count == 0) return NIMG_OK;
     const float4* a[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < n_inputs; ++i) {
         if (!inputs[i]) return NIMG_ERR_ARG;
@@ -1318,8 +1353,8 @@ int nimg_adam_step_dev(float* params, const float* grads, float* m, float* v, lo
 /* The step's flag / scalar bookkeeping as kernels of this library (no framework-native launch inside a training step):
  * mode 0: dst[0 .. n) = value;  mode 1: dst[i] = max(dst[i], src[i]) (the workflow's "NaN seen since the last check" word) */
 int nimg_int_words(int* dst, const int* src, long n, int value, int mode, void* stream) {
+    if (n == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!dst || n < 0 || mode < 0 || mode > 1 || (mode == 1 && !src)) return NIMG_ERR_ARG;
-    if (n == 0) return NIMG_OK;
     hipLaunchKernelGGL(int_words_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dst, src, n, value, mode);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1375,8 +1410,8 @@ unsigned* nimg_internal_tickets(hipStream_t stream, size_t words) {
 }
 
 int nimg_float_fill(float* dst, long n, float value, void* stream) {
+    if (n == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!dst || n < 0) return NIMG_ERR_ARG;
-    if (n == 0) return NIMG_OK;
     hipLaunchKernelGGL(float_fill_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dst, n, value);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;

@@ -937,7 +937,10 @@ def maxpool2(x):
     return y
 
 
-def maxpool2_bwd(dp, yact, add=None, apply_mask=True, out=None):
+def maxpool2_bwd(dp, yact, add=None, apply_mask=True, out=None, alpha=None):
+    """dz = (first arg-max of each window ? dp : 0) [+ add], [times LeakyReLU'(yact; alpha, default 0.2)].  Odd sizes pool VALID:
+    the dropped last row / column gets no pooled gradient, so `add` must then be None or `out` itself (in place)."""
+    a = LRELU_ALPHA if alpha is None else float(alpha)
     _fb(dp, yact, add, out)
     n, h, w, c = yact.shape
     dz = torch.empty_like(yact) if out is None else out
@@ -945,11 +948,11 @@ def maxpool2_bwd(dp, yact, add=None, apply_mask=True, out=None):
         if any(t is not None and not _is_bf16(t) for t in (dp, add, dz)):
             raise RuntimeError('maxpool2_bwd on a bf16-stored activation needs bf16-stored gradients')
         _lib.call('nimg_maxpool2_bwd_bf16', _p(dp), _p(yact), _p(add), _p(dz), n, h, w, c, 1 if apply_mask else 0,
-                  LRELU_ALPHA, _stream())
+                  a, _stream())
         return dz
     _f32(dp, add, dz)
     _lib.call('nimg_maxpool2_bwd', _p(dp), _p(yact), _p(add), _p(dz), n, h, w, c, 1 if apply_mask else 0,
-              LRELU_ALPHA, _stream())
+              a, _stream())
     return dz
 
 
@@ -1053,7 +1056,7 @@ def conv2d_dgrad_unpool_out(dz, w, act, skip=None, apply_mask=True, out=None):
     return out
 
 
-def maxpool2_unpool(dp, idx, pooled, apply_mask=True, out=None, out_bf16=False):
+def maxpool2_unpool(dp, idx, pooled, apply_mask=True, out=None, out_bf16=False, alpha=None):
     """Backward of conv2d_pool's epilogue: the pre-activation gradient at full resolution (optionally stored as bf16:
     its consumers - the bf16 weight / input gradient kernels - round it to bf16 anyway)."""
     _f32(pooled)
@@ -1064,7 +1067,7 @@ def maxpool2_unpool(dp, idx, pooled, apply_mask=True, out=None, out_bf16=False):
         out = torch.empty((n, 2 * ho, 2 * wo, c), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=dp.device)
     flags = (BF16_IN if _is_bf16(dp) else 0) | (BF16_OUT if _is_bf16(out) else 0)
     _lib.call('nimg_maxpool2_unpool_ex', _p(dp), _p(idx), _p(pooled), _p(out), n, ho, wo, c, 1 if apply_mask else 0,
-              LRELU_ALPHA, flags, _stream())
+              LRELU_ALPHA if alpha is None else float(alpha), flags, _stream())
     return out
 
 
@@ -1218,6 +1221,8 @@ def add_n(tensors, out=None):
         return tensors[0] if out is None else out.copy_(tensors[0])
     unaligned = any(t.data_ptr() % 16 for t in tensors) or (out is not None and out.data_ptr() % 16)
     if len(tensors) > 6 or (n & 3) or unaligned:          # pairwise chain (the one-pass kernel moves 16-byte vectors)
+        if out is not None:                                # an input that IS `out` goes first: the chain's first store overwrites it
+            tensors = sorted(tensors, key=lambda t: t.data_ptr() != out.data_ptr())          # (stable: the others keep their order)
         o = add(tensors[0], tensors[1], out=out)           # starts from tensors[0] whatever `out` holds
         for t in tensors[2:]:
             o = add(o, t, out=o)
@@ -1676,10 +1681,10 @@ def affine(x, a, b, out=None):
     return y
 
 
-def lrelu(x):
+def lrelu(x, alpha=None):
     _f32(x)
     y = torch.empty_like(x)
-    _lib.call('nimg_lrelu_fwd', _p(x), _p(y), x.numel(), LRELU_ALPHA, _stream())
+    _lib.call('nimg_lrelu_fwd', _p(x), _p(y), x.numel(), LRELU_ALPHA if alpha is None else float(alpha), _stream())
     return y
 
 
@@ -2070,19 +2075,21 @@ ACTIVATIONS = {'leaky_relu': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'softsign': 
 BIG_KERNELS = (4, 6, 7, 8, 9, 10, 11)    # kernel sizes served by the generic float32 kernels only (conv_mfma.hip / conv_wgrad.hip)
 
 
-def activation(x, kind, out=None):
+def activation(x, kind, out=None, alpha=None):
     """activation_mapping[kind](x), element-wise (out may be x)."""
     _f32(x, out)
     y = torch.empty_like(x) if out is None else out
-    _lib.call('nimg_activation_fwd', _p(x), _p(y), x.numel(), ACTIVATIONS[kind], LRELU_ALPHA, _stream())
+    _lib.call('nimg_activation_fwd', _p(x), _p(y), x.numel(), ACTIVATIONS[kind], LRELU_ALPHA if alpha is None else float(alpha),
+              _stream())
     return y
 
 
-def activation_bwd(dy, y, kind, out=None):
+def activation_bwd(dy, y, kind, out=None, alpha=None):
     """dy * activation'(.) taken from the stored output y (out may be dy)."""
     _f32(dy, y, out)
     dx = torch.empty_like(dy) if out is None else out
-    _lib.call('nimg_activation_bwd', _p(dy), _p(y), _p(dx), dy.numel(), ACTIVATIONS[kind], LRELU_ALPHA, _stream())
+    _lib.call('nimg_activation_bwd', _p(dy), _p(y), _p(dx), dy.numel(), ACTIVATIONS[kind],
+              LRELU_ALPHA if alpha is None else float(alpha), _stream())
     return dx
 
 

@@ -453,3 +453,43 @@ def pack_bits(bits, axis_len=32):
     bits = np.asarray(bits).astype(np.uint64)
     assert bits.shape[-1] == axis_len == 32
     return (bits << np.arange(32, dtype=np.uint64)).sum(axis=-1).astype(np.uint32).view(np.int32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# exact-arithmetic tests of the glue kernels (tests/test_gpu_glue_exact.py, tests/glue_cases.py, tests/test_glue_helpers.py):
+# pooling, layout, element-wise streams, SSIM family.  Routing and permutation kernels get operands whose elements differ from
+# one another, so that no transposition, phase swap or lane swap is invisible.
+def distinct_ints(shape, seed, lo=1):
+    """float32 integers lo, lo + 1, ... in a random order, every element different (the count must stay below 2^24)."""
+    count = int(np.prod(shape))
+    assert abs(lo) + count < (1 << 24)
+    return (np.random.default_rng(seed).permutation(count) + lo).reshape(shape).astype(np.float32)
+
+
+def distinct_bf16(shape, seed, period=16001):
+    """float32 array of bfloat16 NUMBERS, normal and finite, of both signs: bit patterns 0x3800 + (a random permutation of the
+    indices modulo `period`), so all elements differ while the count stays within `period`, and any two elements less than
+    `period` apart in the drawing order differ beyond it."""
+    count = int(np.prod(shape))
+    order = np.random.default_rng(seed).permutation(count) if count <= (1 << 22) else np.arange(count)
+    bits = (0x3800 + order % period).astype(np.uint32)
+    bits |= np.where(order % 3 == 0, 0x8000, 0).astype(np.uint32)
+    v = (bits << 16).view(np.float32).reshape(shape)
+    assert np.isfinite(v).all() and np.abs(v).min() >= F32_MIN_NORMAL
+    return v
+
+
+def lane_complete_argmax(shape, seed):
+    """(n, ho, wo, c) random arg-max bytes 0..3 in which every channel lane of every 8-channel granule holds all four values
+    (the first four pixels of the batch are planted: pixel p, channel ch gets (p + ch + ch // 4) % 4)."""
+    n, ho, wo, c = shape
+    idx = np.random.default_rng(seed).integers(0, 4, size=shape).astype(np.uint8)
+    flat = idx.reshape(n * ho * wo, c)
+    assert flat.shape[0] >= 4, 'four pixels are needed to hold all four values in a lane'
+    ch = np.arange(c)
+    for p in range(4):
+        flat[p] = (p + ch + ch // 4) % 4
+    idx = flat.reshape(shape)
+    for lane in range(c):
+        assert set(np.unique(idx[..., lane]).tolist()) == {0, 1, 2, 3}
+    return idx
