@@ -15,7 +15,8 @@ and the arg-max of a pooling window (first maximum on ties) is determined exactl
    less than float32 would break and small integers cannot see.
 
 Kernel reached by each test id (read off the dispatch - ops.conv2d, conv_bf16_tile.h dispatch_b_t / launch_conv_b, conv_bf16.hip
-wgrad_bf16_impl, wgrad3.hip, wgrad5.hip; it rests on that reading, no kernel trace of the module has been taken).  The 64-channel
+wgrad_bf16_impl, wgrad3.hip, wgrad5.hip - and confirmed by one rocprofv3 --kernel-trace --stats run of this module: every kernel
+named below appears in it, with the template arguments the ids say; the table needed no correction).  The 64-channel
 tiles and with them conv5_ring_kernel<128|64> need >= 384 workgroups of 64 channels (ids ending in -384wg); below that the
 dispatch takes the 32-channel tile, which is what the FAN layer shapes at n = 1 reach (ids tile16buf-tn32-k5-*).
 
@@ -41,8 +42,11 @@ dispatch takes the 32-channel tile, which is what the FAN layer shapes at n = 1 
   conv_fwd_kernel / conv_fwd_packed_kernel / conv_fewout_kernel (conv_mfma.hip, conv_small.hip)   parity_fwd / parity_dgrad[f32-*]
   conv_wgrad_kernel / conv_wgrad_packed_kernel / conv_wgrad_tiny_kernel / conv_wgrad_c3k5_kernel  parity_wgrad[f32-*]
 
-Not reached: the kernels behind switches that csrc/ reads ONCE per process (conv5_dgrad_sparse16_kernel: NIMG_DGRAD5S_ACC16,
-conv5_dgrad_sparse_kernel<4>, the 8-wave ring, the 3x3 ring form) - they cannot be toggled inside one pytest process.
+Not reached here: every kernel behind a switch that csrc/ reads ONCE per process - it cannot be toggled inside one pytest process.
+tests/test_gpu_conv_switches.py runs them in child processes (the BUF = false fallbacks of the buffer-load / LDS-DMA / ring routes,
+conv5_dgrad_sparse16_kernel, conv5_dgrad_sparse_kernel<4>, the 8-wave ring, the 3x3 ring, the pixel-major NB = 4 DMA tile, the
+ticket finish of the weight gradients, ...); its header lists what remains unreached even there, with the reasons (the
+NIMG_CONV3_VARIANTS block: compiled out; the ablation switches: not the layer by design).
 """
 import time
 
