@@ -522,6 +522,11 @@ int nimg_internal_wgrad5_alltaps(const void* in, int cin, const void* g, const u
 int nimg_internal_wgrad3_alltaps(const void* in1, int c1, const void* in2, int c2, const void* dz, int cout, float* partial,
                                  float* db_partial, int n, int h, int wd, int max_slabs, hipStream_t stream, float* dw, float* db,
                                  int accumulate, const void* pre);
+// conv_bf16_packed.hip: the few-channel (cin 3 | 4) weight gradient - its split-K factor, and the launch: *a (conv_bf16_wgrad.h)
+// gets the kernel's tiling, splits and db_partial; returns the dw slabs written (db slabs: a->splits), -1 = launch error
+struct WgradArgsB;
+int nimg_internal_wgrad_packed_splits(int cout, int n, int hout, int wout);
+int nimg_internal_wgrad_packed(WgradArgsB* a, int ks, bool want_db, hipStream_t stream);
 // conv_small.hip: the tiny-filter weight gradient and its workspace; the few-output-channel forward of nimg_conv2d_fwd
 size_t nimg_internal_wgrad_tiny_bytes(int ks, int cin, int cout);
 int nimg_internal_conv_wgrad_tiny(const float* in, const float* dz, float* dw, int cin, int cout, int n, int h, int wd,

@@ -1,6 +1,6 @@
 // Shared by the conv_bf16*.hip translation units (throughput mode of the convolutions, see conv_bf16.hip): the kernel
-// parameter blocks, the vector epilogue of the forward / input-gradient kernels, the weight-gradient tile constants and
-// the host functions that cross those files.  The kernel templates live in conv_bf16_tile.h / _ring.h / _dma.h; each
+// parameter block and the vector epilogue of the forward / input-gradient kernels, and the host functions that cross those
+// files (the weight gradient's share: conv_bf16_wgrad.h).  The kernel templates live in conv_bf16_tile.h / _ring.h / _dma.h; each
 // conv_bf16_k*.hip instantiates the dispatch of its own kernel sizes and nothing else.
 #pragma once
 #include <stdlib.h>
@@ -327,6 +327,6 @@ __device__ __forceinline__ void conv_epilogue_vec(const f32x16 (&acc)[MI][NI], c
 // dispatch_b_t<KS, STRIDE, INB> (conv_bf16_tile.h) of one kernel size; instantiated in conv_bf16_k*.hip
 template <int KS, int STRIDE, bool INB>
 int conv_bf16_dispatch(const ConvArgsB& a, hipStream_t s);
-// launch_conv_b<KS, 1, 16, 16, 1, tn32 ? 32 : 64, INB>: the tile the fused conv + pool entry (conv_bf16.hip) asks for
+// launch_conv_b<KS, 1, 16, 16, 1, tn32 ? 32 : 64, INB>: the tile the fused conv + pool entry (conv_bf16_packed.hip) asks for
 template <int KS, bool INB>
 int conv_bf16_launch_16x16(const ConvArgsB& a, bool tn32, hipStream_t s);

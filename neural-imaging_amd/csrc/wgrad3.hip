@@ -1,7 +1,7 @@
 // 3x3 / stride 1 / SAME weight gradient of the UNet's convolutions (models/pipelines.py:191-216 under tape.gradient, :84-88) in
 // throughput mode, bf16-stored operands: the "all taps in one wave" scheme of wgrad5.hip at kernel size 3.
 //
-// conv_wgrad_bf16_kernel<3, ...> (conv_bf16.hip) stages one 8 x 16 tile at a time through registers into a single LDS buffer
+// conv_wgrad_bf16_kernel<3, ...> (conv_bf16_wgrad.hip) stages one 8 x 16 tile at a time through registers into a single LDS buffer
 // behind two barriers; a tile is ~1 us of MFMA work for the two workgroups of a CU, shorter than the global latency of the
 // next tile's loads, so every tile exposes part of a memory round trip (the 19 GFLOP layers take ~40 us at 0.5 PFLOP/s).
 // Here:

@@ -2,7 +2,7 @@
 // throughput mode, "all taps in one wave" form (round 3).  dW[ky][kx][ci][co] = sum over pixels of in[y+ky-2][x+kx-2][ci] *
 // dz[y][x][co], dz = the 2x2 un-pooling of (pooled gradient, arg-max bytes); GEMM view: M = ci, N = co, K = pixels.
 //
-// conv_wgrad_bf16_kernel<5, ...> (conv_bf16.hip) deals the 25 taps to 8 waves: every wave re-reads the dz fragment and one
+// conv_wgrad_bf16_kernel<5, ...> (conv_bf16_wgrad.hip) deals the 25 taps to 8 waves: every wave re-reads the dz fragment and one
 // shifted input fragment per tap (12 ds_read_b64_tr_b16 per 8 MFMAs); all 8 waves of the ONE workgroup a CU holds stage the
 // next tile at the same time behind two barriers (nothing multiplies meanwhile), and a tile costs ~500 instructions of address
 // arithmetic per wave.  Here a wave owns ALL 25 taps of one 16 ci x 32 co block as 25 x 2 accumulators of
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256, 1) void conv5_wgrad_alltaps_kernel(const Wg5Pa
                 *reinterpret_cast<u32x4*>(zp + (pos >> 1) * ZRS + (pos & 1) * ZS) = route(preZ[i], preK[i][0], preK[i][1], (unsigned)pos);
         }
     };
-    // per-lane parts of the transpose-read addresses (ds_read_b64_tr_b16, semantics in conv_bf16.hip "tr_read8"): inside a
+    // per-lane parts of the transpose-read addresses (ds_read_b64_tr_b16, semantics in conv_bf16_wgrad.hip "tr_read8"): inside a
     // 16-lane group lane g addresses pixel (g >> 2) of 4, channels (g & 3)*4 .. +3 of a 16-channel slot, and receives channel
     // g of the 4 pixels - the K(= pixel)-major fragment both MFMA operands need, straight from the pixel-major tiles.
     const int a_lane = q * IRS + (g >> 2) * 64 + ai * 32 + (g & 3) * 8;    // + step row / column, + ky * IRS, + pixel block

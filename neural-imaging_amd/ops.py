@@ -441,6 +441,18 @@ REDUCE_STREAM = _os.environ.get('NIMG_REDUCE_STREAM', '0') == '1'
 _RSTREAM = {'streams': {}, 'dirty': set()}
 
 
+def _reduce_carrier():
+    """Who runs the slab reduction of a side=True weight gradient instead of a launch right behind it: 'defer', 'stream', 'chain'
+    (in this order when several switches are on) or None.  Reads the switches at call time."""
+    if DEFER_REDUCE:
+        return 'defer'
+    if REDUCE_STREAM:
+        return 'stream'
+    if CHAIN_REDUCE:
+        return 'chain'
+    return None
+
+
 def _reduce_behind(k, entry, device):
     """Issue the reduction described by `entry` (owed by the launch just made on side stream k, the current stream) on k's
     reduction stream."""
@@ -808,14 +820,10 @@ def conv2d_wgrad(x, dz, ks, x2=None, stride=1, padding='SAME', pad_mode=0, pads=
                                             (c2 == 0 or c1 % 8 == 0))):
         need = _lib.load().nimg_conv2d_wgrad_bf16_workspace_bytes(c1 + c2, cout, ks, ks, n, ho, wo)
         flags = (BF16_IN if _is_bf16(x) else 0) | (BF16_DZ if _is_bf16(dz) else 0)
-        if _defer_k is not None and DEFER_REDUCE and not accumulate:
-            _wgrad_deferred(_defer_k, x, c1, x2, c2, dz, None, cout, dw, db, n, h, wd, ks, stride, pt, pl, pad_mode, ho, wo, need, flags)
-            return dw
-        if _defer_k is not None and REDUCE_STREAM and not accumulate:
-            _wgrad_reduce_stream(_defer_k, x, c1, x2, c2, dz, None, cout, dw, db, n, h, wd, ks, stride, pt, pl, pad_mode, ho, wo, need, flags)
-            return dw
-        if _defer_k is not None and CHAIN_REDUCE and not accumulate:
-            _wgrad_chained(_defer_k, x, c1, x2, c2, dz, None, cout, dw, db, n, h, wd, ks, stride, pt, pl, pad_mode, ho, wo, need, flags)
+        carrier = _reduce_carrier() if _defer_k is not None and not accumulate else None
+        if carrier:
+            _wgrad_carried(_defer_k, carrier, x.device, need, flags, _p(x), c1, _p(x2), c2, _p(dz), None, cout, _p(dw), _p(db), n, h, wd,
+                           ks, stride, pt, pl, pad_mode, ho, wo)
             return dw
         if _defer_k is not None and CHAIN_REDUCE:
             _flush_chain_here(_defer_k)        # an accumulating launch follows the chain of its stream
@@ -834,47 +842,33 @@ def conv2d_wgrad(x, dz, ks, x2=None, stride=1, padding='SAME', pad_mode=0, pads=
     return dw
 
 
-def _wgrad_deferred(k, x, c1, x2, c2, dz, idx, cout, dw, db, n, h, wd, ks, stride, pt, pl, pad_mode, ho, wo, need, flags):
-    """One weight gradient whose slab reduction joins side stream k's pending batch (the caller is ON that stream)."""
-    import ctypes
-    st = _defer_state(k)
-    if st['n'] == st['cap']:
-        _flush_deferred(k, on_its_stream=False)
-    ws = _SIDE['ws'][k].claim(need, x.device)
-    entry = ctypes.byref(st['buf'], st['n'] * st['nb'])
-    _lib.call('nimg_conv2d_wgrad_bf16_deferred', _p(x), c1, _p(x2), c2, _p(dz), _p(idx), cout, _p(dw), _p(db), n, h, wd, ks, stride,
-              pt, pl, pad_mode, ho, wo, _p(ws), ws.numel(), flags, entry, _stream())
-    st['n'] += 1
-
-
 def _flush_chain_here(k):
     entry = _CHAIN.pop(k, None)
     if entry is not None:
         _lib.call('nimg_reduce_slabs_batch', entry, 1, _stream())
 
 
-def _wgrad_chained(k, x, c1, x2, c2, dz, idx, cout, dw, db, n, h, wd, ks, stride, pt, pl, pad_mode, ho, wo, need, flags):
-    """One weight gradient on side stream k (the current stream): it runs the reduction its predecessor on k owes and leaves its
-    own to its successor (or to the join)."""
+def _wgrad_carried(k, carrier, device, need, flags, *operands):
+    """One weight gradient on side stream k (the current stream) that leaves its slab reduction to `carrier` (_reduce_carrier):
+    'defer' - k's pending batch (_flush_deferred); 'stream' - k's reduction stream; 'chain' - its successor on k (or the join),
+    while it runs the one its predecessor owes.  operands: in1 .. wout of nimg_conv2d_wgrad_bf16_deferred."""
     import ctypes
-    nb = int(_lib.load().nimg_reduce_entry_bytes())
-    pre = _CHAIN.get(k)
-    entry = (ctypes.c_char * nb)()
-    ws = _SIDE['ws'][k].claim(need, x.device)
-    _lib.call('nimg_conv2d_wgrad_bf16_chained', _p(x), c1, _p(x2), c2, _p(dz), _p(idx), cout, _p(dw), _p(db), n, h, wd, ks, stride,
-              pt, pl, pad_mode, ho, wo, _p(ws), ws.numel(), flags, pre, entry, _stream())
-    _CHAIN[k] = entry
-
-
-def _wgrad_reduce_stream(k, x, c1, x2, c2, dz, idx, cout, dw, db, n, h, wd, ks, stride, pt, pl, pad_mode, ho, wo, need, flags):
-    """One weight gradient on side stream k (the current stream) whose slab reduction goes to k's reduction stream."""
-    import ctypes
-    nb = int(_lib.load().nimg_reduce_entry_bytes())
-    entry = (ctypes.c_char * nb)()
-    ws = _SIDE['ws'][k].claim(need, x.device)
-    _lib.call('nimg_conv2d_wgrad_bf16_deferred', _p(x), c1, _p(x2), c2, _p(dz), _p(idx), cout, _p(dw), _p(db), n, h, wd, ks, stride,
-              pt, pl, pad_mode, ho, wo, _p(ws), ws.numel(), flags, entry, _stream())
-    _reduce_behind(k, entry, x.device)
+    if carrier == 'defer':
+        st = _defer_state(k)
+        if st['n'] == st['cap']:
+            _flush_deferred(k, on_its_stream=False)
+        entry = ctypes.byref(st['buf'], st['n'] * st['nb'])
+    else:
+        entry = (ctypes.c_char * int(_lib.load().nimg_reduce_entry_bytes()))()
+    ws = _SIDE['ws'][k].claim(need, device)
+    name, pre = ('nimg_conv2d_wgrad_bf16_chained', (_CHAIN.get(k),)) if carrier == 'chain' else ('nimg_conv2d_wgrad_bf16_deferred', ())
+    _lib.call(name, *operands, _p(ws), ws.numel(), flags, *pre, entry, _stream())
+    if carrier == 'defer':
+        st['n'] += 1
+    elif carrier == 'chain':
+        _CHAIN[k] = entry
+    else:
+        _reduce_behind(k, entry, device)
 
 
 def bias_grad(dz, db=None, accumulate=False, side=False):
@@ -1120,14 +1114,10 @@ def conv2d_wgrad_unpool(x, g, idx, ks, dw, db=None, side=False, _defer_k=None):
     n, h, wd, cin = x.shape
     cout = g.shape[3]
     need = _lib.load().nimg_conv2d_wgrad_bf16_workspace_bytes(cin, cout, ks, ks, n, h, wd)
-    if _defer_k is not None and DEFER_REDUCE and ks == 5 and h % 2 == 0 and wd % 2 == 0:
-        _wgrad_deferred(_defer_k, x, cin, None, 0, g, idx, cout, dw, db, n, h, wd, ks, 1, 2, 2, 0, h, wd, need, BF16_IN | BF16_DZ)
-        return dw
-    if _defer_k is not None and CHAIN_REDUCE and ks == 5 and h % 2 == 0 and wd % 2 == 0:
-        _wgrad_chained(_defer_k, x, cin, None, 0, g, idx, cout, dw, db, n, h, wd, ks, 1, 2, 2, 0, h, wd, need, BF16_IN | BF16_DZ)
-        return dw
-    if _defer_k is not None and REDUCE_STREAM and ks == 5 and h % 2 == 0 and wd % 2 == 0:
-        _wgrad_reduce_stream(_defer_k, x, cin, None, 0, g, idx, cout, dw, db, n, h, wd, ks, 1, 2, 2, 0, h, wd, need, BF16_IN | BF16_DZ)
+    carrier = _reduce_carrier() if _defer_k is not None and ks == 5 and h % 2 == 0 and wd % 2 == 0 else None
+    if carrier:
+        _wgrad_carried(_defer_k, carrier, x.device, need, BF16_IN | BF16_DZ, _p(x), cin, None, 0, _p(g), _p(idx), cout, _p(dw), _p(db),
+                       n, h, wd, ks, 1, 2, 2, 0, h, wd)
         return dw
     ws = _ws_current(x.device).get(need, x.device)
     _lib.call('nimg_conv2d_wgrad_bf16_unpool', _p(x), cin, _p(g), _p(idx), cout, _p(dw), _p(db), n, h, wd, ks, 0, _p(ws),

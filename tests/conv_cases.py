@@ -46,6 +46,7 @@ SWITCHES = {
     'NIMG_CONV3_LOADER': 'excluded:compiled out of the default build (#ifdef NIMG_CONV3_VARIANTS, tools/build_variant.sh only)',
     # conv_bf16.hip
     'NIMG_NO_CONVT_FAT': 'group:fallbacks',
+    # conv_bf16_wgrad.hip
     'NIMG_NO_WGRAD_PAIR8': 'group:fallbacks',
     'NIMG_NO_NARROW_WGRAD': 'group:fallbacks',
     'NIMG_WGRAD5_BLOCKS': 'group:splits',
@@ -89,7 +90,7 @@ PER_CALL = ('NIMG_NO_WGRAD3_ALLTAPS', 'NIMG_WGRAD3_NB', 'NIMG_WGRAD5_W4', 'NIMG_
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# restatement of the split-K plans (conv_bf16.hip splits_for, wgrad3.hip launch, common.h ticket_group): chooses the ticket shapes
+# restatement of the split-K plans (conv_bf16_wgrad.hip splits_for, wgrad3.hip launch, common.h ticket_group): chooses the ticket shapes
 def cdiv(a, b):
     return -(-a // b)
 

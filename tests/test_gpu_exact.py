@@ -14,7 +14,7 @@ and the arg-max of a pooling window (first maximum on ties) is determined exactl
    max|got - ref| <= 2e-5 max|ref|, bf16 outputs |got - ref| <= 2^-8 |ref| + 2e-5 max|ref| per element - what accumulating in
    less than float32 would break and small integers cannot see.
 
-Kernel reached by each test id (read off the dispatch - ops.conv2d, conv_bf16_tile.h dispatch_b_t / launch_conv_b, conv_bf16.hip
+Kernel reached by each test id (read off the dispatch - ops.conv2d, conv_bf16_tile.h dispatch_b_t / launch_conv_b, conv_bf16_wgrad.hip
 wgrad_bf16_impl, wgrad3.hip, wgrad5.hip - and confirmed by one rocprofv3 --kernel-trace --stats run of this module: every kernel
 named below appears in it, with the template arguments the ids say; the table needed no correction).  The 64-channel
 tiles and with them conv5_ring_kernel<128|64> need >= 384 workgroups of 64 channels (ids ending in -384wg); below that the

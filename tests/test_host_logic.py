@@ -101,6 +101,24 @@ def test_side_stream_of_a_gradient_buffer_is_stable():
     assert ops._side_index(None) == 0
 
 
+def test_reduce_carrier_reads_the_three_switches_at_call_time(monkeypatch):
+    """ops._reduce_carrier(): who carries the slab reduction of a side=True weight gradient.  None by default; each switch alone
+    names its carrier; several together: defer, then the reduction stream, then the chain (what conv2d_wgrad did before the two call
+    sites shared this function).  The switches are plain module globals read on every call - the GPU tests patch them after import."""
+    names = ('DEFER_REDUCE', 'REDUCE_STREAM', 'CHAIN_REDUCE')
+    want = {(0, 0, 0): None, (1, 0, 0): 'defer', (0, 1, 0): 'stream', (0, 0, 1): 'chain',
+            (1, 1, 0): 'defer', (1, 0, 1): 'defer', (0, 1, 1): 'stream', (1, 1, 1): 'defer'}
+    for name in names:
+        monkeypatch.setattr(ops, name, False)
+    assert ops._reduce_carrier() is None
+    for on, carrier in want.items():
+        for name, v in zip(names, on):
+            monkeypatch.setattr(ops, name, bool(v))          # (after import, and after earlier calls of the function)
+        assert ops._reduce_carrier() == carrier, on
+    monkeypatch.undo()
+    assert ops._reduce_carrier() == ('defer' if ops.DEFER_REDUCE else 'stream' if ops.REDUCE_STREAM else 'chain' if ops.CHAIN_REDUCE else None)
+
+
 def test_nearest_resample_operator_matches_oracle():
     """method='nearest' of manipulation_resample (tf_helpers.py:68-76): the composed axis operator picks the pixels the restated
     ResizeNearestNeighbor picks; down by 2 keeps the odd pixels (floor((o + 0.5) * 2) = 2 o + 1), up by 2 repeats each twice."""
