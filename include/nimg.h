@@ -54,9 +54,9 @@ extern "C" {
 
 /* library / ABI version, bumped on any change of an existing entry point's signature or data layout (3: nimg_conv2d_fwd_bf16_res
  * gained out_bf16_copy and stride; 5: the arg-max of nimg_conv1_pool_fwd_c4 / nimg_conv1_wgrad_c4 / nimg_conv1_dgrad_pooled is 2 bits
- * per value; 6: the nimg_l3ic_* bitstream entry points).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
+ * per value; 6: the nimg_l3ic_* bitstream entry points; 7: the nimg_jpeg_* baseline codec entry points).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
  * written against. */
-#define NIMG_ABI_VERSION 6
+#define NIMG_ABI_VERSION 7
 int nimg_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -677,6 +677,31 @@ int nimg_l3ic_encode(const uint8_t* idx, int n_streams, int n_sym, uint8_t* out,
                      uint32_t* freq, void* workspace, size_t workspace_bytes, void* stream);
 int nimg_l3ic_decode(const uint8_t* data, const uint32_t* offsets, const uint32_t* lengths, const float* codebook,
                      int codebook_size, float* z, uint32_t* err, int n, int h, int w, int c, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Baseline JPEG codec - replaces the imageio / libjpeg round trip of compress_batch, compression/jpeg_helpers.py:82-114, and with
+ * it the 'libjpeg' codec of JPEG.process, models/jpeg.py:227-233.  The format is libjpeg's with default settings, byte for byte
+ * (DESIGN.md section 4c): one interleaved scan, Annex K Huffman tables, the IJG tables of `quality` 1..100.  A batch shares one
+ * size (h, w in 1..4096), one quality and one sub-sampling (hs, vs) = (1,1) 4:4:4 | (2,1) 4:2:2 | (2,2) 4:2:0; n <= 65535.
+ * Coefficients: int16 [image][Y | Cb | Cr][block row][block col][64 in zig-zag order], the REAL blocks of a component only:
+ * ceil(ceil(w * hc / hs) / 8) columns with hc = hs for Y and 1 for chroma, rows alike.  One workspace size serves all three calls.
+ *   transform    x (n,h,w,3) float32 (is_u8 = 0) or uint8 (is_u8 = 1) -> coef.  Float input goes through the reference's conversion
+ *                (jpeg_helpers.py:92-97): divided by 255 first if any value of the batch exceeds 1, then (255 * x) in float32,
+ *                truncated; clamped to 0..255 where numpy's cast would wrap.
+ *   encode       coef -> out: the entropy-coded segments of all images back to back (stuffed, padded with 1-bits; the 623-byte
+ *                header and EOI are the caller's), lengths[n] their byte counts (jpeg_helpers.py:97-99, imageio.imsave).  No byte
+ *                is written at or beyond out_capacity: a caller that finds sum(lengths) > out_capacity calls again with more.  A
+ *                segment never exceeds 2 * ceil(blocks-in-scan * 1658 / 8) bytes.  Coefficients beyond the baseline range are
+ *                clamped (DC difference to +-2047, AC to +-1023).
+ *   reconstruct  coef -> y (n,h,w,3) float32 = float32(byte) / 255 of the image libjpeg decodes (jpeg_helpers.py:98,101,
+ *                imageio.imread): islow inverse DCT, fancy chroma up-sampling. */
+size_t nimg_jpeg_workspace_bytes(int n, int h, int w, int hs, int vs);
+int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, int vs, int quality, int16_t* coef, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, uint8_t* out, size_t out_capacity, uint32_t* lengths,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int nimg_jpeg_reconstruct(const int16_t* coef, int n, int h, int w, int hs, int vs, int quality, float* y, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -184,6 +184,10 @@ PROTOTYPES = {
     'nimg_l3ic_quantise': (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
     'nimg_l3ic_encode': (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     'nimg_l3ic_decode': (c_int, [P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
+    'nimg_jpeg_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'nimg_jpeg_transform': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'nimg_jpeg_encode': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, c_size_t, P]),
+    'nimg_jpeg_reconstruct': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
 }
 
 ERRORS = {-1: 'NIMG_ERR_ARG (invalid argument / unsupported configuration)',
@@ -193,7 +197,7 @@ ERRORS = {-1: 'NIMG_ERR_ARG (invalid argument / unsupported configuration)',
 _lib = None
 
 
-ABI_VERSION = 6         # include/nimg.h NIMG_ABI_VERSION
+ABI_VERSION = 7         # include/nimg.h NIMG_ABI_VERSION
 TICKET_BYTES = 64 * 1024        # include/nimg.h NIMG_TICKET_BYTES
 
 

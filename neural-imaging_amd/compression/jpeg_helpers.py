@@ -1,11 +1,45 @@
 """
-JPEG table helpers with the reference's names (compression/jpeg_helpers.py:253-310).  jpeg_qtable goes through the
-native library (nimg_jpeg_qtable) so the tables the kernels see are the ones tested bit-exactly against the reference.
-The libjpeg batch codec / bit-stream parser of the reference file are CPU validation tooling and out of scope.
+JPEG helpers with the reference's names (compression/jpeg_helpers.py).
+
+  jpeg_qtable, zigzag, jpeg_qf_estimation (:253-310)   the tables of the differentiable codec; jpeg_qtable goes through the native
+                                                        library (nimg_jpeg_qtable), tested bit-exactly against the reference
+  compress_batch (:82-114), match_quality (:26-79)      the standard codec - the reference's imageio / libjpeg round trip - on the
+                                                        GPU kernels nimg_jpeg_* (format: DESIGN.md section 4c, libjpeg's byte for byte)
+  encode_batch                                          new: the files themselves
+  JPEGMarkerStats (:133-250)                            host parsing of a file's segments
+
+JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
 """
+import struct
+from collections import OrderedDict
+
 import numpy as np
+import torch
 
 from .. import ops
+from ..device import default_device, unwrap
+
+JPEG_HEADER_BYTES = 623           # SOI .. SOS of every file written here
+_DHT_OFFSET = 177
+
+# The four Annex K Huffman table segments as libjpeg writes them (ids 00, 10, 01, 11): 16 counts, then the symbols.
+_DHT = tuple(bytes.fromhex(t) for t in (
+    '00' '00010501010101010100000000000000' '000102030405060708090a0b',
+    '10' '0002010303020403050504040000017d'
+    '01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738'
+    '393a434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5'
+    'a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa',
+    '01' '00030101010101010101010000000000' '000102030405060708090a0b',
+    '11' '00020102040403040705040400010277'
+    '000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a353637'
+    '38393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3'
+    'a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa'))
+
+_BASE_TABLES = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+     100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56) + (99,) * 5 + (47, 66) + (99,) * 38)
 
 
 def jpeg_qtable(quality, channel=0):
@@ -29,3 +63,201 @@ def jpeg_qf_estimation(q_mtx, channel=0):
     """The IJG quality 1..100 whose table of `channel` is closest (mean absolute difference) to q_mtx; ties -> the lowest."""
     tables = np.stack([jpeg_qtable(qf, channel) for qf in range(1, 101)]).astype(np.float64)
     return 1 + int(np.abs(tables - np.asarray(q_mtx, dtype=np.float64)).mean(axis=(1, 2)).argmin())
+
+
+# ---- the standard codec ---------------------------------------------------------------------------------------------------
+def libjpeg_qtable(quality, channel=0):
+    """The table libjpeg itself writes for a quality 1..100, (8,8) int64.  jpeg_qtable above scales by the real number 5000 / q as
+    the reference's Python does; libjpeg divides in integers, so entries differ by 1 or 2 at many qualities below 50 that do
+    not divide 5000.  The files and the kernels (csrc/jpegc.hip make_qtabs) use libjpeg's."""
+    quality = int(min(100, max(1, quality)))
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    t = (np.array(_BASE_TABLES[0 if channel == 0 else 1], np.int64) * scale + 50) // 100
+    return np.clip(t, 1, 255).reshape(8, 8)
+
+
+def jpeg_header(h, w, quality, subsampling='4:4:4'):
+    """The 623 bytes from SOI to the end of SOS, as libjpeg writes them with default settings."""
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
+    out = bytes.fromhex('ffd8' 'ffe00010' '4a46494600' '0101' '00' '0001' '0001' '0000')
+    for t in (0, 1):
+        out += bytes.fromhex('ffdb0043') + bytes([t]) + libjpeg_qtable(quality, t).ravel()[order].astype(np.uint8).tobytes()
+    out += bytes.fromhex('ffc00011' '08') + struct.pack('>HH', h, w) + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, 1])
+    for t in _DHT:
+        out += b'\xff\xc4' + struct.pack('>H', len(t) + 2) + t
+    return out + bytes.fromhex('ffda000c' '03' '0100' '0211' '0311' '00' '3f' '00')
+
+
+def _device_batch(batch_x, keep_bytes, device=None):
+    """numpy / DeviceArray / torch (n,h,w,3) -> contiguous device tensor: uint8 as it is when keep_bytes, everything else float32
+    (the kernel then applies the reference's conversion, jpeg_helpers.py:92-97)."""
+    x = unwrap(batch_x)
+    if not isinstance(x, torch.Tensor):
+        x = np.ascontiguousarray(x if (keep_bytes and x.dtype == np.uint8) else np.asarray(x, dtype=np.float32))
+        x = torch.from_numpy(x if x.flags.writeable else x.copy())          # (torch refuses to wrap read-only memory quietly)
+    dtype = torch.uint8 if (keep_bytes and x.dtype == torch.uint8) else torch.float32
+    dev = x.device if x.is_cuda else (device if device is not None else default_device())
+    return x.to(device=dev, dtype=dtype).contiguous()
+
+
+def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True):
+    """One batch through the GPU codec: x (n,h,w,3) device tensor, float32 or uint8 -> (decoded (n,h,w,3) float32 device tensor or
+    None, list of the entropy-coded segments as bytes or None).  One host synchronisation (for the lengths) when want_bytes."""
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError('Invalid JPEG quality: {}'.format(quality))
+    n, h, w, _ = x.shape
+    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
+    coef = ops.jpeg_transform(x, quality, hs, vs, workspace=ws)
+    segments = None
+    if want_bytes:
+        # room for 3 bytes per sample (random noise at quality 100 needs about 2); the bound is 6.5, and a batch that needs more
+        # than it was given reports so through its lengths and is coded again with exactly what it needs
+        scan = ops.jpeg_geometry(h, w, hs, vs)[1]
+        capacity = n * min(ops.jpeg_ecd_bound(h, w, hs, vs), 192 * scan + 1024)
+        data, lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=capacity)
+        lengths = lengths.cpu().numpy().astype(np.int64)
+        if int(lengths.sum()) > capacity:
+            data, _ = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=int(lengths.sum()))
+        blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
+        ends = np.concatenate([[0], np.cumsum(lengths)])
+        segments = [blob[ends[i]:ends[i + 1]] for i in range(n)]
+    image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if want_image else None
+    return image, segments
+
+
+def encode_batch(batch_x, quality, subsampling='4:4:4'):
+    """The JPEG files of a batch (n,h,w,3) or one image (h,w,3), a list of bytes.  uint8 input is coded as it is; float input goes
+    through the reference's conversion (x / 255 first if its maximum exceeds 1, then (255 x) truncated)."""
+    x = _device_batch(batch_x, keep_bytes=True)
+    if x.dim() == 3:
+        x = x[None]
+    _, segments = device_codec(x, quality, subsampling, want_image=False)
+    head = jpeg_header(x.shape[1], x.shape[2], quality, subsampling)
+    return [head + s + b'\xff\xd9' for s in segments]
+
+
+def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4'):
+    """Compress an image or a batch with the standard JPEG codec (jpeg_helpers.py:82-114).  (h,w,3) -> (float64 image, bytes);
+    (n,h,w,3) -> (float32 batch, list of bytes).  `effective` counts from the first Huffman table on instead of the whole file.
+    Every input, uint8 included, goes through the reference's conversion: x / 255 in float32 if the maximum exceeds 1, then
+    (255 x) truncated - a byte k can come out as k - 1.  Values that numpy's cast would wrap are clamped to 0..255."""
+    x = _device_batch(batch_x, keep_bytes=False)
+    if x.dim() not in (3, 4):
+        raise ValueError('compress_batch needs an (h,w,3) image or an (n,h,w,3) batch')
+    single = x.dim() == 3
+    image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling)
+    sizes = [JPEG_HEADER_BYTES + len(s) + 2 - (_DHT_OFFSET if effective else 0) for s in segments]
+    image = image.cpu().numpy()
+    if single:
+        return np.rint(image[0] * np.float32(255)).astype(np.uint8) / 255, sizes[0]
+    return image, sizes
+
+
+def match_quality(image, target=0.95, match='ssim', subsampling='4:4:4'):
+    """The JPEG quality 1..95 whose SSIM or bpp is closest to `target`, by the reference's bisection (jpeg_helpers.py:26-79)."""
+    from ..helpers import metrics
+    assert image.ndim == 3, 'Only RGB images supported'
+
+    def ssim_gap(q):
+        return metrics.ssim(image, compress_batch(image, q, subsampling=subsampling)[0].squeeze()) - target
+
+    def bpp_gap(q):
+        return 8 * np.mean(compress_batch(image, q, subsampling=subsampling)[1]) / image.shape[0] / image.shape[1] - target
+
+    if match not in ('ssim', 'bpp'):
+        raise ValueError('Invalid argument: match')
+    gap = ssim_gap if match == 'ssim' else bpp_gap
+    low, high = 1, 95
+    gap_low, gap_high = gap(low), gap(high)
+    while high - low > 1:
+        if gap_low * gap_high > 0:
+            raise ValueError('Same deviation for both end-points {} - {}'.format(low, high))
+        mid = (low + high) // 2
+        gap_mid = gap(mid)
+        if gap_mid * gap_high > 0:
+            high, gap_high = mid, gap_mid
+        else:
+            low, gap_low = mid, gap_mid
+    return low if abs(gap_high) > abs(gap_low) else high
+
+
+class JPEGMarkerStats(object):
+    """Where the segments of a baseline JPEG file start (jpeg_helpers.py:133-250): `blocks` maps 'SOI', 'APP:<n>/<index>',
+    'DQT:<id>', 'DCT' (SOF0), 'DHT:<id byte>', 'SOS', 'ECD' and 'EOI' to byte offsets ('EOI' = the file length).  `shape` is read
+    from SOF0 - no decode.  Anything that cannot be parsed, progressive files included, raises IOError."""
+
+    def __init__(self, image):
+        if type(image) is str:
+            with open(image, 'rb') as f:
+                image = f.read()
+        elif type(image) is not bytes:
+            raise ValueError('Image not supported! Supported: str, bytes')
+        self.blocks = OrderedDict()
+        self.shape = None
+        self._quantization_tables = {}
+        try:
+            self._scan(image)
+            if 'EOI' not in self.blocks or self.shape is None:
+                raise ValueError('no frame header or no end of image')
+        except Exception as e:
+            raise IOError('Parsing error: {}'.format(e))
+
+    def _scan(self, data):
+        order = np.argsort(zigzag(8).ravel(), kind='stable')
+        pos, apps = 0, 0
+        self.blocks['SOI'] = 0
+        while pos < len(data):
+            marker, = struct.unpack_from('>H', data, pos)
+            if marker == 0xffd8:
+                pos += 2
+                continue
+            if marker == 0xffd9:
+                self.blocks['EOI'] = pos + 2
+                return
+            size = 2 + struct.unpack_from('>H', data, pos + 2)[0]
+            body = data[pos + 4:pos + size]
+            if marker == 0xffdb:
+                for k in range(0, len(body), 65):
+                    self.blocks['DQT:{}'.format(body[k] & 15)] = pos
+                    table = np.zeros(64, np.uint8)
+                    table[order] = np.frombuffer(body[k + 1:k + 65], np.uint8)
+                    self._quantization_tables[body[k] & 15] = table.reshape(8, 8)
+            elif marker == 0xffc0:
+                self.blocks['DCT'] = pos
+                rows, cols = struct.unpack_from('>HH', body, 1)
+                self.shape = (rows, cols, body[5]) if body[5] > 1 else (rows, cols)
+            elif marker == 0xffc2:
+                raise NotImplementedError('Progressive JPEG images not supported yet')
+            elif marker == 0xffc4:
+                k = 0
+                while k < len(body):
+                    self.blocks['DHT:{}'.format(body[k])] = pos
+                    k += 17 + sum(body[k + 1:k + 17])
+            elif marker == 0xffda:
+                self.blocks['SOS'] = pos
+                self.blocks['ECD'] = pos + size
+                pos = len(data) - 2                      # a valid file ends with EOI; anything else fails on the next read
+                continue
+            elif 0xffe0 <= marker <= 0xffef:
+                self.blocks['APP:{}/{}'.format(marker & 15, apps)] = pos
+                apps += 1
+            elif marker in (0xfffe, 0xffdd):
+                self.blocks['RST'] = pos
+            else:
+                return
+            pos += size
+
+    def get_bytes(self):
+        return self.blocks['EOI']
+
+    def get_effective_bytes(self):
+        return self.blocks['EOI'] - self.blocks['DHT:0']
+
+    def get_effective_bpp(self):
+        return 8 * self.get_effective_bytes() / self.shape[0] / self.shape[1]
+
+    def get_bpp(self):
+        return 8 * self.get_bytes() / self.shape[0] / self.shape[1]

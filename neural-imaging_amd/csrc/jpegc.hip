@@ -1,0 +1,691 @@
+// Baseline JPEG codec: the files libjpeg writes with default settings - one interleaved scan, Annex K
+// Huffman tables, no restart markers - and the images it decodes from them, as integer kernels over a whole batch per launch.
+//   transform    RGB (float32 | uint8, NHWC) -> quantised coefficients, int16 [image][component][block row][block col][64 zig-zag],
+//                real blocks only (colour, edge replication, chroma down-sampling, jfdctint forward DCT, quantisation)
+//   encode       coefficients -> the entropy-coded segments of all images back to back + lengths[n]:
+//                  bit length of every block in scan order (dummy blocks included) | exclusive scan per image | zero the words
+//                  that will be OR-ed into | every block places its bits at its offset (last block: the 1-padding) |
+//                  count the FF bytes per image | scan the segment lengths | scatter the bytes with their 00 stuffing
+//   reconstruct  coefficients -> float32 NHWC (dequantise, jidctint inverse DCT, fancy chroma up-sampling, colour, k / 255)
+// Nothing here loops over images or blocks on the host, and nothing is read back: the caller synchronises once for `lengths`.
+#include "common.h"
+
+namespace {
+
+constexpr int BLOCK_BITS_MAX = 1658;        // DC 9 + 11, 63 x (AC 16 + 10): the longest block with the Annex K tables
+constexpr int SCAN_THREADS = 1024;
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- geometry ---------------------------------------------------------------------------------------------------------
+struct Geo {
+    int n, h, w, hs, vs, hsh;          // hsh = log2(hs)
+    int bhY, bwY, bhC, bwC;            // real extent in blocks: ceil(ceil(W * h / hmax) / 8), the same for the height
+    int ceh, cew;                      // chroma extent in samples: ceil(H / vs), ceil(W / hs)
+    int my, mx, per;                   // MCU grid; blocks per MCU = hs * vs + 2
+    int nbY, nbC, NB;                  // real blocks per image: Y, one chroma component, all three
+    int SB;                            // blocks per image in scan order, dummies included
+    unsigned raw_words;                // capacity of one image's un-stuffed bit buffer, in 32-bit words
+};
+
+bool make_geo(Geo* g, int n, int h, int w, int hs, int vs) {
+    if (n < 1 || n > 65535 || h < 1 || w < 1 || h > 4096 || w > 4096) return false;
+    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
+    g->n = n; g->h = h; g->w = w; g->hs = hs; g->vs = vs; g->hsh = hs - 1;
+    g->bhY = (h + 7) / 8; g->bwY = (w + 7) / 8;
+    g->ceh = (h + vs - 1) / vs; g->cew = (w + hs - 1) / hs;
+    g->bhC = (g->ceh + 7) / 8; g->bwC = (g->cew + 7) / 8;
+    g->my = (h + 8 * vs - 1) / (8 * vs); g->mx = (w + 8 * hs - 1) / (8 * hs);
+    g->per = hs * vs + 2;
+    g->nbY = g->bhY * g->bwY; g->nbC = g->bhC * g->bwC; g->NB = g->nbY + 2 * g->nbC;
+    g->SB = g->my * g->mx * g->per;
+    const unsigned long words = ((unsigned long)g->SB * BLOCK_BITS_MAX + 31) / 32 + 1;
+    g->raw_words = (unsigned)((words + 3) & ~3ul);
+    return (long)n * g->SB < 0x7fffffffL;
+}
+
+struct Workspace {
+    uint32_t* flag;                    // transform: non-zero = some float sample exceeds 1
+    uint32_t* off;                     // [n][SB] bit lengths, then (in place) bit offsets
+    uint32_t* total;                   // [n] bits of an image before the final padding
+    unsigned long long* dst;           // [n] first byte of an image's segment in the output
+    uint32_t* raw;                     // [n][raw_words] the un-stuffed bits, MSB first in every word
+    uint8_t* planes;                   // reconstruct: [n][Y | Cb | Cr] sample planes over the real blocks
+    size_t bytes;
+};
+
+Workspace carve(const Geo& g, void* base) {
+    Workspace ws;
+    uint8_t* p = (uint8_t*)base;
+    ws.flag = (uint32_t*)p; p += 256;
+    ws.off = (uint32_t*)p; p += align256((size_t)g.n * g.SB * 4);
+    ws.total = (uint32_t*)p; p += align256((size_t)g.n * 4);
+    ws.dst = (unsigned long long*)p; p += align256((size_t)g.n * 8);
+    ws.raw = (uint32_t*)p; p += align256((size_t)g.n * g.raw_words * 4);
+    ws.planes = p; p += align256((size_t)g.n * g.NB * 64);
+    ws.bytes = (size_t)(p - (uint8_t*)base);
+    return ws;
+}
+
+// ---- tables -----------------------------------------------------------------------------------------------------------
+// natural index (8 * row + col) of scan position k
+__constant__ const unsigned char c_nat_of_zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
+                                                    12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+                                                    58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// Annex K: codes per length 1..16 and the symbols in code order (as in the DHT segments of every file)
+constexpr int DC_LUMA_BITS[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+constexpr int DC_CHROMA_BITS[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+constexpr int AC_LUMA_BITS[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125};
+constexpr int AC_CHROMA_BITS[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119};
+constexpr char DC_VALS[] = "000102030405060708090a0b";
+constexpr char AC_LUMA_VALS[] =
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738"
+    "393a434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5"
+    "a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa";
+constexpr char AC_CHROMA_VALS[] =
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a353637"
+    "38393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3"
+    "a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa";
+
+struct HuffTabs {
+    uint32_t dc[2][16];        // [luma | chroma][category]: code << 5 | length
+    uint32_t ac[2][256];       // [luma | chroma][run << 4 | category]
+};
+constexpr int hexv(char c) { return c <= '9' ? c - '0' : c - 'a' + 10; }
+constexpr void fill_codes(uint32_t* tab, const int* bits, const char* vals) {
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int j = 0; j < bits[len - 1]; ++j, ++k, ++code) tab[hexv(vals[2 * k]) * 16 + hexv(vals[2 * k + 1])] = code << 5 | len;
+        code <<= 1;
+    }
+}
+constexpr HuffTabs make_tabs() {
+    HuffTabs t{};
+    fill_codes(t.dc[0], DC_LUMA_BITS, DC_VALS);
+    fill_codes(t.dc[1], DC_CHROMA_BITS, DC_VALS);
+    fill_codes(t.ac[0], AC_LUMA_BITS, AC_LUMA_VALS);
+    fill_codes(t.ac[1], AC_CHROMA_BITS, AC_CHROMA_VALS);
+    return t;
+}
+__constant__ const HuffTabs c_huff = make_tabs();
+
+struct QTabs { uint16_t q[2][64]; };        // [luma | chroma], natural order
+
+// libjpeg's tables: jpeg_quality_scaling + jpeg_add_quant_table in integers (5000 / quality is an integer division there)
+QTabs make_qtabs(int quality) {
+    static const int base[2][64] = {
+        {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+         18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+         100, 103, 99},
+        {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+         99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    QTabs t;
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < 64; ++k) {
+            const int v = (base[c][k] * scale + 50) / 100;
+            t.q[c][k] = (uint16_t)(v < 1 ? 1 : (v > 255 ? 255 : v));
+        }
+    return t;
+}
+
+// ---- transform --------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) jpeg_above_one_kernel(const float* __restrict__ x, long count, uint32_t* flag) {
+    bool any = false;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) any |= x[i] > 1.0f;
+    if (__ballot(any) != 0 && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
+// the reference's conversion: (255 * x).astype(uint8) in float32 after an optional x / 255; clamped where numpy would wrap
+__device__ __forceinline__ int byte_of(float v, bool div) {
+    if (div) v = __fdiv_rn(v, 255.0f);
+    const int i = (int)__fmul_rn(255.0f, v);
+    return min(max(i, 0), 255);
+}
+
+template <bool U8>
+__device__ __forceinline__ void load_rgb(const void* img, int w, int y, int x, bool div, int& r, int& g, int& b) {
+    const long i = ((long)y * w + x) * 3;
+    if (U8) {
+        const uint8_t* p = (const uint8_t*)img + i;
+        r = p[0]; g = p[1]; b = p[2];
+    } else {
+        const float* p = (const float*)img + i;
+        r = byte_of(p[0], div); g = byte_of(p[1], div); b = byte_of(p[2], div);
+    }
+}
+
+// sample (y, x) of component `comp` as the forward DCT sees it: the right edge replicated at full resolution, the bottom row up
+// to a multiple of the vertical factor, chroma down-sampled, then the component's last row replicated downwards
+template <bool U8>
+__device__ __forceinline__ int sample(const void* img, const Geo& g, int comp, int y, int x, bool div) {
+    int r, gg, b;
+    if (comp == 0) {
+        load_rgb<U8>(img, g.w, min(y, g.h - 1), min(x, g.w - 1), div, r, gg, b);
+        return (19595 * r + 38470 * gg + 7471 * b + 32768) >> 16;
+    }
+    const int cy = min(y, g.ceh - 1);
+    int sum = 0;
+    for (int dy = 0; dy < g.vs; ++dy)
+        for (int dx = 0; dx < g.hs; ++dx) {
+            load_rgb<U8>(img, g.w, min(cy * g.vs + dy, g.h - 1), min(x * g.hs + dx, g.w - 1), div, r, gg, b);
+            sum += comp == 1 ? (-11059 * r - 21709 * gg + 32768 * b + (128 << 16) + 32767) >> 16
+                             : (32768 * r - 27439 * gg - 5329 * b + (128 << 16) + 32767) >> 16;
+        }
+    if (g.hs == 1) return sum;
+    return g.vs == 2 ? (sum + 1 + (x & 1)) >> 2 : (sum + (x & 1)) >> 1;
+}
+
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// one pass of jfdctint over 8 values S apart; FIRST = the row pass (n = 11, scaled up by 2 bits), else the column pass (n = 15)
+template <int S, bool FIRST>
+__device__ __forceinline__ void fdct8(int* d) {
+    constexpr int n = FIRST ? 11 : 15;
+    const int t0 = d[0] + d[7 * S], t7 = d[0] - d[7 * S], t1 = d[S] + d[6 * S], t6 = d[S] - d[6 * S];
+    const int t2 = d[2 * S] + d[5 * S], t5 = d[2 * S] - d[5 * S], t3 = d[3 * S] + d[4 * S], t4 = d[3 * S] - d[4 * S];
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    d[0] = FIRST ? (t10 + t11) * 4 : descale(t10 + t11, 2);
+    d[4 * S] = FIRST ? (t10 - t11) * 4 : descale(t10 - t11, 2);
+    int z1 = (t12 + t13) * 4433;
+    d[2 * S] = descale(z1 + t13 * 6270, n);
+    d[6 * S] = descale(z1 - t12 * 15137, n);
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * 9633;
+    const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+    z1 *= -7373; z2 *= -20995;
+    z3 = z3 * -16069 + z5;
+    z4 = z4 * -3196 + z5;
+    d[7 * S] = descale(a4 + z1 + z3, n);
+    d[5 * S] = descale(a5 + z2 + z4, n);
+    d[3 * S] = descale(a6 + z2 + z3, n);
+    d[S] = descale(a7 + z1 + z4, n);
+}
+
+// one pass of jidctint; n = 11 for the column pass, 18 for the row pass
+template <int S>
+__device__ __forceinline__ void idct8(int* d, int n) {
+    int z1 = (d[2 * S] + d[6 * S]) * 4433;
+    const int t2 = z1 - d[6 * S] * 15137, t3 = z1 + d[2 * S] * 6270;
+    const int t0 = (d[0] + d[4 * S]) * 8192, t1 = (d[0] - d[4 * S]) * 8192;
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    int a0 = d[7 * S], a1 = d[5 * S], a2 = d[3 * S], a3 = d[S];
+    z1 = a0 + a3;
+    int z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+    const int z5 = (z3 + z4) * 9633;
+    a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299;
+    z1 *= -7373; z2 *= -20995;
+    z3 = z3 * -16069 + z5;
+    z4 = z4 * -3196 + z5;
+    a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+    d[0] = descale(t10 + a3, n); d[7 * S] = descale(t10 - a3, n);
+    d[S] = descale(t11 + a2, n); d[6 * S] = descale(t11 - a2, n);
+    d[2 * S] = descale(t12 + a1, n); d[5 * S] = descale(t12 - a1, n);
+    d[3 * S] = descale(t13 + a0, n); d[4 * S] = descale(t13 - a0, n);
+}
+
+// real block t of the batch -> image, component, block row / column
+__device__ __forceinline__ void locate(const Geo& g, long t, int& img, int& comp, int& br, int& bc) {
+    img = (int)(t / g.NB);
+    int b = (int)(t - (long)img * g.NB);
+    if (b < g.nbY) {
+        comp = 0; br = b / g.bwY; bc = b - br * g.bwY;
+    } else {
+        b -= g.nbY;
+        comp = b < g.nbC ? 1 : 2;
+        b -= (comp - 1) * g.nbC;
+        br = b / g.bwC; bc = b - br * g.bwC;
+    }
+}
+
+// one thread per real block
+template <bool U8>
+__global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restrict__ x, int16_t* __restrict__ coef, Geo g, QTabs qt,
+                                                             const uint32_t* __restrict__ flag) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.NB) return;
+    int img, comp, br, bc;
+    locate(g, t, img, comp, br, bc);
+    const bool div = !U8 && *flag != 0;
+    const void* base = U8 ? (const void*)((const uint8_t*)x + (long)img * g.h * g.w * 3)
+                          : (const void*)((const float*)x + (long)img * g.h * g.w * 3);
+    int d[64];
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) d[8 * r + c] = sample<U8>(base, g, comp, 8 * br + r, 8 * bc + c, div) - 128;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) fdct8<1, true>(d + 8 * r);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) fdct8<8, false>(d + c);
+    const uint16_t* q = qt.q[comp ? 1 : 0];
+    uint32_t o[32];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const int nat = c_nat_of_zz[k];
+        const int v = d[nat], qv = (int)q[nat] << 3;
+        const int m = (int)(((unsigned)abs(v) + (unsigned)(qv >> 1)) / (unsigned)qv);
+        const uint32_t c16 = (uint32_t)(v < 0 ? -m : m) & 0xffffu;
+        if (k & 1) o[k >> 1] |= c16 << 16;
+        else o[k >> 1] = c16;
+    }
+    uint4* dst = reinterpret_cast<uint4*>(coef + t * 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dst[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+}
+
+// ---- entropy coding -----------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// exclusive scan over the SCAN_THREADS threads of a workgroup; wtot: 16 words of LDS; total = the sum of all
+template <typename T>
+__device__ __forceinline__ T block_excl_scan(T v, T* wtot, T& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const T incl = wave_incl_scan(v, lane);
+    __syncthreads();                                   // the previous round's readers are done with wtot
+    if (lane == 63) wtot[wv] = incl;
+    __syncthreads();
+    T run = incl - v, tot = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_THREADS / 64; ++k) {
+        const T s = wtot[k];
+        if (k < wv) run += s;
+        tot += s;
+    }
+    total = tot;
+    return run;
+}
+
+// bit sink: EMIT = false only counts.  Bits are MSB first; word j of the image's buffer holds bits 32 j .. 32 j + 31.  The first
+// and the last word a block touches may be shared with its neighbours: OR-ed into zeroed memory; the words in between are its own.
+template <bool EMIT>
+struct BitSink {
+    uint32_t* base;
+    unsigned widx, cap, count;
+    unsigned long long acc;
+    int nacc;
+    bool first;
+    __device__ __forceinline__ void init(uint32_t* b, unsigned cap_words, unsigned bit0) {
+        base = b; cap = cap_words; widx = bit0 >> 5; nacc = (int)(bit0 & 31u); acc = 0; first = true; count = 0;
+    }
+    __device__ __forceinline__ void put(uint32_t v, int len) {          // len <= 26, v < 2^len
+        count += (unsigned)len;
+        if (!EMIT) return;
+        acc = (acc << len) | v;
+        nacc += len;
+        if (nacc >= 32) {
+            const uint32_t word = (uint32_t)(acc >> (nacc - 32));
+            if (widx < cap) {
+                if (first) atomicOr(base + widx, word);
+                else base[widx] = word;
+            }
+            first = false;
+            ++widx;
+            nacc -= 32;
+            acc &= (1ull << nacc) - 1ull;
+        }
+    }
+    __device__ __forceinline__ void finish() {
+        if (EMIT && nacc > 0 && widx < cap) atomicOr(base + widx, (uint32_t)(acc << (32 - nacc)));
+    }
+};
+
+__device__ __forceinline__ int category(int a) { return 32 - __clz(a); }        // of |value|; 0 for 0
+
+// the DC of Y block k of MCU (mr, mc) as it is coded: a dummy block (beyond the real extent, to the right or below) carries the DC
+// of the block before it in the MCU; block 0 of an MCU is always real
+__device__ __forceinline__ int y_dc(const int16_t* __restrict__ cy, const Geo& g, int mr, int mc, int k, bool& real) {
+    real = true;
+    for (;; --k) {
+        const int br = mr * g.vs + (k >> g.hsh), bc = mc * g.hs + (k & (g.hs - 1));
+        if ((br < g.bhY && bc < g.bwY) || k == 0) return cy[((long)br * g.bwY + bc) * 64];
+        real = false;
+    }
+}
+
+// codes scan block s of one image into `sink`; returns nothing - the sink counts
+template <bool EMIT>
+__device__ __forceinline__ void code_block(const int16_t* __restrict__ ci, const Geo& g, int s, BitSink<EMIT>& sink) {
+    const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.per - 2;
+    const int16_t* blk;
+    int dc, pred, t;
+    bool real = true;
+    if (k < ny) {
+        t = 0;
+        bool dummy_real;
+        dc = y_dc(ci, g, mr, mc, k, dummy_real);
+        real = dummy_real;
+        if (k > 0) pred = y_dc(ci, g, mr, mc, k - 1, dummy_real);
+        else if (m > 0) pred = y_dc(ci, g, (m - 1) / g.mx, (m - 1) % g.mx, ny - 1, dummy_real);
+        else pred = 0;
+        blk = ci + ((long)(mr * g.vs + (k >> g.hsh)) * g.bwY + mc * g.hs + (k & (g.hs - 1))) * 64;
+    } else {                       // the chroma grid is the MCU grid: block m, never a dummy
+        t = 1;
+        blk = ci + ((long)g.nbY + (long)(k - ny) * g.nbC + m) * 64;
+        dc = blk[0];
+        pred = m > 0 ? blk[-64] : 0;
+    }
+    // values beyond what baseline coding can carry are clamped, so a block never exceeds BLOCK_BITS_MAX bits
+    const int diff = min(max(dc - pred, -2047), 2047);
+    int sz = category(abs(diff));
+    uint32_t e = c_huff.dc[t][sz];
+    sink.put(((e >> 5) << sz) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << sz) - 1u)), (int)(e & 31u) + sz);
+    int run = 0;
+    if (real) {
+        const uint4* p = reinterpret_cast<const uint4*>(blk);
+        for (int c = 0; c < 8; ++c) {
+            const uint4 q = p[c];
+            const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (c == 0 && j == 0) continue;
+                int v = (int)(short)(wds[j >> 1] >> (16 * (j & 1)));
+                if (v == 0) { ++run; continue; }
+                v = min(max(v, -1023), 1023);
+                while (run >= 16) {
+                    e = c_huff.ac[t][0xf0];
+                    sink.put(e >> 5, (int)(e & 31u));
+                    run -= 16;
+                }
+                sz = category(abs(v));
+                e = c_huff.ac[t][(run << 4) | sz];
+                sink.put(((e >> 5) << sz) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << sz) - 1u)), (int)(e & 31u) + sz);
+                run = 0;
+            }
+        }
+    } else {
+        run = 63;
+    }
+    if (run > 0) {
+        e = c_huff.ac[t][0];
+        sink.put(e >> 5, (int)(e & 31u));
+    }
+}
+
+__global__ void __launch_bounds__(256) jpeg_bitlen_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, Geo g) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.SB) return;
+    const int img = (int)(t / g.SB), s = (int)(t - (long)img * g.SB);
+    BitSink<false> sink;
+    sink.init(nullptr, 0, 0);
+    code_block<false>(coef + (long)img * g.NB * 64, g, s, sink);
+    len[t] = sink.count;
+}
+
+// one workgroup per image: lengths -> offsets in place, total[image] = the bits before the padding
+__global__ void __launch_bounds__(SCAN_THREADS) jpeg_bitscan_kernel(uint32_t* __restrict__ off, uint32_t* __restrict__ total, int SB) {
+    __shared__ uint32_t wtot[SCAN_THREADS / 64];
+    uint32_t* o = off + (long)blockIdx.x * SB;
+    uint32_t carry = 0;
+    for (int b = 0; b < SB; b += SCAN_THREADS) {
+        const int j = b + threadIdx.x;
+        const uint32_t v = j < SB ? o[j] : 0u;
+        uint32_t sum;
+        const uint32_t ex = block_excl_scan(v, wtot, sum);
+        if (j < SB) o[j] = carry + ex;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) total[blockIdx.x] = carry;
+}
+
+// zeroes the words the bits of an image will be OR-ed into (nothing beyond them, and never beyond the image's slot)
+__global__ void __launch_bounds__(256) jpeg_zero_kernel(uint32_t* __restrict__ raw, const uint32_t* __restrict__ total, unsigned raw_words) {
+    const unsigned img = blockIdx.y;
+    const unsigned need = min(raw_words, ((total[img] + 7u) / 8u + 3u) / 4u);
+    const unsigned i = (blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (i >= need) return;                               // raw_words is a multiple of 4 and the slot 16-byte aligned
+    *reinterpret_cast<uint4*>(raw + (size_t)img * raw_words + i) = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ void __launch_bounds__(256) jpeg_emit_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off,
+                                                        const uint32_t* __restrict__ total, uint32_t* __restrict__ raw, Geo g) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.SB) return;
+    const int img = (int)(t / g.SB), s = (int)(t - (long)img * g.SB);
+    BitSink<true> sink;
+    sink.init(raw + (size_t)img * g.raw_words, g.raw_words, off[t]);
+    code_block<true>(coef + (long)img * g.NB * 64, g, s, sink);
+    if (s == g.SB - 1) {                                 // the last byte is filled up with 1-bits
+        const int pad = (int)((0u - total[img]) & 7u);
+        if (pad) sink.put((1u << pad) - 1u, pad);
+    }
+    sink.finish();
+}
+
+__device__ __forceinline__ unsigned ff_bytes(uint32_t word) {
+    return (unsigned)((word >> 24) == 0xffu) + (unsigned)(((word >> 16) & 0xffu) == 0xffu) +
+           (unsigned)(((word >> 8) & 0xffu) == 0xffu) + (unsigned)((word & 0xffu) == 0xffu);
+}
+
+// one workgroup per image: lengths[image] = its bytes + its FF bytes.  The bytes past the end of the last word are zero.
+__global__ void __launch_bounds__(SCAN_THREADS) jpeg_count_kernel(const uint32_t* __restrict__ raw, const uint32_t* __restrict__ total,
+                                                                  uint32_t* __restrict__ lengths, unsigned raw_words) {
+    __shared__ uint32_t wtot[SCAN_THREADS / 64];
+    const unsigned img = blockIdx.x, nbytes = (total[img] + 7u) / 8u, nwords = min(raw_words, (nbytes + 3u) / 4u);
+    const uint32_t* r = raw + (size_t)img * raw_words;
+    uint32_t cnt = 0;
+    for (unsigned j = threadIdx.x; j < nwords; j += SCAN_THREADS) cnt += ff_bytes(r[j]);
+    uint32_t sum;
+    block_excl_scan(cnt, wtot, sum);
+    if (threadIdx.x == 0) lengths[img] = nbytes + sum;
+}
+
+// one workgroup: dst[image] = sum of the lengths before it
+__global__ void __launch_bounds__(SCAN_THREADS) jpeg_imgscan_kernel(const uint32_t* __restrict__ lengths, unsigned long long* __restrict__ dst,
+                                                                    int n) {
+    __shared__ unsigned long long wtot[SCAN_THREADS / 64];
+    const int per = (n + SCAN_THREADS - 1) / SCAN_THREADS, j0 = min(n, (int)threadIdx.x * per), j1 = min(n, j0 + per);
+    unsigned long long loc = 0, sum;
+    for (int j = j0; j < j1; ++j) loc += lengths[j];
+    unsigned long long run = block_excl_scan(loc, wtot, sum);
+    for (int j = j0; j < j1; ++j) {
+        dst[j] = run;
+        run += lengths[j];
+    }
+}
+
+// one workgroup per image: its bytes to dst[image] + position + FF bytes before it, every FF followed by 00
+__global__ void __launch_bounds__(SCAN_THREADS) jpeg_stuff_kernel(const uint32_t* __restrict__ raw, const uint32_t* __restrict__ total,
+                                                                  const unsigned long long* __restrict__ dst, uint8_t* __restrict__ out,
+                                                                  unsigned long long capacity, unsigned raw_words) {
+    __shared__ uint32_t wtot[SCAN_THREADS / 64];
+    const unsigned img = blockIdx.x, nbytes = (total[img] + 7u) / 8u, nwords = min(raw_words, (nbytes + 3u) / 4u);
+    const uint32_t* r = raw + (size_t)img * raw_words;
+    const unsigned long long d0 = dst[img];
+    uint32_t carry = 0;
+    for (unsigned b = 0; b < nwords; b += SCAN_THREADS) {
+        const unsigned j = b + threadIdx.x;
+        const uint32_t word = j < nwords ? r[j] : 0u;
+        uint32_t sum;
+        uint32_t before = carry + block_excl_scan((uint32_t)ff_bytes(word), wtot, sum);
+        carry += sum;
+        if (j < nwords) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned pos = 4u * j + (unsigned)q;
+                const uint32_t byte = (word >> (24 - 8 * q)) & 0xffu;
+                if (pos < nbytes) {
+                    const unsigned long long at = d0 + pos + before;
+                    if (at < capacity) out[at] = (uint8_t)byte;
+                    if (byte == 0xffu) {
+                        if (at + 1 < capacity) out[at + 1] = 0;
+                        ++before;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- reconstruct --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint8_t* plane_of(uint8_t* planes, const Geo& g, int img, int comp) {
+    return planes + (size_t)img * g.NB * 64 + (comp ? (size_t)g.nbY * 64 + (size_t)(comp - 1) * g.nbC * 64 : 0);
+}
+
+// one thread per real block: dequantise, inverse DCT (columns, then rows), + 128, clamp -> the component's sample plane
+__global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t* __restrict__ coef, uint8_t* __restrict__ planes, Geo g, QTabs qt) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.NB) return;
+    int img, comp, br, bc;
+    locate(g, t, img, comp, br, bc);
+    const uint16_t* q = qt.q[comp ? 1 : 0];
+    const uint4* src = reinterpret_cast<const uint4*>(coef + t * 64);
+    uint32_t wds[32];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint4 v = src[j];
+        wds[4 * j] = v.x; wds[4 * j + 1] = v.y; wds[4 * j + 2] = v.z; wds[4 * j + 3] = v.w;
+    }
+    int d[64];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const int nat = c_nat_of_zz[k];
+        d[nat] = (int)(short)(wds[k >> 1] >> (16 * (k & 1))) * (int)q[nat];
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) idct8<8>(d + c, 11);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) idct8<1>(d + 8 * r, 18);
+    const int stride = 8 * (comp ? g.bwC : g.bwY);
+    uint8_t* p = plane_of(planes, g, img, comp) + (size_t)(8 * br) * stride + 8 * bc;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            lo |= (uint32_t)min(max(d[8 * r + c] + 128, 0), 255) << (8 * c);
+            hi |= (uint32_t)min(max(d[8 * r + 4 + c] + 128, 0), 255) << (8 * c);
+        }
+        *reinterpret_cast<uint2*>(p + (size_t)r * stride) = make_uint2(lo, hi);
+    }
+}
+
+// chroma sample at full-resolution (y, x): libjpeg's "fancy" triangle filter over the component's real extent; with at most two
+// chroma columns libjpeg replicates instead
+__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const Geo& g, int y, int x) {
+    const int stride = 8 * g.bwC;
+    if (g.hs == 1) return p[(size_t)y * stride + x];
+    const int i = x >> 1, j = g.vs == 2 ? y >> 1 : y;
+    if (g.cew <= 2) return p[(size_t)j * stride + i];
+    const int nb = (x & 1) ? min(i + 1, g.cew - 1) : max(i - 1, 0);
+    const uint8_t* near = p + (size_t)j * stride;
+    if (g.vs == 1) return (3 * near[i] + near[nb] + 1 + (x & 1)) >> 2;
+    const uint8_t* far = p + (size_t)((y & 1) ? min(j + 1, g.ceh - 1) : max(j - 1, 0)) * stride;
+    const int si = 3 * near[i] + far[i], sn = 3 * near[nb] + far[nb];
+    return (3 * si + sn + 8 - (x & 1)) >> 4;
+}
+
+// one thread per pixel
+__global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ planes, float* __restrict__ out, Geo g) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.h * g.w) return;
+    const int img = (int)(t / ((long)g.h * g.w)), r = (int)(t - (long)img * g.h * g.w), y = r / g.w, x = r - y * g.w;
+    const int yy = plane_of(planes, g, img, 0)[(size_t)y * 8 * g.bwY + x];
+    const int cb = chroma_at(plane_of(planes, g, img, 1), g, y, x) - 128;
+    const int cr = chroma_at(plane_of(planes, g, img, 2), g, y, x) - 128;
+    const int R = yy + ((91881 * cr + 32768) >> 16);
+    const int G = yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    const int B = yy + ((116130 * cb + 32768) >> 16);
+    float* o = out + t * 3;
+    o[0] = __fdiv_rn((float)min(max(R, 0), 255), 255.0f);
+    o[1] = __fdiv_rn((float)min(max(G, 0), 255), 255.0f);
+    o[2] = __fdiv_rn((float)min(max(B, 0), 255), 255.0f);
+}
+
+inline bool grid_ok(long items, int per_block) { return (items + per_block - 1) / per_block <= 0x7fffffffL; }
+
+}  // namespace
+
+extern "C" {
+
+size_t nimg_jpeg_workspace_bytes(int n, int h, int w, int hs, int vs) {
+    Geo g;
+    if (!make_geo(&g, n, h, w, hs, vs)) return 0;
+    return carve(g, nullptr).bytes;
+}
+
+int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, int vs, int quality, int16_t* coef, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    Geo g;
+    if (!x || !coef || !workspace || quality < 1 || quality > 100 || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    const Workspace ws = carve(g, workspace);
+    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
+    const long blocks = (long)n * g.NB;
+    if (!grid_ok(blocks, 256)) return NIMG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const QTabs qt = make_qtabs(quality);
+    const unsigned grid = (unsigned)((blocks + 255) / 256);
+    if (is_u8) {
+        hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(grid), dim3(256), 0, st, x, coef, g, qt, (const uint32_t*)ws.flag);
+    } else {
+        const long count = (long)n * h * w * 3;
+        if (hipMemsetAsync(ws.flag, 0, 4, st) != hipSuccess) return NIMG_ERR_LAUNCH;
+        hipLaunchKernelGGL(jpeg_above_one_kernel, dim3((unsigned)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096)), dim3(256), 0, st, (const float*)x,
+                           count, ws.flag);
+        NIMG_CHECK_LAUNCH();
+        hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(grid), dim3(256), 0, st, x, coef, g, qt, (const uint32_t*)ws.flag);
+    }
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, uint8_t* out, size_t out_capacity, uint32_t* lengths,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    Geo g;
+    if (!coef || !out || !lengths || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    const Workspace ws = carve(g, workspace);
+    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const long blocks = (long)n * g.SB;
+    const unsigned grid = (unsigned)((blocks + 255) / 256);
+    hipLaunchKernelGGL(jpeg_bitlen_kernel, dim3(grid), dim3(256), 0, st, coef, ws.off, g);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_bitscan_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, ws.off, ws.total, g.SB);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_zero_kernel, dim3((g.raw_words / 4 + 255) / 256, (unsigned)n), dim3(256), 0, st, ws.raw,
+                       (const uint32_t*)ws.total, g.raw_words);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_emit_kernel, dim3(grid), dim3(256), 0, st, coef, (const uint32_t*)ws.off, (const uint32_t*)ws.total, ws.raw,
+                       g);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, (const uint32_t*)ws.raw,
+                       (const uint32_t*)ws.total, lengths, g.raw_words);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_imgscan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, (const uint32_t*)lengths, ws.dst, n);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, (const uint32_t*)ws.raw,
+                       (const uint32_t*)ws.total, (const unsigned long long*)ws.dst, out, (unsigned long long)out_capacity, g.raw_words);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_jpeg_reconstruct(const int16_t* coef, int n, int h, int w, int hs, int vs, int quality, float* y, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    Geo g;
+    if (!coef || !y || !workspace || quality < 1 || quality > 100 || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    const Workspace ws = carve(g, workspace);
+    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
+    const long blocks = (long)n * g.NB, pixels = (long)n * h * w;
+    if (!grid_ok(blocks, 256) || !grid_ok(pixels, 256)) return NIMG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g,
+                       make_qtabs(quality));
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, ws.planes, y, g);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+}  // extern "C"

@@ -6,8 +6,9 @@ JPEG compression models on the fused HIP kernel.  Mirrors the reference's models
   differentiable_jpeg (:38-42)  - lazily created shared instance used by the 'jpeg' manipulation
 
 Differences by design: Q tables are passed to the kernel per call, so the temporary table swap of JPEG.process
-(:235-243, not re-entrant in the reference) has no shared state here.  The 'libjpeg' codec (:227-233) is a CPU
-validation path through imageio and is out of scope - it raises NotImplementedError.
+(:235-243, not re-entrant in the reference) has no shared state here.  The 'libjpeg' codec (:227-233) - the reference's
+final-validation codec, a host round trip through imageio there - is the baseline codec of csrc/jpegc.hip here: libjpeg's
+files and decoded images bit for bit, on the device (compression/jpeg_helpers.py).  It has no gradient.
 """
 import numpy as np
 import torch
@@ -15,7 +16,7 @@ import torch
 from .. import ops
 from ..device import DeviceArray, default_device, to_device
 from ..helpers.utils import is_number
-from ..compression.jpeg_helpers import jpeg_qf_estimation
+from ..compression.jpeg_helpers import device_codec, jpeg_qf_estimation
 from .tfmodel import ParamStore, TFModel
 
 _common_codec = None
@@ -119,7 +120,15 @@ class JPEG(TFModel):
     # forward/backward used by the workflow ----------------------------------------------------------------------
     def forward(self, x, quality=None, training=False, out=None):
         if self._codec_model is None:
-            raise NotImplementedError('the libjpeg codec is CPU validation tooling (out of scope, SURVEY 2 row 10)')
+            if training:
+                raise NotImplementedError('the libjpeg codec has no gradient (the reference has none either): train on a '
+                                          'differentiable codec, validate on this one')
+            # models/jpeg.py:227-233: compress_batch(batch_x, quality)[0] at 4:4:4; the byte counts are not asked for here
+            y, _ = device_codec(x, self.resolve_quality(self.quality if quality is None else quality), want_bytes=False)
+            if out is not None:
+                out.copy_(y)
+                y = out
+            return y, None
         # the quality is resolved FIRST (an invalid / unspecified one raises even with trainable tables); the model's own tables -
         # the learned ones - serve iff the resolved quality is the constructor's, any other quality swaps in its IJG tables for
         # this call (models/jpeg.py:210-243)
@@ -134,6 +143,8 @@ class JPEG(TFModel):
 
     def backward(self, ctx, dy, accumulate=False):
         """d loss / d x; with trainable tables also fills (accumulate: adds to) their gradients in the model's gradient buffer."""
+        if self._codec_model is None:
+            raise NotImplementedError('the libjpeg codec has no gradient')
         if ctx.get('learned'):
             return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec, dq=self._model.flat_grad, accumulate=accumulate)
         return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec)

@@ -2223,3 +2223,86 @@ def l3ic_decode(data, offsets, lengths, codebook, shape):
     _lib.call('nimg_l3ic_decode', _p(data), _p(offsets), _p(lengths), _p(codebook), codebook.numel(), _p(z), _p(err), n, h, w,
               c, _stream())
     return z, err
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# baseline JPEG codec (compression/jpeg_helpers.py, models/jpeg.py 'libjpeg'; include/nimg.h nimg_jpeg_*)
+JPEG_SUBSAMPLING = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
+JPEG_BLOCK_BITS_MAX = 1658       # DC 9 + 11 bits, 63 x (AC 16 + 10)
+
+
+def jpeg_subsampling(subsampling):
+    """'4:4:4' | '4:2:2' | '4:2:0' -> the luma sampling factors (hs, vs)."""
+    if subsampling not in JPEG_SUBSAMPLING:
+        raise ValueError('Unsupported chrominance sub-sampling: {} (4:4:4, 4:2:2 or 4:2:0)'.format(subsampling))
+    return JPEG_SUBSAMPLING[subsampling]
+
+
+def jpeg_geometry(h, w, hs, vs):
+    """(real blocks per image over Y, Cb, Cr; blocks per image in scan order, dummy blocks included; [(rows, cols)] of the real
+    blocks per component)."""
+    comps = [(-(-h // 8), -(-w // 8))] + [(-(-(-(-h // vs)) // 8), -(-(-(-w // hs)) // 8))] * 2
+    scan = -(-h // (8 * vs)) * -(-w // (8 * hs)) * (hs * vs + 2)
+    return sum(r * c for r, c in comps), scan, comps
+
+
+def jpeg_ecd_bound(h, w, hs, vs):
+    """Upper bound of one image's entropy-coded segment in bytes (every block at its longest, every byte stuffed)."""
+    return 2 * -(-jpeg_geometry(h, w, hs, vs)[1] * JPEG_BLOCK_BITS_MAX // 8)
+
+
+def _jpeg_workspace(n, h, w, hs, vs, device, workspace):
+    need = int(_lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs))
+    if need == 0:
+        raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    _chk(workspace)
+    if workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError('JPEG workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
+    return workspace, need
+
+
+def jpeg_transform(x, quality, hs=1, vs=1, workspace=None):
+    """(n,h,w,3) float32 or uint8 -> (n, real blocks, 64) int16 quantised coefficients in zig-zag order, the blocks of an image
+    ordered [Y | Cb | Cr][block row][block col]."""
+    _chk(x)
+    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
+        raise RuntimeError('jpeg_transform needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(x.dtype, tuple(x.shape)))
+    n, h, w, _ = x.shape
+    ws, need = _jpeg_workspace(n, h, w, hs, vs, x.device, workspace)
+    coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
+    _lib.call('nimg_jpeg_transform', _p(x), int(x.dtype == torch.uint8), n, h, w, hs, vs, int(quality), _p(coef), _p(ws), need,
+              _stream())
+    return coef
+
+
+def jpeg_encode(coef, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None):
+    """Coefficients of jpeg_transform -> (entropy-coded segments back to back (uint8), lengths (n,) int32).  No byte is written at
+    or beyond `capacity` (default: the whole of `out`; without `out`: the upper bound, so that every segment fits)."""
+    _chk(coef)
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('jpeg_encode: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    if out is None:
+        out = torch.empty(n * jpeg_ecd_bound(h, w, hs, vs) if capacity is None else int(capacity), dtype=torch.uint8,
+                          device=coef.device)
+    _chk(out)
+    lengths = torch.empty(n, dtype=torch.int32, device=coef.device)
+    _lib.call('nimg_jpeg_encode', _p(coef), n, h, w, hs, vs, _p(out), out.numel() if capacity is None else int(capacity),
+              _p(lengths), _p(ws), need, _stream())
+    return out, lengths
+
+
+def jpeg_reconstruct(coef, h, w, quality, hs=1, vs=1, workspace=None, out=None):
+    """Coefficients of jpeg_transform -> the (n,h,w,3) float32 image libjpeg decodes from them, in [0, 1]."""
+    _chk(coef)
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('jpeg_reconstruct: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    y = torch.empty((n, h, w, 3), dtype=torch.float32, device=coef.device) if out is None else out
+    _f32(y)
+    _lib.call('nimg_jpeg_reconstruct', _p(coef), n, h, w, hs, vs, int(quality), _p(y), _p(ws), need, _stream())
+    return y

@@ -1,0 +1,110 @@
+"""
+Times the baseline JPEG codec (neural_imaging_amd.compression.jpeg_helpers over nimg_jpeg_*) for one configuration with device
+events, after a warm-up:
+  transform    RGB -> quantised coefficients (one kernel; float input: plus the scan for a value above 1)
+  encode       coefficients -> entropy-coded segments and their lengths (seven kernels, one nimg_jpeg_encode call)
+  copy_d2h     the lengths, then the segments, device to host
+  reconstruct  coefficients -> decoded float32 images (two kernels)
+  compress_batch_total   jpeg_helpers.compress_batch on the host batch: upload, the three stages, both downloads
+at 4:4:4 and at 4:2:0, on natural images.  Prints one JSON line per sub-sampling.  --pillow adds the host's time for the same
+images through Pillow (libjpeg), one after the other, where Pillow is installed; it needs no GPU.
+
+    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow]
+For the split of the calls into their kernels: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_time.py ...
+"""
+import argparse
+import importlib
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+importlib.import_module('neural-imaging_amd')
+from neural_imaging_amd import ops  # noqa: E402
+from neural_imaging_amd.compression import jpeg_helpers  # noqa: E402
+from util import natural_images  # noqa: E402
+from src_stamp import csrc_sha16  # noqa: E402
+
+SUBSAMPLINGS = ('4:4:4', '4:2:0')
+
+
+def timed(fn, reps):
+    """median milliseconds of fn() between device events, and its last result"""
+    out, times = None, []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times)), out
+
+
+def measure(x_host, quality, subsampling, reps, dev):
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    n, h, w, _ = x_host.shape
+    x = torch.from_numpy(x_host).to(dev)
+    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
+    ms = {}
+    ms['transform'], coef = timed(lambda: ops.jpeg_transform(x, quality, hs, vs, workspace=ws), reps)
+    ms['encode'], (data, lengths) = timed(lambda: ops.jpeg_encode(coef, h, w, hs, vs, out=out, workspace=ws), reps)
+
+    def copy_out():
+        ln = lengths.cpu().numpy().astype(np.int64)
+        return data[:int(ln.sum())].cpu().numpy(), ln
+    ms['copy_d2h'], (blob, ln) = timed(copy_out, reps)
+    ms['reconstruct'], y = timed(lambda: ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws), reps)
+    ms['compress_batch_total'], (yb, sizes) = timed(lambda: jpeg_helpers.compress_batch(x_host, quality, subsampling=subsampling), reps)
+    assert np.array_equal(yb, y.cpu().numpy()) and sizes == (ln + jpeg_helpers.JPEG_HEADER_BYTES + 2).tolist()
+    return {'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality, 'bytes': int(ln.sum()),
+            'bpp': 8.0 * float(np.mean(sizes)) / h / w, 'ms': {k: round(v, 4) for k, v in ms.items()},
+            'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
+
+
+def pillow(x_host, quality, subsampling, reps):
+    from PIL import Image
+    u8 = np.clip(np.trunc(np.float32(255) * x_host), 0, 255).astype(np.uint8)
+    times = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        for img in u8:
+            buf = io.BytesIO()
+            Image.fromarray(img).save(buf, format='JPEG', quality=quality, subsampling=0 if subsampling == '4:4:4' else 2)
+            np.asarray(Image.open(io.BytesIO(buf.getvalue())))
+        times.append((time.perf_counter() - t) * 1e3)
+    return {'subsampling': subsampling, 'batch': len(u8), 'pillow_ms': round(float(np.median(times)), 3),
+            'pillow_images_per_s': len(u8) / float(np.median(times)) * 1e3}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--size', type=int, default=256)
+    ap.add_argument('--quality', type=int, default=75)
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--pillow', action='store_true', help='time Pillow on the host instead (no GPU needed)')
+    args = ap.parse_args()
+    x = natural_images(args.batch, args.size, args.size, seed=1)
+    if args.pillow:
+        for subsampling in SUBSAMPLINGS:
+            print(json.dumps(pillow(x, args.quality, subsampling, max(3, args.reps // 4))))
+        return
+    if not torch.cuda.is_available():
+        raise SystemExit('jpeg_time.py needs a GPU (or --pillow)')
+    dev = torch.device('cuda', 0)
+    for subsampling in SUBSAMPLINGS:
+        measure(x, args.quality, subsampling, 3, dev)                    # warm-up: code objects, allocator
+        print(json.dumps(dict(measure(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())))
+
+
+if __name__ == '__main__':
+    main()
