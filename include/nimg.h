@@ -54,9 +54,10 @@ extern "C" {
 
 /* library / ABI version, bumped on any change of an existing entry point's signature or data layout (3: nimg_conv2d_fwd_bf16_res
  * gained out_bf16_copy and stride; 5: the arg-max of nimg_conv1_pool_fwd_c4 / nimg_conv1_wgrad_c4 / nimg_conv1_dgrad_pooled is 2 bits
- * per value; 6: the nimg_l3ic_* bitstream entry points; 7: the nimg_jpeg_* baseline codec entry points).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
+ * per value; 6: the nimg_l3ic_* bitstream entry points; 7: the nimg_jpeg_* baseline codec entry points; 8: the per-item
+ * nimg_jpeg_*_items forms and nimg_msssim).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
  * written against. */
-#define NIMG_ABI_VERSION 7
+#define NIMG_ABI_VERSION 8
 int nimg_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -334,6 +335,15 @@ int nimg_msssim_combine(const float* values, const float* items, int scales, int
                         void* stream);
 int nimg_ssim_maps_grad(const float* y, const float* t, const float* maps, const float* coef, float* grad_y, int n,
                         int h, int w, int c, const float* gauss_win, float grad_scale, int accumulate, void* stream);
+/* The metric itself: out[i] = tf.image.ssim_multiscale(a, b, max_val)[i] of two (n,h,w,c) batches, a float64 (its users take
+ * 1 - out[i]) - the five scales of nimg_ssim_planes with nimg_avgpool_fwd (2x2) between them, then
+ * out[i] = mean_c prod_k relu(v[k][i][c]) ^ w[k].  The value of an image does not depend on the rest of the batch: every sum has one
+ * fixed order and is taken over that image alone.  h and w must be multiples of 16 with h / 16, w / 16 >= 11 (TF pads odd scales
+ * symmetrically instead; not built) - workspace_bytes is 0 and the call NIMG_ERR_ARG otherwise.  The workspace holds the pooled
+ * pyramids of both batches, the per-scale values and nimg_ssim_planes' own. */
+size_t nimg_msssim_workspace_bytes(int n, int h, int w, int c);
+int nimg_msssim(const float* a, const float* b, int n, int h, int w, int c, float max_val, const float* gauss_win, double* out,
+                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * GPU-resident training-data feed (helpers/dataset.py:89-131 `Dataset.next_training_batch`, helpers/loading.py:132-211
@@ -702,6 +712,18 @@ int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, u
                      void* workspace, size_t workspace_bytes, void* stream);
 int nimg_jpeg_reconstruct(const int16_t* coef, int n, int h, int w, int hs, int vs, int quality, float* y, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* The item forms: one quality per image, for quality sweeps and per-image searches in one launch.  quality (device, n_items bytes):
+ * item j is coded with libjpeg's tables of quality[j], read from a bank of all 100 built at compile time by the arithmetic of the
+ * single-quality entry points.  A byte outside 1..100 is clamped to that range - no read leaves the bank - and *err (device, zeroed
+ * by the caller) |= 1.  Workspace: nimg_jpeg_workspace_bytes(n_items, ...); nimg_jpeg_encode serves any coefficient tensor as it is.
+ *   transform_items    item j = source image j % n_src of x (n_src,h,w,3): a quality-major sweep of Q qualities over N images
+ *                      (n_items = Q * N) reads the N images in place.  Coefficients as above, n_items images.  The "any value above
+ *                      1" flag of float input stays one per call, taken over the n_src source images.
+ *   reconstruct_items  coef of n_items images -> y (n_items,h,w,3), item j dequantised with the tables of quality[j]. */
+int nimg_jpeg_transform_items(const void* x, int is_u8, int n_src, int h, int w, int hs, int vs, const uint8_t* quality, int n_items,
+                              int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream);
+int nimg_jpeg_reconstruct_items(const int16_t* coef, int n_items, int h, int w, int hs, int vs, const uint8_t* quality, float* y, int* err,
+                                void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -188,6 +188,10 @@ PROTOTYPES = {
     'nimg_jpeg_transform': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
     'nimg_jpeg_encode': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, c_size_t, P]),
     'nimg_jpeg_reconstruct': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'nimg_jpeg_transform_items': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
+    'nimg_jpeg_reconstruct_items': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+    'nimg_msssim_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'nimg_msssim': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]),
 }
 
 ERRORS = {-1: 'NIMG_ERR_ARG (invalid argument / unsupported configuration)',
@@ -197,7 +201,7 @@ ERRORS = {-1: 'NIMG_ERR_ARG (invalid argument / unsupported configuration)',
 _lib = None
 
 
-ABI_VERSION = 7         # include/nimg.h NIMG_ABI_VERSION
+ABI_VERSION = 8         # include/nimg.h NIMG_ABI_VERSION
 TICKET_BYTES = 64 * 1024        # include/nimg.h NIMG_TICKET_BYTES
 
 

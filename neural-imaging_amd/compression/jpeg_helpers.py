@@ -6,6 +6,8 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
   compress_batch (:82-114), match_quality (:26-79)      the standard codec - the reference's imageio / libjpeg round trip - on the
                                                         GPU kernels nimg_jpeg_* (format: DESIGN.md section 4c, libjpeg's byte for byte)
   encode_batch                                          new: the files themselves
+  rate_distortion, match_quality_batch                  new: a whole quality sweep / the bisection of every image of a batch through
+                                                        the item kernels (one quality per item)
   JPEGMarkerStats (:133-250)                            host parsing of a file's segments
 
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
@@ -182,6 +184,125 @@ def match_quality(image, target=0.95, match='ssim', subsampling='4:4:4'):
         else:
             low, gap_low = mid, gap_mid
     return low if abs(gap_high) > abs(gap_low) else high
+
+
+# ---- one quality per item --------------------------------------------------------------------------
+RD_WORKSPACE_BUDGET = 2 << 30          # bytes of codec workspace one item call may take; a longer sweep is cut between qualities
+
+
+def _check_qualities(qualities):
+    q = np.asarray(qualities).reshape(-1)
+    if q.size == 0 or not np.issubdtype(q.dtype, np.number) or (q != np.rint(q)).any() or q.min() < 1 or q.max() > 100:
+        raise ValueError('Invalid JPEG qualities: {} (integers 1..100)'.format(list(np.asarray(qualities).reshape(-1))))
+    return q.astype(np.int64)
+
+
+def _file_bytes(lengths, effective):
+    return JPEG_HEADER_BYTES + lengths + 2 - (_DHT_OFFSET if effective else 0)
+
+
+def _qualities_per_call(n, h, w, hs, vs, total):
+    """How many qualities of a sweep over n images fit one item call: the workspace within RD_WORKSPACE_BUDGET (at least one)."""
+    size = ops._lib.load().nimg_jpeg_workspace_bytes
+    k = max(1, min(total, 65535 // n))
+    while k > 1 and int(size(k * n, h, w, hs, vs)) > RD_WORKSPACE_BUDGET:
+        k -= 1
+    return k
+
+
+def _item_round(x, item_q, hs, vs, want_lengths, want_images):
+    """One item call: source batch x, one quality per item (item j = image j % n) -> (lengths (items,) int32 device tensor or None,
+    decoded (items,h,w,3) device tensor or None).  Nothing is read back."""
+    _, h, w, _ = x.shape
+    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(len(item_q), h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
+    q = ops.jpeg_item_qualities(item_q, len(item_q), x.device)
+    coef, _ = ops.jpeg_transform_items(x, q, hs, vs, workspace=ws)
+    lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=1)[1] if want_lengths else None      # byte counts only
+    y = ops.jpeg_reconstruct_items(coef, h, w, q, hs, vs, workspace=ws)[0] if want_images else None
+    return lengths, y
+
+
+def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, want_images=False):
+    """The rate-distortion table of a batch (n,h,w,3) over Q qualities: a dict of (Q, n) arrays 'ssim', 'psnr', 'msssim', 'msssim_db'
+    (helpers.metrics of the source against what libjpeg decodes), 'bytes' and 'bpp' (compress_batch's count: the whole file, or from
+    the first Huffman table on when `effective`).  With want_images also the decoded (Q,n,h,w,3) device tensor.  The batch is
+    uploaded once and coded as Q * n items - one transform, one encode and one reconstruct call, or one set per group of qualities
+    where the workspace would exceed RD_WORKSPACE_BUDGET - and the numbers come back in one download."""
+    from ..helpers import metrics
+    q = _check_qualities(qualities)
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    x = _device_batch(batch_x, keep_bytes=False)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError('rate_distortion needs an (n,h,w,3) batch')
+    n, h, w, _ = x.shape
+    step = _qualities_per_call(n, h, w, hs, vs, len(q))
+    rows, images = [], []
+    for k0 in range(0, len(q), step):
+        part = q[k0:k0 + step]
+        lengths, y = _item_round(x, np.repeat(part, n), hs, vs, True, True)           # quality-major: item j = (part[j // n], image j % n)
+        y = y.view(len(part), n, h, w, 3)
+        for k in range(len(part)):
+            ms = metrics._msssim_device(x, y[k])
+            rows.append(torch.stack([ops.ssim(x, y[k], mode='skimage', max_val=1.0).double(),
+                                     10.0 * torch.log10(1.0 / metrics._mean_per_image(x, y[k], lambda d: d * d)),
+                                     torch.full((n,), float('nan'), dtype=torch.float64, device=x.device) if ms is None else ms.double(),
+                                     lengths[k * n:(k + 1) * n].double()]))
+        if want_images:
+            images.append(y)
+    table = torch.stack(rows).cpu().numpy()                            # (Q, 4, n): the one download
+    size = _file_bytes(table[:, 3].astype(np.int64), effective)
+    with np.errstate(divide='ignore'):
+        out = {'ssim': table[:, 0], 'psnr': table[:, 1], 'msssim': table[:, 2], 'msssim_db': -10.0 * np.log10(1.0 - table[:, 2]),
+               'bytes': size, 'bpp': 8 * size / h / w}
+    if want_images:
+        return out, (images[0] if len(images) == 1 else torch.cat(images))
+    return out
+
+
+def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4'):
+    """match_quality for every image of a batch (n,h,w,3) at once: the reference's bisection over 1..95, where each round is one item
+    call in which image i carries its own current quality - 8 calls whatever n is (the two end points share the first).  `target`
+    is a scalar or one value per image.  Returns an int array (n,).  An image whose end points do not bracket its target raises the
+    reference's ValueError, naming the first such image."""
+    if match not in ('ssim', 'bpp'):
+        raise ValueError('Invalid argument: match')
+    shape = tuple(unwrap(batch_x).shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError('match_quality_batch needs an (n,h,w,3) batch')
+    n, h, w, _ = shape
+    target = np.asarray(target, dtype=np.float64)
+    if target.ndim > 1 or (target.ndim == 1 and len(target) != n):
+        raise ValueError('target: a scalar or {} values needed, got shape {}'.format(n, target.shape))
+    target = np.broadcast_to(target, (n,))
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    x = _device_batch(batch_x, keep_bytes=False)
+
+    def gaps(item_q):            # item j = image j % n at item_q[j] -> its gap to the target, as match_quality's ssim_gap / bpp_gap
+        reps = len(item_q) // n
+        if match == 'ssim':
+            _, y = _item_round(x, item_q, hs, vs, False, True)
+            v = torch.cat([ops.ssim(x, y[r * n:(r + 1) * n], mode='skimage', max_val=1.0) for r in range(reps)]).double().cpu().numpy()
+        else:
+            lengths, _ = _item_round(x, item_q, hs, vs, True, False)
+            v = 8 * _file_bytes(lengths.cpu().numpy().astype(np.float64), False) / h / w
+        return v - np.tile(target, reps)
+
+    low, high = np.full(n, 1, np.int64), np.full(n, 95, np.int64)
+    ends = gaps(np.concatenate([low, high]))
+    gap_low, gap_high = ends[:n].copy(), ends[n:].copy()
+    while (high - low > 1).any():
+        active = high - low > 1
+        same = active & (gap_low * gap_high > 0)
+        if same.any():
+            i = int(np.flatnonzero(same)[0])
+            raise ValueError('Same deviation for both end-points {} - {} (image {})'.format(low[i], high[i], i))
+        mid = np.where(active, (low + high) // 2, low)               # a finished image rides along at a quality it has seen
+        gap_mid = gaps(mid)
+        up = active & (gap_mid * gap_high > 0)
+        down = active & ~up
+        high[up], gap_high[up] = mid[up], gap_mid[up]
+        low[down], gap_low[down] = mid[down], gap_mid[down]
+    return np.where(np.abs(gap_high) > np.abs(gap_low), low, high)
 
 
 class JPEGMarkerStats(object):

@@ -1988,6 +1988,23 @@ def msssim_loss(y, t, grad_scale=None, grad_out=None, accumulate=False, max_val=
     return loss, acc
 
 
+def msssim(a, b, max_val=1.0):
+    """Per-image tf.image.ssim_multiscale of two (N,H,W,C) batches -> (N,) float64 (its consumers need 1 - value): the five scales and the combination of
+    msssim_loss, one value per image instead of the batch mean, and no image's value depends on the others.  Same size rule."""
+    _f32(a, b)
+    n, h, w, c = a.shape
+    if tuple(b.shape) != tuple(a.shape):
+        raise ValueError('Incompatible tensor shapes! {} and {}'.format(tuple(a.shape), tuple(b.shape)))
+    div = 1 << (MSSSIM_SCALES - 1)
+    if h % div or w % div or h // div < 11 or w // div < 11:
+        raise ValueError('MS-SSIM needs image sizes that are multiples of {} and at least {} pixels'.format(div, 11 * div))
+    out = torch.empty((n,), dtype=torch.float64, device=a.device)
+    ws = torch.empty(int(_lib.load().nimg_msssim_workspace_bytes(n, h, w, c)), dtype=torch.uint8, device=a.device)   # the pyramids
+    _lib.call('nimg_msssim', _p(a), _p(b), n, h, w, c, float(max_val), _p(_ssim_window(a.device)), _p(out), _p(ws), ws.numel(),
+              _stream())
+    return out
+
+
 IMAGE_LOSSES = {'L2': mse255, 'L1': mae255, 'SSIM': ssim_loss, 'MS-SSIM': msssim_loss}
 
 
@@ -2306,3 +2323,54 @@ def jpeg_reconstruct(coef, h, w, quality, hs=1, vs=1, workspace=None, out=None):
     _f32(y)
     _lib.call('nimg_jpeg_reconstruct', _p(coef), n, h, w, hs, vs, int(quality), _p(y), _p(ws), need, _stream())
     return y
+
+
+def jpeg_item_qualities(quality, n_items, device):
+    """One quality per item as the item kernels read them: a (n_items,) uint8 device tensor.  Values given on the host are checked
+    here (1..100); a device tensor is taken as it is - the kernels clamp what they find and say so through their error flag."""
+    if isinstance(quality, torch.Tensor) and quality.is_cuda:
+        _chk(quality)
+        if quality.dtype != torch.uint8 or quality.numel() != n_items:
+            raise RuntimeError('item qualities: {} uint8 values needed, got {} {}'.format(n_items, quality.dtype, tuple(quality.shape)))
+        return quality
+    q = np.asarray(quality.cpu() if isinstance(quality, torch.Tensor) else quality).reshape(-1)
+    if q.size != n_items:
+        raise ValueError('item qualities: {} values needed, got {}'.format(n_items, q.size))
+    bad = np.ones(q.shape, bool) if not np.issubdtype(q.dtype, np.number) else (q != np.rint(q)) | (q < 1) | (q > 100)
+    if bad.any():
+        raise ValueError('Invalid JPEG quality: {} (integers 1..100)'.format(q[bad][0]))
+    return torch.from_numpy(q.astype(np.uint8)).to(device)
+
+
+def jpeg_transform_items(x, quality, hs=1, vs=1, workspace=None, err=None):
+    """(n_src,h,w,3) float32 or uint8 and one quality per item -> ((n_items, real blocks, 64) int16 coefficients laid out as
+    jpeg_transform's, (1,) int32 error flag: non-zero = a quality byte outside 1..100 was clamped).  Item j codes source image
+    j % n_src at quality[j]; n_items = len(quality), so a quality-major sweep reads the sources in place."""
+    _chk(x)
+    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
+        raise RuntimeError('jpeg_transform_items needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(x.dtype, tuple(x.shape)))
+    n_src, h, w, _ = x.shape
+    n_items = int(quality.numel() if isinstance(quality, torch.Tensor) else np.size(quality))
+    q = jpeg_item_qualities(quality, n_items, x.device)
+    ws, need = _jpeg_workspace(n_items, h, w, hs, vs, x.device, workspace)
+    coef = torch.empty((n_items, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
+    err = torch.zeros((1,), dtype=torch.int32, device=x.device) if err is None else err
+    _lib.call('nimg_jpeg_transform_items', _p(x), int(x.dtype == torch.uint8), n_src, h, w, hs, vs, _p(q), n_items, _p(coef), _p(err),
+              _p(ws), need, _stream())
+    return coef, err
+
+
+def jpeg_reconstruct_items(coef, h, w, quality, hs=1, vs=1, workspace=None, out=None, err=None):
+    """Coefficients of n_items images and one quality per item -> ((n_items,h,w,3) float32 decoded images, (1,) int32 error flag as
+    jpeg_transform_items')."""
+    _chk(coef)
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('jpeg_reconstruct_items: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    q = jpeg_item_qualities(quality, n, coef.device)
+    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    y = torch.empty((n, h, w, 3), dtype=torch.float32, device=coef.device) if out is None else out
+    _f32(y)
+    err = torch.zeros((1,), dtype=torch.int32, device=coef.device) if err is None else err
+    _lib.call('nimg_jpeg_reconstruct_items', _p(coef), n, h, w, hs, vs, _p(q), _p(y), _p(err), _p(ws), need, _stream())
+    return y, err
