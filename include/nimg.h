@@ -55,7 +55,8 @@ extern "C" {
 /* library / ABI version, bumped on any change of an existing entry point's signature or data layout (3: nimg_conv2d_fwd_bf16_res
  * gained out_bf16_copy and stride; 5: the arg-max of nimg_conv1_pool_fwd_c4 / nimg_conv1_wgrad_c4 / nimg_conv1_dgrad_pooled is 2 bits
  * per value; 6: the nimg_l3ic_* bitstream entry points; 7: the nimg_jpeg_* baseline codec entry points; 8: the per-item
- * nimg_jpeg_*_items forms and nimg_msssim).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
+ * nimg_jpeg_*_items forms and nimg_msssim; version 8 also carries the later, purely added nimg_jpeg_decode* and
+ * nimg_jpeg_reconstruct_tables entry points).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
  * written against. */
 #define NIMG_ABI_VERSION 8
 int nimg_abi_version(void);
@@ -724,6 +725,32 @@ int nimg_jpeg_transform_items(const void* x, int is_u8, int n_src, int h, int w,
                               int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream);
 int nimg_jpeg_reconstruct_items(const int16_t* coef, int n_items, int h, int w, int hs, int vs, const uint8_t* quality, float* y, int* err,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* Decoding baseline JPEG files.  The caller parses the headers; the device takes the entropy-coded segments
+ * of n files of one geometry and their Huffman tables and leaves the coefficient tensor described above.
+ *   ecd        (device) the segments back to back, as they stand in the files (stuffed); segment i = bytes ecd_off[i] .. ecd_off[i+1]
+ *   ecd_off    (device) n + 1 ascending byte offsets; ecd_off[n] <= the ecd_bytes the workspace was sized for, and ecd is readable
+ *              up to ecd_off[n].  There is no ecd_bytes argument: the device checks the offsets against the largest total the given
+ *              workspace could serve, so a workspace larger than nimg_jpeg_decode_workspace_bytes asked for loosens that check (and
+ *              lengthens the clearing of the un-stuffed buffer) - pass the size that was asked for
+ *   huffman    (device) [n][6][16 + 256] bytes: per image the tables Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC, each the 16 counts of
+ *              its DHT body followed by the symbols in code order (unused symbol bytes are ignored)
+ *   subseq_bits  the stream of an image is decoded by one thread per subsequence of this many bits: a multiple of 32 up to 2^30,
+ *              0 = the default (2048); a value at least as large as the stream is a sequential decode
+ *   status     (device) [n], written: 0 = decoded, else bits 1 marker inside the segment | 2 invalid code | 4 zig-zag index past 63 |
+ *              8 category out of range | 16 bits needed beyond the end | 32 fewer blocks than the scan has | 64 DC outside int16 |
+ *              128 DHT counts that are no prefix code | 256 bad offsets.  Nothing is read or written out of bounds whatever the
+ *              bits say; coefficients of an image with a non-zero status are unspecified.
+ *   rounds     (device, optional) [n]: synchronisation rounds image i took, at most its number of subsequences - 1
+ * nimg_jpeg_reconstruct_tables is nimg_jpeg_reconstruct with the quantisation tables given per image and component instead of a
+ * quality: qtabs (device) [n][3][64] uint16 in natural order; y is (n,h,w,3) uint8 - the decoded bytes - when out_u8, else float32
+ * = float32(byte) / 255.  Its workspace is nimg_jpeg_workspace_bytes. */
+size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, size_t ecd_bytes, int subseq_bits);
+int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                     int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

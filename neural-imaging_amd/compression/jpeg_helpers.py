@@ -6,6 +6,10 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
   compress_batch (:82-114), match_quality (:26-79)      the standard codec - the reference's imageio / libjpeg round trip - on the
                                                         GPU kernels nimg_jpeg_* (format: DESIGN.md section 4c, libjpeg's byte for byte)
   encode_batch                                          new: the files themselves
+  parse_header, decode_batch, decode_coefficients       new: the way back - any baseline file (its own quantisation and Huffman tables,
+                                                        optimised ones included) decoded on the GPU to the bytes imageio.imread returns;
+                                                        headers are parsed on the host, the entropy decoder is the parallel Huffman
+                                                        decoder of DESIGN.md section 4e (nimg_jpeg_decode, nimg_jpeg_reconstruct_tables)
   rate_distortion, match_quality_batch                  new: a whole quality sweep / the bisection of every image of a batch through
                                                         the item kernels (one quality per item)
   JPEGMarkerStats (:133-250)                            host parsing of a file's segments
@@ -13,7 +17,7 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
 """
 import struct
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -303,6 +307,238 @@ def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4')
         high[up], gap_high[up] = mid[up], gap_mid[up]
         low[down], gap_low[down] = mid[down], gap_mid[down]
     return np.where(np.abs(gap_high) > np.abs(gap_low), low, high)
+
+
+# ---- reading files ---------------------------------------------------------------------------------
+JPEGHeader = namedtuple('JPEGHeader', 'h w hs vs qtables huffman ecd_offset ecd_end')
+JPEG_STATUS_BITS = OrderedDict([(1, 'marker inside the entropy-coded segment'), (2, 'invalid Huffman code'), (4, 'zig-zag index past 63'),
+                                (8, 'coefficient category out of range'), (16, 'bits needed beyond the end of the stream'),
+                                (32, 'fewer blocks than the scan has'), (64, 'DC value outside int16'),
+                                (128, 'Huffman table that is no prefix code'), (256, 'bad segment offsets')])
+_MAX_SIDE = 4096
+_SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless', 0xc5: 'differential sequential',
+              0xc6: 'differential progressive', 0xc7: 'differential lossless', 0xc9: 'arithmetic-coded sequential',
+              0xca: 'arithmetic-coded progressive', 0xcb: 'arithmetic-coded lossless', 0xcd: 'arithmetic-coded differential sequential',
+              0xce: 'arithmetic-coded differential progressive', 0xcf: 'arithmetic-coded differential lossless'}
+
+
+def parse_header(data):
+    """The header of a baseline JPEG file, read on the host without decoding: JPEGHeader(h, w, hs, vs, qtables (3, 64) uint16 in
+    natural order per component, huffman = six (16 counts, symbols) pairs of bytes in the order Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC
+    as the DHT bodies have them, ecd_offset, ecd_end = the offset of the final FFD9).  Accepted: SOF0 with 8-bit samples, three
+    components in one interleaved scan, luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma, any 8-bit quantisation and any Huffman tables
+    in any assignment, no restart interval; APPn and COM are skipped.  Every other file raises ValueError naming the reason."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError('JPEG data: bytes needed, got {}'.format(type(data).__name__))
+    data = bytes(data)
+    if data[:2] != b'\xff\xd8':
+        raise ValueError('not a JPEG file: no SOI marker')
+    order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
+    qt, huff, frame, pos = {}, {}, None, 2
+    while True:
+        if pos + 4 > len(data):
+            raise ValueError('truncated file: no SOS marker')
+        if data[pos] != 0xff:
+            raise ValueError('no marker at offset {}'.format(pos))
+        marker = data[pos + 1]
+        if marker == 0xff:                                               # fill byte
+            pos += 1
+            continue
+        if marker == 0xd9:
+            raise ValueError('EOI before any scan')
+        if marker == 0xd8 or marker == 0x01 or 0xd0 <= marker <= 0xd7:
+            raise ValueError('unexpected marker FF{:02X} in the header'.format(marker))
+        size = struct.unpack_from('>H', data, pos + 2)[0]
+        if size < 2 or pos + 2 + size > len(data):
+            raise ValueError('truncated segment FF{:02X} at offset {}'.format(marker, pos))
+        body = data[pos + 4:pos + 2 + size]
+        if marker == 0xdb:
+            k = 0
+            while k < len(body):
+                if body[k] >> 4:
+                    raise ValueError('16-bit quantisation table (DQT precision {})'.format(body[k] >> 4))
+                if (body[k] & 15) > 3 or k + 65 > len(body):
+                    raise ValueError('malformed DQT segment')
+                table = np.zeros(64, np.uint16)
+                table[order] = np.frombuffer(body[k + 1:k + 65], np.uint8)
+                qt[body[k] & 15] = table
+                k += 65
+        elif marker == 0xc4:
+            k = 0
+            while k < len(body):
+                if k + 17 > len(body) or (body[k] >> 4) > 1 or (body[k] & 15) > 3:
+                    raise ValueError('malformed DHT segment')
+                count = sum(body[k + 1:k + 17])
+                if count > 256 or k + 17 + count > len(body):
+                    raise ValueError('malformed DHT segment')
+                huff[body[k]] = (bytes(body[k + 1:k + 17]), bytes(body[k + 17:k + 17 + count]))
+                k += 17 + count
+        elif marker == 0xc0:
+            if frame is not None:
+                raise ValueError('several frame headers')
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise ValueError('malformed SOF0 segment')
+            if body[0] != 8:
+                raise ValueError('{}-bit samples (only 8-bit baseline files are read)'.format(body[0]))
+            h, w, ncomp = struct.unpack_from('>HH', body, 1) + (body[5],)
+            if ncomp != 3:
+                raise ValueError('{} (3 components needed, the file has {})'.format(
+                    {1: 'grey-scale file', 4: 'CMYK / four-component file'}.get(ncomp, 'unsupported number of components'), ncomp))
+            if h < 1 or w < 1 or h > _MAX_SIDE or w > _MAX_SIDE:
+                raise ValueError('unsupported size {}x{} (1..{} per side)'.format(h, w, _MAX_SIDE))
+            comps = [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(3)]
+            sampling = tuple(c[1:3] for c in comps)
+            if sampling[0] not in ((1, 1), (2, 1), (2, 2)) or sampling[1:] != ((1, 1), (1, 1)):
+                raise ValueError('unsupported sampling factors {} (luma 1x1, 2x1 or 2x2 over 1x1 chroma)'.format(
+                    ' '.join('{}x{}'.format(*f) for f in sampling)))
+            frame = (h, w, comps)
+        elif marker in _SOF_NAMES:
+            raise ValueError('{} file (SOF{}): only baseline sequential files (SOF0) are read'.format(_SOF_NAMES[marker], marker - 0xc0))
+        elif marker == 0xcc:
+            raise ValueError('arithmetic-coded file (DAC segment)')
+        elif marker == 0xdd:
+            if len(body) != 2:
+                raise ValueError('malformed DRI segment')
+            if struct.unpack('>H', body)[0] != 0:
+                raise ValueError('restart interval {} (DRI): files with restart markers are not read'.format(struct.unpack('>H', body)[0]))
+        elif marker == 0xda:
+            break
+        elif not (0xe0 <= marker <= 0xef or marker == 0xfe or marker == 0xdc or 0xf0 <= marker <= 0xfd):
+            raise ValueError('unsupported marker FF{:02X} in the header'.format(marker))
+        pos += 2 + size
+    if frame is None:
+        raise ValueError('no frame header (SOF0) before the scan')
+    h, w, comps = frame
+    if len(body) < 1 or len(body) != 4 + 2 * body[0]:
+        raise ValueError('malformed SOS segment')
+    if body[0] != 3:
+        raise ValueError('non-interleaved file: the scan holds {} of 3 components'.format(body[0]))
+    if [body[1 + 2 * c] for c in range(3)] != [c[0] for c in comps]:
+        raise ValueError('the scan does not list the components in frame order')
+    ss, se, ahal = body[7], body[8], body[9]
+    if (ss, se, ahal) != (0, 63, 0):
+        raise ValueError('not a baseline scan: Ss={} Se={} Ah/Al={:02x} (0, 63, 00 needed)'.format(ss, se, ahal))
+    tables, qtables = [], np.zeros((3, 64), np.uint16)
+    for c in range(3):
+        sel = body[2 + 2 * c]
+        if (sel >> 4) > 3 or (sel & 15) > 3:
+            raise ValueError('malformed SOS segment')
+        for cls, ident in ((0, sel >> 4), (1, sel & 15)):
+            if (cls << 4 | ident) not in huff:
+                raise ValueError('missing Huffman table: {} table {} of component {}'.format('AC' if cls else 'DC', ident, c))
+            tables.append(huff[cls << 4 | ident])
+        if comps[c][3] not in qt:
+            raise ValueError('missing quantisation table {} of component {}'.format(comps[c][3], c))
+        qtables[c] = qt[comps[c][3]]
+    ecd_offset = pos + 2 + size
+    k = ecd_offset
+    while True:
+        k = data.find(b'\xff', k)
+        if k < 0 or k + 1 >= len(data):
+            raise ValueError('no EOI marker behind the entropy-coded segment')
+        nxt = data[k + 1]
+        if nxt == 0:
+            k += 2
+            continue
+        if nxt == 0xd9:
+            break
+        if 0xd0 <= nxt <= 0xd7:
+            raise ValueError('restart marker FF{:02X} in the entropy-coded segment: files with restart markers are not read'.format(nxt))
+        if nxt in (0xda, 0xc4, 0xdb, 0xdd):
+            raise ValueError('several scans: marker FF{:02X} behind the first entropy-coded segment'.format(nxt))
+        raise ValueError('unexpected marker FF{:02X} in the entropy-coded segment'.format(nxt))
+    return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, tuple(tables), ecd_offset, k)
+
+
+def _status_text(status):
+    return ' | '.join(text for bit, text in JPEG_STATUS_BITS.items() if status & bit)
+
+
+def _decode_groups(files, subseq_bits, device):
+    """Headers parsed, one upload, one nimg_jpeg_decode per group of equal (h, w, hs, vs).  Returns (headers, groups) with groups =
+    [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back."""
+    headers = [parse_header(f) for f in files]
+    if not headers:
+        raise ValueError('no files to decode')
+    keys = OrderedDict()
+    for i, hd in enumerate(headers):
+        keys.setdefault((hd.h, hd.w, hd.hs, hd.vs), []).append(i)
+    dev = device if device is not None else default_device()
+    order = [i for idx in keys.values() for i in idx]                    # the segments back to back, group after group
+    blob = b''.join(files[i][headers[i].ecd_offset:headers[i].ecd_end] for i in order)
+    huff = np.zeros((len(order), 6, 272), np.uint8)
+    for j, i in enumerate(order):
+        for t, (counts, symbols) in enumerate(headers[i].huffman):
+            huff[j, t, :16] = np.frombuffer(counts, np.uint8)
+            huff[j, t, 16:16 + len(symbols)] = np.frombuffer(symbols, np.uint8)
+    qt = np.stack([headers[i].qtables for i in order]).view(np.int16)
+    ecd = torch.from_numpy(np.frombuffer(blob if blob else b'\0', np.uint8).copy()).to(dev)
+    huff, qt = torch.from_numpy(huff).to(dev), torch.from_numpy(qt).to(dev)
+    groups, j0, b0 = [], 0, 0
+    for (h, w, hs, vs), idx in keys.items():
+        lengths = [headers[i].ecd_end - headers[i].ecd_offset for i in idx]
+        off = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
+        part = ecd[b0:b0 + max(sum(lengths), 1)]
+        coef, status, rounds = ops.jpeg_decode(part, off, huff[j0:j0 + len(idx)], h, w, hs, vs, subseq_bits=subseq_bits)
+        groups.append((idx, (h, w, hs, vs), coef, status, rounds, qt[j0:j0 + len(idx)]))
+        j0, b0 = j0 + len(idx), b0 + sum(lengths)
+    return headers, groups
+
+
+def _raise_on_status(groups, status):
+    """status: numpy per group, in group order."""
+    bad = sorted((i, int(s)) for (idx, _, _, _, _, _), st in zip(groups, status) for i, s in zip(idx, st) if s)
+    if bad:
+        raise ValueError('damaged JPEG data in file(s) {}: {}'.format(
+            [i for i, _ in bad], '; '.join('{}: status {} ({})'.format(i, s, _status_text(s)) for i, s in bad)))
+
+
+def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None):
+    """Decode baseline JPEG files on the GPU: a list of bytes (or one bytes) -> (n,h,w,3) uint8, the array imageio.imread returns for
+    each (libjpeg's islow inverse DCT and fancy up-sampling, bit for bit), or float32(byte) / 255 with as_float.  Files of different
+    geometry give a list of (h,w,3) arrays in input order.  Any 8-bit quantisation and Huffman tables are read from each file
+    (parse_header names what is refused).  The segments go up in one copy, every group of equal (h, w, sampling) takes one decode and
+    one reconstruct call, status and images come down once; device_output keeps the images on the device.  Damaged data raises
+    ValueError naming the indices and the status bits (JPEG_STATUS_BITS)."""
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    files = [bytes(files)] if single else [bytes(f) for f in files]
+    headers, groups = _decode_groups(files, subseq_bits, device)
+    images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
+              for _, (h, w, hs, vs), coef, _, _, qt in groups]
+    words = [len(g[0]) for g in groups]
+    parts = [g[3].view(torch.uint8) for g in groups]                    # one download: the status words, then the images
+    if not device_output:
+        parts += [y.view(torch.uint8).reshape(-1) for y in images]
+    flat = torch.cat(parts).cpu().numpy()
+    _raise_on_status(groups, np.split(flat[:4 * sum(words)].view(np.int32), np.cumsum(words)[:-1]))
+    if not device_output:
+        at, out = 4 * sum(words), []
+        for y in images:
+            size = y.numel() * y.element_size()
+            out.append(flat[at:at + size].view(np.float32 if as_float else np.uint8).reshape(tuple(y.shape)))
+            at += size
+        images = out
+    if len(groups) == 1:
+        return images[0]
+    result = [None] * len(files)
+    for (idx, _, _, _, _, _), y in zip(groups, images):
+        for j, i in enumerate(idx):
+            result[i] = y[j]
+    return result
+
+
+def decode_coefficients(files, device_output=False, subseq_bits=0, device=None):
+    """The quantised coefficients of baseline files of ONE geometry, as stored in the files: ((n, real blocks, 64) int16 in the layout
+    of DESIGN.md section 4c - [Y | Cb | Cr][block row][block col][zig-zag] - and the (n, 3, 64) uint16 quantisation tables per
+    component in natural order; jpeg_qf_estimation(tables[i, c].reshape(8, 8), c) names the quality they came from)."""
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    files = [bytes(files)] if single else [bytes(f) for f in files]
+    headers, groups = _decode_groups(files, subseq_bits, device)
+    if len(groups) != 1:
+        raise ValueError('decode_coefficients needs files of one geometry, got {}'.format([g[1] for g in groups]))
+    _, _, coef, status, _, _ = groups[0]
+    _raise_on_status(groups, [status.cpu().numpy()])
+    return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
 
 
 class JPEGMarkerStats(object):

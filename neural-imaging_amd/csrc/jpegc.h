@@ -90,6 +90,36 @@ constexpr QTabs make_qtabs(int quality) {
     return t;
 }
 
+// ---- scans over a workgroup of SCAN_THREADS ------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// exclusive scan over the NT threads of a workgroup; wtot: NT / 64 words of LDS; total = the sum of all
+template <typename T, int NT = SCAN_THREADS>
+__device__ __forceinline__ T block_excl_scan(T v, T* wtot, T& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const T incl = wave_incl_scan(v, lane);
+    __syncthreads();                                   // the previous round's readers are done with wtot
+    if (lane == 63) wtot[wv] = incl;
+    __syncthreads();
+    T run = incl - v, tot = 0;
+#pragma unroll
+    for (int k = 0; k < NT / 64; ++k) {
+        const T s = wtot[k];
+        if (k < wv) run += s;
+        tot += s;
+    }
+    total = tot;
+    return run;
+}
+
 // ---- transform --------------------------------------------------------------------------------------------------------
 // the reference's conversion: (255 * x).astype(uint8) in float32 after an optional x / 255; clamped where numpy would wrap
 __device__ __forceinline__ int byte_of(float v, bool div) {
@@ -197,6 +227,21 @@ __device__ __forceinline__ void locate(const Geo& g, long t, int& img, int& comp
 // ---- reconstruct --------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint8_t* plane_of(uint8_t* planes, const Geo& g, int img, int comp) {
     return planes + (size_t)img * g.NB * 64 + (comp ? (size_t)g.nbY * 64 + (size_t)(comp - 1) * g.nbC * 64 : 0);
+}
+
+// chroma sample at full-resolution (y, x): libjpeg's "fancy" triangle filter over the component's real extent; with at most two
+// chroma columns libjpeg replicates instead
+__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const Geo& g, int y, int x) {
+    const int stride = 8 * g.bwC;
+    if (g.hs == 1) return p[(size_t)y * stride + x];
+    const int i = x >> 1, j = g.vs == 2 ? y >> 1 : y;
+    if (g.cew <= 2) return p[(size_t)j * stride + i];
+    const int nb = (x & 1) ? min(i + 1, g.cew - 1) : max(i - 1, 0);
+    const uint8_t* near = p + (size_t)j * stride;
+    if (g.vs == 1) return (3 * near[i] + near[nb] + 1 + (x & 1)) >> 2;
+    const uint8_t* far = p + (size_t)((y & 1) ? min(j + 1, g.ceh - 1) : max(j - 1, 0)) * stride;
+    const int si = 3 * near[i] + far[i], sn = 3 * near[nb] + far[nb];
+    return (3 * si + sn + 8 - (x & 1)) >> 4;
 }
 
 inline bool grid_ok(long items, int per_block) { return (items + per_block - 1) / per_block <= 0x7fffffffL; }

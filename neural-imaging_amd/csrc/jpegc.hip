@@ -94,35 +94,6 @@ __global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restr
 }
 
 // ---- entropy coding -----------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-// exclusive scan over the SCAN_THREADS threads of a workgroup; wtot: 16 words of LDS; total = the sum of all
-template <typename T>
-__device__ __forceinline__ T block_excl_scan(T v, T* wtot, T& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const T incl = wave_incl_scan(v, lane);
-    __syncthreads();                                   // the previous round's readers are done with wtot
-    if (lane == 63) wtot[wv] = incl;
-    __syncthreads();
-    T run = incl - v, tot = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_THREADS / 64; ++k) {
-        const T s = wtot[k];
-        if (k < wv) run += s;
-        tot += s;
-    }
-    total = tot;
-    return run;
-}
-
 // bit sink: EMIT = false only counts.  Bits are MSB first; word j of the image's buffer holds bits 32 j .. 32 j + 31.  The first
 // and the last word a block touches may be shared with its neighbours: OR-ed into zeroed memory; the words in between are its own.
 template <bool EMIT>
@@ -381,21 +352,6 @@ __global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t* __restric
         }
         *reinterpret_cast<uint2*>(p + (size_t)r * stride) = make_uint2(lo, hi);
     }
-}
-
-// chroma sample at full-resolution (y, x): libjpeg's "fancy" triangle filter over the component's real extent; with at most two
-// chroma columns libjpeg replicates instead
-__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const Geo& g, int y, int x) {
-    const int stride = 8 * g.bwC;
-    if (g.hs == 1) return p[(size_t)y * stride + x];
-    const int i = x >> 1, j = g.vs == 2 ? y >> 1 : y;
-    if (g.cew <= 2) return p[(size_t)j * stride + i];
-    const int nb = (x & 1) ? min(i + 1, g.cew - 1) : max(i - 1, 0);
-    const uint8_t* near = p + (size_t)j * stride;
-    if (g.vs == 1) return (3 * near[i] + near[nb] + 1 + (x & 1)) >> 2;
-    const uint8_t* far = p + (size_t)((y & 1) ? min(j + 1, g.ceh - 1) : max(j - 1, 0)) * stride;
-    const int si = 3 * near[i] + far[i], sn = 3 * near[nb] + far[nb];
-    return (3 * si + sn + 8 - (x & 1)) >> 4;
 }
 
 // one thread per pixel

@@ -1,0 +1,382 @@
+// Decoder of baseline JPEG files: the entropy-coded segments of a batch -> the coefficient tensor of
+// jpegc.hip, by the self-synchronisation of Huffman codes (Weissenberger and Schmidt), and the coefficients -> images with the
+// tables of each file.
+//   prepare    one workgroup per image: the six Huffman tables from the DHT counts; the segment without its stuffing (FF 00 -> FF),
+//              MSB first in 32-bit words, by a block scan with a carry; the number of subsequences
+//   speculate  one thread per subsequence of subseq_bits bits: decode from the guess (m, z) = (0, 0), store exit state and blocks begun
+//   sync       one workgroup per image: rounds in which thread i decodes subsequence i again from the stored exit state of i - 1,
+//              until a round changes nothing (or all are known to be true); then the exclusive scan of the block counts
+//   write      one thread per subsequence: decode from the true state; AC values into coef, DC differences into a scan-order array
+//   dc         one workgroup per (image, component): prefix sum of the differences, dummy blocks included, into position 0
+// The rounds are driven inside ONE workgroup per image: the states of an image are exchanged between the threads of a workgroup
+// only, behind its barrier, so nothing waits on another workgroup and no flag crosses a kernel.  An image with more subsequences
+// than the workgroup has threads is walked in chunks from the last to the first, which keeps a round a pure function of the states
+// of the round before (thread i reads i - 1 before any thread of this round has written it): the number of rounds is the same
+// for every chunking, on the host as on the device.
+// The sequential core - tables, block placement, the decode of one subsequence - is jpegd.h, shared with a host program.
+#include "jpegc.h"
+#include "jpegd.h"
+
+namespace {
+
+constexpr int DEC_THREADS = 256;
+constexpr int SYNC_THREADS = 256;        // the workgroup that synchronises one image; longer images are walked in chunks of it
+constexpr uint32_t SUBSEQ_DEFAULT = 2048;        // the fastest setting measured
+constexpr uint32_t SUBSEQ_MAX = 1u << 30;
+constexpr uint64_t ECD_MAX = (1ull << 28) - 1;        // bytes of one segment: bit positions stay below 2^31
+
+struct DLayout {
+    uint32_t* total_bits;        // [n] bits of an image's un-stuffed stream
+    uint32_t* nsub;              // [n] its subsequences (0: the image is not decoded)
+    JpegdTable* tabs;            // [n][6]
+    int32_t* dcdiff;             // [n][SB] DC differences in scan order
+    uint32_t* raw;               // un-stuffed streams; image i from word (ecd_off[i] >> 2) + 2 i, (len + 3) / 4 + 1 words
+    JpegdState* exit;            // exit states; image i from slot 8 ecd_off[i] / subseq_bits + i
+    uint32_t* cnt;               // blocks begun, then (in place) the index of the first block begun; slots as `exit`
+    size_t raw_words, slots, bytes;
+};
+
+DLayout carve_d(const Geo& g, uint64_t ecd_bytes, uint32_t sb, void* base) {
+    DLayout d;
+    uint8_t* p = (uint8_t*)base;
+    d.total_bits = (uint32_t*)p; p += align256((size_t)g.n * 4);
+    d.nsub = (uint32_t*)p; p += align256((size_t)g.n * 4);
+    d.tabs = (JpegdTable*)p; p += align256((size_t)g.n * 6 * sizeof(JpegdTable));
+    d.dcdiff = (int32_t*)p; p += align256((size_t)g.n * g.SB * 4);
+    d.raw_words = (size_t)(ecd_bytes / 4) + 2 * (size_t)g.n + 2;
+    d.raw = (uint32_t*)p; p += align256(d.raw_words * 4);
+    d.slots = (size_t)(8 * ecd_bytes / sb) + (size_t)g.n + 1;
+    d.exit = (JpegdState*)p; p += align256(d.slots * sizeof(JpegdState));
+    d.cnt = (uint32_t*)p; p += align256(d.slots * 4);
+    d.bytes = (size_t)(p - (uint8_t*)base);
+    return d;
+}
+
+bool subseq_ok(int subseq_bits, uint32_t* sb) {
+    if (subseq_bits < 0 || (subseq_bits & 31) || (uint32_t)subseq_bits > SUBSEQ_MAX) return false;
+    *sb = subseq_bits ? (uint32_t)subseq_bits : SUBSEQ_DEFAULT;
+    return true;
+}
+
+JpegdGeo core_geo(const Geo& g) {
+    JpegdGeo c;
+    c.per = g.per; c.hs = g.hs; c.vs = g.vs; c.hsh = g.hsh; c.mx = g.mx; c.bhY = g.bhY; c.bwY = g.bwY; c.bwC = g.bwC;
+    c.nbY = g.nbY; c.nbC = g.nbC; c.SB = g.SB;
+    return c;
+}
+
+struct DArgs {
+    const uint8_t* ecd;
+    const uint64_t* off;
+    const uint8_t* huffman;
+    uint64_t ecd_cap;            // the segment bytes the workspace was sized for
+    uint32_t sb;
+    int n, NB;
+    JpegdGeo g;
+    int16_t* coef;
+    uint32_t* status;
+    uint32_t* rounds;
+};
+
+__device__ __forceinline__ size_t raw_start(uint64_t off, int img) { return (size_t)(off >> 2) + 2 * (size_t)img; }
+__device__ __forceinline__ size_t slot_start(uint64_t off, uint32_t sb, int img) { return (size_t)(8 * off / sb) + (size_t)img; }
+
+// ---- prepare ------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DLayout d) {
+    __shared__ uint32_t wtot[SCAN_THREADS / 64];
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const uint64_t o0 = a.off[img], o1 = a.off[img + 1];
+    if (o1 < o0 || o1 > a.ecd_cap || o1 - o0 > ECD_MAX) {               // uniform
+        if (tid == 0) {
+            atomicOr(a.status + img, JPEGD_ST_OFFSETS);
+            d.total_bits[img] = 0; d.nsub[img] = 0;
+        }
+        return;
+    }
+    if (tid < 6 && !jpegd_build_table(a.huffman + ((size_t)img * 6 + tid) * JPEGD_DHT_BYTES, d.tabs + (size_t)img * 6 + tid))
+        atomicOr(a.status + img, JPEGD_ST_TABLE);
+    const uint32_t len = (uint32_t)(o1 - o0), cap_bytes = ((len + 3u) / 4u + 1u) * 4u;
+    const uint8_t* src = a.ecd + o0;
+    uint8_t* out = (uint8_t*)(d.raw + raw_start(o0, img));
+    uint32_t carry = 0;
+    bool marker = false;
+    for (uint32_t base = 0; base < len; base += 4u * SCAN_THREADS) {
+        const uint32_t j = base + 4u * tid;
+        uint8_t b[6];                                  // the byte before, four of this thread's, the byte after
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const uint32_t k = j + (uint32_t)q - 1u;
+            b[q] = (j + (uint32_t)q >= 1u && k < len) ? src[k] : (uint8_t)1;        // outside the segment: neither FF nor 00
+        }
+        uint32_t keep = 0, kept = 0;
+#pragma unroll
+        for (int q = 1; q <= 4; ++q) {
+            if (j + (uint32_t)q - 1u >= len) break;
+            if (b[q] == 0xff && b[q + 1] != 0) marker = true;
+            if (!(b[q] == 0 && b[q - 1] == 0xff)) { keep |= 1u << q; ++kept; }
+        }
+        uint32_t sum;
+        uint32_t at = carry + block_excl_scan(kept, wtot, sum);
+        carry += sum;
+#pragma unroll
+        for (int q = 1; q <= 4; ++q)
+            if (keep >> q & 1u) {
+                if (at < cap_bytes) out[(at & ~3u) + 3u - (at & 3u)] = b[q];       // byte k of the stream: bits 31 - 8 (k & 3) .. of word k / 4
+                ++at;
+            }
+    }
+    if (marker) atomicOr(a.status + img, JPEGD_ST_MARKER);
+    if (tid == 0) {
+        const uint32_t total = 8u * carry;
+        d.total_bits[img] = total;
+        d.nsub[img] = total == 0 ? 1u : (total + a.sb - 1u) / a.sb;
+    }
+}
+
+// the six tables of an image into LDS
+__device__ __forceinline__ void load_tables(JpegdTable* dst, const JpegdTable* src, int threads) {
+    const uint32_t* s = (const uint32_t*)src;
+    uint32_t* t = (uint32_t*)dst;
+    for (int k = threadIdx.x; k < (int)(6 * sizeof(JpegdTable) / 4); k += threads) t[k] = s[k];
+    __syncthreads();
+}
+
+// ---- speculate / write: one thread per subsequence ------------------------------------------------------------------------
+template <bool WRITE>
+__global__ void __launch_bounds__(DEC_THREADS) jpegd_decode_kernel(DArgs a, DLayout d) {
+    __shared__ JpegdTable tabs[6];
+    const int img = blockIdx.y;
+    const uint32_t S = d.nsub[img];
+    if (blockIdx.x * DEC_THREADS >= S) return;           // uniform
+    load_tables(tabs, d.tabs + (size_t)img * 6, DEC_THREADS);
+    const uint64_t o0 = a.off[img];
+    const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
+    const uint32_t* bits = d.raw + raw_start(o0, img);
+    JpegdState* ex = d.exit + slot_start(o0, a.sb, img);
+    uint32_t* cnt = d.cnt + slot_start(o0, a.sb, img);
+    uint32_t status = 0;
+    for (uint32_t i = blockIdx.x * DEC_THREADS + threadIdx.x; i < S; i += gridDim.x * DEC_THREADS) {
+        JpegdState s;
+        if (WRITE && i) s = ex[i - 1];
+        else { s.p = i * a.sb; s.mz = 0; }
+        const uint32_t limit = min((i + 1u) * a.sb, total);
+        uint32_t begun;
+        jpegd_run<WRITE>(bits, nwords, total, limit, tabs, a.g, s, begun, WRITE ? cnt[i] : 0u,
+                         a.coef + (size_t)img * a.NB * 64, d.dcdiff + (size_t)img * a.g.SB, status);
+        if (!WRITE) { ex[i] = s; cnt[i] = begun; }
+    }
+    if (WRITE && status) atomicOr(a.status + img, status);
+}
+
+// ---- synchronise and place: one workgroup per image -------------------------------------------------------------------------
+__global__ void __launch_bounds__(SYNC_THREADS) jpegd_sync_kernel(DArgs a, DLayout d) {
+    __shared__ JpegdTable tabs[6];
+    __shared__ uint32_t wtot[SYNC_THREADS / 64];
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const uint32_t S = d.nsub[img];
+    if (S == 0) {
+        if (tid == 0 && a.rounds) a.rounds[img] = 0;
+        return;
+    }
+    load_tables(tabs, d.tabs + (size_t)img * 6, SYNC_THREADS);
+    const uint64_t o0 = a.off[img];
+    const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
+    const uint32_t* bits = d.raw + raw_start(o0, img);
+    JpegdState* ex = d.exit + slot_start(o0, a.sb, img);
+    uint32_t* cnt = d.cnt + slot_start(o0, a.sb, img);
+    const uint32_t chunks = (S + SYNC_THREADS - 1) / SYNC_THREADS;
+    uint32_t rounds = 0, unused = 0;
+    // after round r the subsequences 0 .. r are true: S - 1 rounds always suffice
+    while (rounds + 1 < S) {
+        ++rounds;
+        int changed = 0;
+        for (uint32_t c = chunks; c-- > 0;) {
+            const uint32_t i = c * SYNC_THREADS + tid;
+            const bool active = i >= rounds && i < S;
+            JpegdState s;
+            if (active) s = ex[i - 1];
+            __syncthreads();                           // every state of this chunk's predecessors is read before one is written
+            if (active) {
+                const JpegdState old = ex[i];
+                uint32_t begun;
+                jpegd_run<false>(bits, nwords, total, min((i + 1u) * a.sb, total), tabs, a.g, s, begun, 0u, nullptr, nullptr, unused);
+                if (s.p != old.p || s.mz != old.mz) changed = 1;
+                ex[i] = s; cnt[i] = begun;
+            }
+        }
+        if (!__syncthreads_or(changed)) break;
+    }
+    __syncthreads();
+    uint32_t carry = 0;
+    for (uint32_t c = 0; c < chunks; ++c) {
+        const uint32_t i = c * SYNC_THREADS + tid;
+        const uint32_t v = i < S ? cnt[i] : 0u;
+        uint32_t sum;
+        const uint32_t exq = block_excl_scan<uint32_t, SYNC_THREADS>(v, wtot, sum);
+        if (i < S) cnt[i] = carry + exq;
+        carry += sum;
+    }
+    if (tid == 0) {
+        if (carry < (uint32_t)a.g.SB) atomicOr(a.status + img, JPEGD_ST_BLOCKS);
+        if (a.rounds) a.rounds[img] = rounds;
+    }
+}
+
+// ---- DC: one workgroup per (component, image) --------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout d) {
+    __shared__ int wtot[SCAN_THREADS / 64];
+    const int comp = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
+    if (d.nsub[img] == 0) return;
+    const int ny = a.g.per - 2, mcus = a.g.SB / a.g.per, count = comp ? mcus : mcus * ny;
+    const int32_t* diff = d.dcdiff + (size_t)img * a.g.SB;
+    int16_t* coef = a.coef + (size_t)img * a.NB * 64;
+    int carry = 0;
+    bool bad = false;
+    for (int base = 0; base < count; base += SCAN_THREADS) {
+        const int j = base + tid;
+        const uint32_t b = comp ? (uint32_t)(j * a.g.per + ny + comp - 1) : (uint32_t)((j / ny) * a.g.per + j % ny);
+        const int v = j < count ? diff[b] : 0;
+        int sum;
+        const int dc = carry + block_excl_scan(v, wtot, sum) + v;
+        carry += sum;
+        if (j < count) {
+            int c2;
+            const long at = jpegd_place(a.g, b, c2);
+            if (dc < -32768 || dc > 32767) bad = true;
+            if (at >= 0) coef[at * 64] = (int16_t)dc;
+        }
+    }
+    if (bad) atomicOr(a.status + img, JPEGD_ST_DC);
+}
+
+// ---- reconstruct with the tables of each image ----------------------------------------------------------------------------------
+// one thread per real block (jpeg_idct_kernel with the table of (image, component) read from memory)
+__global__ void __launch_bounds__(256) jpegd_idct_tables_kernel(const int16_t* __restrict__ coef, uint8_t* __restrict__ planes, Geo g,
+                                                                const uint16_t* __restrict__ qtabs) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.NB) return;
+    int img, comp, br, bc;
+    locate(g, t, img, comp, br, bc);
+    const uint16_t* q = qtabs + ((size_t)img * 3 + comp) * 64;
+    const uint4* src = reinterpret_cast<const uint4*>(coef + t * 64);
+    uint32_t wds[32];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint4 v = src[j];
+        wds[4 * j] = v.x; wds[4 * j + 1] = v.y; wds[4 * j + 2] = v.z; wds[4 * j + 3] = v.w;
+    }
+    int d[64];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const int nat = c_nat_of_zz[k];
+        d[nat] = (int)(short)(wds[k >> 1] >> (16 * (k & 1))) * (int)q[nat];
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) idct8<8>(d + c, 11);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) idct8<1>(d + 8 * r, 18);
+    const int stride = 8 * (comp ? g.bwC : g.bwY);
+    uint8_t* p = plane_of(planes, g, img, comp) + (size_t)(8 * br) * stride + 8 * bc;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            lo |= (uint32_t)min(max(d[8 * r + c] + 128, 0), 255) << (8 * c);
+            hi |= (uint32_t)min(max(d[8 * r + 4 + c] + 128, 0), 255) << (8 * c);
+        }
+        *reinterpret_cast<uint2*>(p + (size_t)r * stride) = make_uint2(lo, hi);
+    }
+}
+
+// one thread per pixel (jpeg_colour_kernel, which can also leave the bytes as they are)
+template <bool U8>
+__global__ void __launch_bounds__(256) jpegd_colour_kernel(uint8_t* __restrict__ planes, void* __restrict__ out, Geo g) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.h * g.w) return;
+    const int img = (int)(t / ((long)g.h * g.w)), r = (int)(t - (long)img * g.h * g.w), y = r / g.w, x = r - y * g.w;
+    const int yy = plane_of(planes, g, img, 0)[(size_t)y * 8 * g.bwY + x];
+    const int cb = chroma_at(plane_of(planes, g, img, 1), g, y, x) - 128;
+    const int cr = chroma_at(plane_of(planes, g, img, 2), g, y, x) - 128;
+    const int R = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
+    const int G = min(max(yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16), 0), 255);
+    const int B = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
+    if (U8) {
+        uint8_t* o = (uint8_t*)out + t * 3;
+        o[0] = (uint8_t)R; o[1] = (uint8_t)G; o[2] = (uint8_t)B;
+    } else {
+        float* o = (float*)out + t * 3;
+        o[0] = __fdiv_rn((float)R, 255.0f);
+        o[1] = __fdiv_rn((float)G, 255.0f);
+        o[2] = __fdiv_rn((float)B, 255.0f);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, size_t ecd_bytes, int subseq_bits) {
+    Geo g;
+    uint32_t sb;
+    if (!make_geo(&g, n, h, w, hs, vs) || !subseq_ok(subseq_bits, &sb) || ecd_bytes > (size_t)n * ECD_MAX) return 0;
+    return carve_d(g, ecd_bytes, sb, nullptr).bytes;
+}
+
+int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                     int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    Geo g;
+    uint32_t sb;
+    if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs) || !subseq_ok(subseq_bits, &sb))
+        return NIMG_ERR_ARG;
+    // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
+    if (carve_d(g, 0, sb, workspace).bytes > workspace_bytes) return NIMG_ERR_WORKSPACE;
+    uint64_t lo = 0, hi = (uint64_t)n * ECD_MAX;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (carve_d(g, mid, sb, workspace).bytes <= workspace_bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    const DLayout d = carve_d(g, lo, sb, workspace);
+    DArgs a;
+    a.ecd = ecd; a.off = ecd_off; a.huffman = huffman; a.ecd_cap = lo; a.sb = sb; a.n = n; a.NB = g.NB; a.g = core_geo(g);
+    a.coef = coef; a.status = status; a.rounds = rounds;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(status, 0, (size_t)n * 4, st) != hipSuccess || hipMemsetAsync(coef, 0, (size_t)n * g.NB * 128, st) != hipSuccess ||
+        hipMemsetAsync(d.dcdiff, 0, (size_t)n * g.SB * 4, st) != hipSuccess || hipMemsetAsync(d.raw, 0, d.raw_words * 4, st) != hipSuccess)
+        return NIMG_ERR_LAUNCH;
+    hipLaunchKernelGGL(jpegd_prepare_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    NIMG_CHECK_LAUNCH();
+    // no valid stream is longer than SB blocks of JPEGD_BLOCK_BITS_MAX bits; a longer (damaged) one is covered by the threads' stride
+    const uint64_t bits_max = min((uint64_t)g.SB * JPEGD_BLOCK_BITS_MAX, 8 * min(lo, ECD_MAX));
+    const unsigned gx = (unsigned)min((uint64_t)4096, max((uint64_t)1, (bits_max / sb + DEC_THREADS) / DEC_THREADS));
+    hipLaunchKernelGGL(jpegd_decode_kernel<false>, dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpegd_sync_kernel, dim3((unsigned)n), dim3(SYNC_THREADS), 0, st, a, d);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpegd_decode_kernel<true>, dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpegd_dc_kernel, dim3(3, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    Geo g;
+    if (!coef || !y || !qtabs || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    const Workspace ws = carve(g, workspace);
+    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
+    const long blocks = (long)n * g.NB, pixels = (long)n * h * w;
+    if (!grid_ok(blocks, 256) || !grid_ok(pixels, 256)) return NIMG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(jpegd_idct_tables_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g, qtabs);
+    NIMG_CHECK_LAUNCH();
+    if (out_u8) hipLaunchKernelGGL(jpegd_colour_kernel<true>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, ws.planes, y, g);
+    else hipLaunchKernelGGL(jpegd_colour_kernel<false>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, ws.planes, y, g);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+}  // extern "C"

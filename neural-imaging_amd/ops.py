@@ -2374,3 +2374,58 @@ def jpeg_reconstruct_items(coef, h, w, quality, hs=1, vs=1, workspace=None, out=
     err = torch.zeros((1,), dtype=torch.int32, device=coef.device) if err is None else err
     _lib.call('nimg_jpeg_reconstruct_items', _p(coef), n, h, w, hs, vs, _p(q), _p(y), _p(err), _p(ws), need, _stream())
     return y, err
+
+
+JPEG_SUBSEQ_BITS_MAX = 1 << 30
+
+
+def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspace=None):
+    """The entropy-coded segments of n baseline files of one geometry -> (coefficients (n, real blocks, 64) int16 as jpeg_transform
+    leaves them, status (n,) int32 - 0 = decoded, the bits are include/nimg.h's - and rounds (n,) int32, the synchronisation rounds
+    each image took).  ecd: uint8 device tensor, the segments back to back as they stand in the files; ecd_off: (n + 1,) int64
+    offsets into it; huffman: (n, 6, 272) uint8, per image the tables Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC as 16 counts + 256
+    symbols.  subseq_bits: bits one thread decodes (a multiple of 32, 0 = the default; at least the stream = a sequential decode)."""
+    _chk(ecd)
+    _chk(ecd_off)
+    _chk(huffman)
+    n = ecd_off.numel() - 1
+    if ecd.dtype != torch.uint8 or ecd_off.dtype != torch.int64 or n < 1:
+        raise RuntimeError('jpeg_decode: uint8 segments and (n + 1,) int64 offsets needed, got {} and {} {}'.format(
+            ecd.dtype, ecd_off.dtype, tuple(ecd_off.shape)))
+    if huffman.dtype != torch.uint8 or tuple(huffman.shape) != (n, 6, 272):
+        raise RuntimeError('jpeg_decode: Huffman tables {} {}, ({}, 6, 272) uint8 needed'.format(huffman.dtype, tuple(huffman.shape), n))
+    subseq_bits = int(subseq_bits)
+    need = int(_lib.load().nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
+    if need == 0:
+        raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{} subseq_bits={}'.format(n, h, w, hs, vs, subseq_bits))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=ecd.device)
+    _chk(workspace)
+    if workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError('JPEG decode workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
+    coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
+    status = torch.empty(n, dtype=torch.int32, device=ecd.device)
+    rounds = torch.empty(n, dtype=torch.int32, device=ecd.device)
+    _lib.call('nimg_jpeg_decode', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, subseq_bits, _p(coef), _p(status), _p(rounds),
+              _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    return coef, status, rounds
+
+
+def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspace=None, out=None):
+    """jpeg_reconstruct with the quantisation tables given per image and component: qtabs (n, 3, 64) uint16 (or int16 bit patterns)
+    in natural order.  Returns (n,h,w,3) uint8 - the bytes libjpeg decodes - when out_u8, else float32 = byte / 255."""
+    _chk(coef)
+    _chk(qtabs)
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('jpeg_reconstruct_tables: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, 3, 64):
+        raise RuntimeError('jpeg_reconstruct_tables: tables {} {}, ({}, 3, 64) 16-bit integers needed'.format(qtabs.dtype, tuple(qtabs.shape), n))
+    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    dtype = torch.uint8 if out_u8 else torch.float32
+    y = torch.empty((n, h, w, 3), dtype=dtype, device=coef.device) if out is None else out
+    _chk(y)
+    if y.dtype != dtype or tuple(y.shape) != (n, h, w, 3):
+        raise RuntimeError('jpeg_reconstruct_tables: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, (n, h, w, 3)))
+    _lib.call('nimg_jpeg_reconstruct_tables', _p(coef), n, h, w, hs, vs, _p(qtabs), _p(y), int(bool(out_u8)), _p(ws), need, _stream())
+    return y

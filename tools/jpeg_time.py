@@ -8,8 +8,12 @@ events, after a warm-up:
   compress_batch_total   jpeg_helpers.compress_batch on the host batch: upload, the three stages, both downloads
 at 4:4:4 and at 4:2:0, on natural images.  Prints one JSON line per sub-sampling.  --pillow adds the host's time for the same
 images through Pillow (libjpeg), one after the other, where Pillow is installed; it needs no GPU.
+--decode times the way back on the files encode_batch writes for the same images: nimg_jpeg_decode as a whole
+and per kernel (prepare, speculate, sync, write, dc - from the profiler's kernel records), the synchronisation rounds,
+nimg_jpeg_reconstruct_tables and decode_batch from bytes to bytes, at subseq_bits 256, 512, 1024, 2048 and at one subsequence per
+image - the sequential decode the parallel one is measured against.  One JSON line per sub-sampling and setting.
 
-    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow]
+    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode]
 For the split of the calls into their kernels: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_time.py ...
 """
 import argparse
@@ -70,6 +74,71 @@ def measure(x_host, quality, subsampling, reps, dev):
             'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
 
 
+# stage -> what its kernel's name holds in the profiler's records, demangled or mangled
+DECODE_STAGES = (('prepare', ('jpegd_prepare_kernel',)), ('speculate', ('jpegd_decode_kernel<false>', 'jpegd_decode_kernelILb0E')),
+                 ('sync', ('jpegd_sync_kernel',)), ('write', ('jpegd_decode_kernel<true>', 'jpegd_decode_kernelILb1E')),
+                 ('dc', ('jpegd_dc_kernel',)))
+
+
+def kernel_ms(fn, reps):
+    """mean milliseconds per call of every decoder kernel, from the profiler's device records; None where it records none"""
+    from torch.profiler import ProfilerActivity, profile
+    try:
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+        events = [(e.name, e.device_time_total if hasattr(e, 'device_time_total') else e.cuda_time_total) for e in prof.events()]
+    except Exception:
+        return None
+    out = {}
+    for stage, keys in DECODE_STAGES:
+        times = [t for name, t in events if any(k in name for k in keys)]
+        if not times:                                                # a stage without a record: no partial table
+            return None
+        out[stage] = round(sum(times) / reps / 1e3, 4)
+    return out
+
+
+def measure_decode(x_host, quality, subsampling, reps, dev):
+    """one dict per subseq_bits setting"""
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    n, h, w, _ = x_host.shape
+    files = jpeg_helpers.encode_batch(x_host, quality, subsampling)
+    heads = [jpeg_helpers.parse_header(f) for f in files]
+    segments = [f[hd.ecd_offset:hd.ecd_end] for f, hd in zip(files, heads)]
+    ecd = torch.from_numpy(np.frombuffer(b''.join(segments), np.uint8).copy()).to(dev)
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(s) for s in segments])]).astype(np.int64)).to(dev)
+    huff = np.zeros((n, 6, 272), np.uint8)
+    for t, (counts, symbols) in enumerate(heads[0].huffman):
+        huff[:, t, :16], huff[:, t, 16:16 + len(symbols)] = np.frombuffer(counts, np.uint8), np.frombuffer(symbols, np.uint8)
+    huff = torch.from_numpy(huff).to(dev)
+    qt = torch.from_numpy(np.stack([hd.qtables for hd in heads]).view(np.int16)).to(dev)
+    want = ops.jpeg_transform(torch.from_numpy(x_host).to(dev), quality, hs, vs)
+    whole = -(-8 * max(len(s) for s in segments) // 32) * 32
+    rows = []
+    for subseq_bits in (256, 512, 1024, 2048, whole):
+        size = int(ops._lib.load().nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
+        ws = torch.empty(size, dtype=torch.uint8, device=dev)
+
+        def decode():
+            return ops.jpeg_decode(ecd, off, huff, h, w, hs, vs, subseq_bits=subseq_bits, workspace=ws)
+        ms = {}
+        ms['decode'], (coef, status, rounds) = timed(decode, reps)
+        assert int(status.abs().sum()) == 0 and torch.equal(coef, want)
+        ms['reconstruct_tables'], y = timed(lambda: ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=True), reps)
+        ms['decode_batch_total'], yb = timed(lambda: jpeg_helpers.decode_batch(files, subseq_bits=subseq_bits), max(3, reps // 4))
+        assert np.array_equal(yb, y.cpu().numpy())
+        r = rounds.cpu().numpy()
+        rows.append({'mode': 'decode', 'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality,
+                     'subseq_bits': subseq_bits, 'sequential': subseq_bits == whole, 'segment_bytes': int(ecd.numel()),
+                     'subsequences_per_image': round(8.0 * ecd.numel() / n / subseq_bits, 1), 'workspace_bytes': size,
+                     'rounds': {'min': int(r.min()), 'median': float(np.median(r)), 'max': int(r.max())},
+                     'ms': {k: round(v, 4) for k, v in ms.items()}, 'kernel_ms': kernel_ms(decode, reps),
+                     'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}})
+    return rows
+
+
 def pillow(x_host, quality, subsampling, reps):
     from PIL import Image
     u8 = np.clip(np.trunc(np.float32(255) * x_host), 0, 255).astype(np.uint8)
@@ -92,6 +161,7 @@ def main():
     ap.add_argument('--quality', type=int, default=75)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--pillow', action='store_true', help='time Pillow on the host instead (no GPU needed)')
+    ap.add_argument('--decode', action='store_true', help='time the decoder instead, per subseq_bits setting')
     args = ap.parse_args()
     x = natural_images(args.batch, args.size, args.size, seed=1)
     if args.pillow:
@@ -101,6 +171,12 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit('jpeg_time.py needs a GPU (or --pillow)')
     dev = torch.device('cuda', 0)
+    if args.decode:
+        for subsampling in SUBSAMPLINGS:
+            measure_decode(x[:4], args.quality, subsampling, 2, dev)                  # warm-up
+            for row in measure_decode(x, args.quality, subsampling, args.reps, dev):
+                print(json.dumps(dict(row, csrc_sha16=csrc_sha16())), flush=True)
+        return
     for subsampling in SUBSAMPLINGS:
         measure(x, args.quality, subsampling, 3, dev)                    # warm-up: code objects, allocator
         print(json.dumps(dict(measure(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())))
