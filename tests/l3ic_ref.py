@@ -180,6 +180,92 @@ def decode_layer(payload, n_sym, k=256):
     return rans_decode(payload, n_sym, k)
 
 
+# the decoder's error word (include/nimg.h NIMG_L3IC_E_*)
+E_READ, E_LANES, E_RANGE, E_SYMBOL, E_FREQ, E_VARINT, E_ODD, E_UNUSED, E_STATE, E_RLE = (1 << i for i in range(10))
+E_NAMES = {E_READ: 'READ', E_LANES: 'LANES', E_RANGE: 'RANGE', E_SYMBOL: 'SYMBOL', E_FREQ: 'FREQ', E_VARINT: 'VARINT',
+           E_ODD: 'ODD', E_UNUSED: 'UNUSED', E_STATE: 'STATE', E_RLE: 'RLE'}
+
+
+def decode_status(payload, n_sym, k=256):
+    """The error word nimg_l3ic_decode reports for one stream (0 = valid), restated from include/nimg.h and the order of
+    checks in l3ic_decode_kernel.  The payload kind goes by length: == n_sym RAW, == 3 RLE, > n_sym refused (READ), else
+    rANS.  rANS: a read past the payload gives 0 and READ; the header's LANES, RANGE (a > b) and SYMBOL accumulate and any of
+    them stops before the table; the table's VARINT, FREQ (the running sum passing 4096 ends the table there, as does a final
+    sum other than 4096), RANGE (a zero frequency at a or b as the table was left) and READ stop before the body; the body
+    runs to its end whatever happens and accumulates READ, ODD, UNUSED and STATE."""
+    p = bytes(payload)
+    n, err = len(p), [0]
+
+    def rd(o):
+        if o < n:
+            return p[o]
+        err[0] |= E_READ
+        return 0
+
+    if n == n_sym:
+        return E_SYMBOL if any(v >= k for v in p) else 0
+    if n == 3:
+        count, s = p[0] | (p[1] << 8), p[2]
+        return (E_RLE if count != n_sym else 0) | (E_SYMBOL if s >= k else 0)
+    if n > n_sym:
+        return E_READ
+    lanes, a, b = rd(0), rd(1), rd(2)
+    if not 1 <= lanes <= 64:
+        err[0] |= E_LANES
+    if a > b:
+        err[0] |= E_RANGE
+    if b >= k:
+        err[0] |= E_SYMBOL
+    if err[0]:
+        return err[0]
+    f, pos, total = [0] * 256, 3, 0
+    for s in range(a, b + 1):
+        v = rd(pos)
+        pos += 1
+        if v & 0x80:
+            v2 = rd(pos)
+            pos += 1
+            if v2 & 0x80:
+                err[0] |= E_VARINT
+            v = (v & 0x7f) | ((v2 & 0x7f) << 7)
+        if total + v > M:
+            err[0] |= E_FREQ
+            break
+        f[s] = v
+        total += v
+    if total != M:
+        err[0] |= E_FREQ
+    if not f[a] or not f[b]:
+        err[0] |= E_RANGE
+    if err[0]:
+        return err[0]
+    cum = _cum(f)
+    slot_sym = np.repeat(np.arange(256), f)
+    x = [LOW] * 64
+    for lane in range(lanes):
+        o = pos + 4 * lane
+        x[lane] = rd(o) | (rd(o + 1) << 8) | (rd(o + 2) << 16) | (rd(o + 3) << 24)
+    ws = pos + 4 * lanes
+    if ws <= n and (n - ws) & 1:
+        err[0] |= E_ODD
+    nwords = (n - ws) >> 1 if ws <= n else 0
+    wp = 0
+    for i in range(n_sym):
+        lane = i % lanes
+        slot = x[lane] & (M - 1)
+        s = int(slot_sym[slot])
+        x[lane] = f[s] * (x[lane] >> M_BITS) + slot - cum[s]
+        if x[lane] < LOW:
+            o = ws + 2 * wp
+            x[lane] = ((x[lane] << 16) | rd(o) | (rd(o + 1) << 8)) & 0xffffffff
+            wp += 1
+    if wp < nwords:
+        err[0] |= E_UNUSED
+    if any(v != LOW for v in x[:lanes]):
+        err[0] |= E_STATE
+    return err[0]
+
+
 def pack_container(h, w, payloads):
     out = bytearray([h, w, len(payloads)])
     out += struct.pack('<H', 2 * len(payloads))
