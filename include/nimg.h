@@ -56,7 +56,7 @@ extern "C" {
  * gained out_bf16_copy and stride; 5: the arg-max of nimg_conv1_pool_fwd_c4 / nimg_conv1_wgrad_c4 / nimg_conv1_dgrad_pooled is 2 bits
  * per value; 6: the nimg_l3ic_* bitstream entry points; 7: the nimg_jpeg_* baseline codec entry points; 8: the per-item
  * nimg_jpeg_*_items forms and nimg_msssim; version 8 also carries the later, purely added nimg_jpeg_decode* and
- * nimg_jpeg_reconstruct_tables entry points).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
+ * nimg_jpeg_reconstruct_tables entry points and the nimg_jpeg_histogram / _optimal_tables / _encode_tables ones).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
  * written against. */
 #define NIMG_ABI_VERSION 8
 int nimg_abi_version(void);
@@ -751,6 +751,33 @@ int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t*
                      void* stream);
 int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* Writing files with optimised Huffman tables - what imageio.imsave writes with libjpeg's optimize_coding in
+ * compression/jpeg_helpers.py:97.  A table is 16 + 256 bytes: the 16 counts of a DHT body, then the symbols in code order, unused
+ * symbol bytes 0 - the layout nimg_jpeg_decode takes; the four tables of an image stand in DHT-id order 00 (Y DC), 10 (Y AC),
+ * 01 (chroma DC), 11 (chroma AC), Cb and Cr sharing the last two.  Geometry and coefficients as above.
+ *   histogram       coef -> hist (device) [n][4][257] uint32, zeroed by the call: how often nimg_jpeg_encode would emit each symbol
+ *                   of each table (its clamps included; a dummy block counts its DC category and one end-of-block).  Entry 256 is 0.
+ *                   (jpeg_helpers.py:97, imageio.imsave: libjpeg's statistics pass.)
+ *   optimal_tables  hist (device) [n_tables][257] -> tables (device) [n_tables][272] by libjpeg's jpeg_gen_optimal_table: entry 256
+ *                   is not read (the pseudo-symbol counts 1), ties go to the larger index, sizes are limited to 16 as Annex K.3.
+ *                   status (device) [n_tables], written: 0, or 1 = a code size above 32, 2 = a histogram total of 2^32 or more (the
+ *                   pseudo-symbol counted); such a table is all zeros, as is the table of an all-zero histogram (status 0).
+ *                   n_tables <= 4 * 65535.  (jpeg_helpers.py:97, imageio.imsave: jpeg_gen_optimal_table.)
+ *   encode_tables   nimg_jpeg_encode with the tables of each image read from `tables` (device) [n][4][272]: out, out_capacity and
+ *                   lengths as there.  status (device) [n], written: 0, or bits 1 = counts that are no prefix code of lengths
+ *                   1..16 with at most 256 symbols (nothing is emitted for the image, its length is 0) | 2 = a symbol that occurs
+ *                   in the image has no code (it and its value bits are left out).  A DC table's symbols above 15 are ignored; of a
+ *                   symbol listed twice the last code counts.  Every store stays inside the image's slot whatever the tables say.
+ *                   A segment never exceeds 2 * ceil(blocks-in-scan * 1665 / 8) bytes (a DC code may take 16 bits here).  The
+ *                   workspace is nimg_jpeg_encode_tables_workspace_bytes - larger than nimg_jpeg_workspace_bytes by the code
+ *                   words.  (jpeg_helpers.py:97, imageio.imsave: the output pass.) */
+int nimg_jpeg_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, uint32_t* hist, void* stream);
+int nimg_jpeg_optimal_tables(const uint32_t* hist, int n_tables, uint8_t* tables, uint32_t* status, void* stream);
+size_t nimg_jpeg_encode_tables_workspace_bytes(int n, int h, int w, int hs, int vs);
+int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint8_t* tables, uint8_t* out,
+                            size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -193,6 +193,10 @@ PROTOTYPES = {
     'nimg_jpeg_decode_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_size_t, c_int]),
     'nimg_jpeg_decode': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     'nimg_jpeg_reconstruct_tables': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P]),
+    'nimg_jpeg_histogram': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'nimg_jpeg_optimal_tables': (c_int, [P, c_int, P, P, P]),
+    'nimg_jpeg_encode_tables_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'nimg_jpeg_encode_tables': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, P, c_size_t, P]),
     'nimg_msssim_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'nimg_msssim': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]),
 }

@@ -6,6 +6,8 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
   compress_batch (:82-114), match_quality (:26-79)      the standard codec - the reference's imageio / libjpeg round trip - on the
                                                         GPU kernels nimg_jpeg_* (format: DESIGN.md section 4c, libjpeg's byte for byte)
   encode_batch                                          new: the files themselves
+  optimize=True (compress_batch, encode_batch,          new: files with optimised Huffman tables, libjpeg's optimize_coding byte for
+  rate_distortion, match_quality[_batch])               byte - histograms, tables and coding per image on the GPU
   parse_header, decode_batch, decode_coefficients       new: the way back - any baseline file (its own quantisation and Huffman tables,
                                                         optimised ones included) decoded on the GPU to the bytes imageio.imread returns;
                                                         headers are parsed on the host, the entropy decoder is the parallel Huffman
@@ -82,15 +84,23 @@ def libjpeg_qtable(quality, channel=0):
     return np.clip(t, 1, 255).reshape(8, 8)
 
 
-def jpeg_header(h, w, quality, subsampling='4:4:4'):
-    """The 623 bytes from SOI to the end of SOS, as libjpeg writes them with default settings."""
+def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None):
+    """The bytes from SOI to the end of SOS as libjpeg writes them: 623 with default settings.  huffman: one image's four tables in
+    DHT-id order 00 10 01 11 as (4, 272) bytes (16 counts, then the symbols in code order) - what libjpeg writes with optimize_coding:
+    four DHT segments of 21 bytes + the table's symbols each.  The first DHT segment stays at offset 177."""
     hs, vs = ops.jpeg_subsampling(subsampling)
     order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
     out = bytes.fromhex('ffd8' 'ffe00010' '4a46494600' '0101' '00' '0001' '0001' '0000')
     for t in (0, 1):
         out += bytes.fromhex('ffdb0043') + bytes([t]) + libjpeg_qtable(quality, t).ravel()[order].astype(np.uint8).tobytes()
     out += bytes.fromhex('ffc00011' '08') + struct.pack('>HH', h, w) + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, 1])
-    for t in _DHT:
+    tables = _DHT
+    if huffman is not None:
+        huffman = np.asarray(huffman)
+        if huffman.dtype != np.uint8 or huffman.shape != (4, 272):
+            raise ValueError('huffman: (4, 272) uint8 needed, got {} {}'.format(huffman.dtype, huffman.shape))
+        tables = [bytes([ident]) + t[:16 + int(t[:16].sum(dtype=np.int64))].tobytes() for ident, t in zip((0x00, 0x10, 0x01, 0x11), huffman)]
+    for t in tables:
         out += b'\xff\xc4' + struct.pack('>H', len(t) + 2) + t
     return out + bytes.fromhex('ffda000c' '03' '0100' '0211' '0311' '00' '3f' '00')
 
@@ -107,9 +117,47 @@ def _device_batch(batch_x, keep_bytes, device=None):
     return x.to(device=dev, dtype=dtype).contiguous()
 
 
-def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True):
+JPEG_OPT_STATUS_BITS = OrderedDict([(1, 'Huffman table that is no prefix code'), (2, 'symbol without a code'),
+                                    (4, 'Huffman code size above 32'), (8, 'symbol histogram total of 2^32 or more')])
+
+
+def _optimised(coef, h, w, hs, vs, capacity):
+    """histogram -> optimal tables -> encode_tables on the device: (segments, lengths (n,) int32, tables (n,4,272) uint8, status (n,)
+    int32: the bits of JPEG_OPT_STATUS_BITS).  Nothing is read back."""
+    tables, tstatus = ops.jpeg_optimal_tables(ops.jpeg_histogram(coef, h, w, hs, vs))
+    data, lengths, status = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=capacity)
+    tstatus = tstatus[:, 0] | tstatus[:, 1] | tstatus[:, 2] | tstatus[:, 3]
+    return data, lengths, tables, status | (tstatus << 2)
+
+
+def _raise_on_opt_status(status):
+    bad = [(i, int(s)) for i, s in enumerate(np.asarray(status).tolist()) if s]
+    if bad:
+        raise ValueError('optimised Huffman coding failed for image(s) {}: {}'.format(
+            [i for i, _ in bad], '; '.join('{}: status {} ({})'.format(
+                i, s, ' | '.join(text for bit, text in JPEG_OPT_STATUS_BITS.items() if s & bit)) for i, s in bad)))
+
+
+def _device_codec_optimised(coef, n, h, w, hs, vs):
+    """([segment bytes], tables (n,4,272) uint8 numpy) - lengths, status and tables in one download, then the segments."""
+    capacity = n * min(ops.jpeg_ecd_bound_tables(h, w, hs, vs), 192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024)
+    data, lengths, tables, status = _optimised(coef, h, w, hs, vs, capacity)
+    flat = torch.cat([lengths.view(torch.uint8), status.view(torch.uint8), tables.reshape(-1)]).cpu().numpy()
+    lengths, status = flat[:4 * n].view(np.int32).astype(np.int64), flat[4 * n:8 * n].view(np.int32)
+    _raise_on_opt_status(status)
+    if int(lengths.sum()) > capacity:
+        data = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=int(lengths.sum()))[0]
+    tables = flat[8 * n:].reshape(n, 4, 272)
+    blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
+    ends = np.concatenate([[0], np.cumsum(lengths)])
+    return [blob[ends[i]:ends[i + 1]] for i in range(n)], tables
+
+
+def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True, optimize=False):
     """One batch through the GPU codec: x (n,h,w,3) device tensor, float32 or uint8 -> (decoded (n,h,w,3) float32 device tensor or
-    None, list of the entropy-coded segments as bytes or None).  One host synchronisation (for the lengths) when want_bytes."""
+    None, list of the entropy-coded segments as bytes or None).  One host synchronisation (for the lengths) when want_bytes.
+    With `optimize` the segments are coded with per-image optimal Huffman tables (histogram -> optimal tables -> encode_tables, the
+    tables and the lengths coming back together) and a third value is returned: the tables, (n, 4, 272) uint8, or None."""
     hs, vs = ops.jpeg_subsampling(subsampling)
     quality = int(quality)
     if not 1 <= quality <= 100:
@@ -117,8 +165,10 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
     n, h, w, _ = x.shape
     ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
     coef = ops.jpeg_transform(x, quality, hs, vs, workspace=ws)
-    segments = None
-    if want_bytes:
+    segments = tables = None
+    if want_bytes and optimize:
+        segments, tables = _device_codec_optimised(coef, n, h, w, hs, vs)
+    elif want_bytes:
         # room for 3 bytes per sample (random noise at quality 100 needs about 2); the bound is 6.5, and a batch that needs more
         # than it was given reports so through its lengths and is coded again with exactly what it needs
         scan = ops.jpeg_geometry(h, w, hs, vs)[1]
@@ -131,47 +181,63 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
         ends = np.concatenate([[0], np.cumsum(lengths)])
         segments = [blob[ends[i]:ends[i + 1]] for i in range(n)]
     image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if want_image else None
-    return image, segments
+    return (image, segments, tables) if optimize else (image, segments)
 
 
-def encode_batch(batch_x, quality, subsampling='4:4:4'):
+def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False):
     """The JPEG files of a batch (n,h,w,3) or one image (h,w,3), a list of bytes.  uint8 input is coded as it is; float input goes
-    through the reference's conversion (x / 255 first if its maximum exceeds 1, then (255 x) truncated)."""
+    through the reference's conversion (x / 255 first if its maximum exceeds 1, then (255 x) truncated).  `optimize`: every file with
+    Huffman tables of its own, the files libjpeg writes with optimize_coding (Pillow: optimize=True)."""
     x = _device_batch(batch_x, keep_bytes=True)
     if x.dim() == 3:
         x = x[None]
+    if optimize:
+        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, optimize=True)
+        return [jpeg_header(x.shape[1], x.shape[2], quality, subsampling, huffman=t) + s + b'\xff\xd9' for s, t in zip(segments, tables)]
     _, segments = device_codec(x, quality, subsampling, want_image=False)
     head = jpeg_header(x.shape[1], x.shape[2], quality, subsampling)
     return [head + s + b'\xff\xd9' for s in segments]
 
 
-def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4'):
+def _optimised_header_bytes(tables):
+    """SOI .. SOS with the DHT segments of `tables` (..., 4, 272): 623 with each table's symbols in place of Annex K's 348."""
+    return JPEG_HEADER_BYTES - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)
+
+
+def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False):
     """Compress an image or a batch with the standard JPEG codec (jpeg_helpers.py:82-114).  (h,w,3) -> (float64 image, bytes);
     (n,h,w,3) -> (float32 batch, list of bytes).  `effective` counts from the first Huffman table on instead of the whole file.
     Every input, uint8 included, goes through the reference's conversion: x / 255 in float32 if the maximum exceeds 1, then
-    (255 x) truncated - a byte k can come out as k - 1.  Values that numpy's cast would wrap are clamped to 0..255."""
+    (255 x) truncated - a byte k can come out as k - 1.  Values that numpy's cast would wrap are clamped to 0..255.
+    `optimize`: the sizes are those of the files with optimised Huffman tables (encode_batch(optimize=True)); the image is the same."""
     x = _device_batch(batch_x, keep_bytes=False)
     if x.dim() not in (3, 4):
         raise ValueError('compress_batch needs an (h,w,3) image or an (n,h,w,3) batch')
     single = x.dim() == 3
-    image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling)
-    sizes = [JPEG_HEADER_BYTES + len(s) + 2 - (_DHT_OFFSET if effective else 0) for s in segments]
+    if optimize:
+        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=True)
+        heads = _optimised_header_bytes(tables).tolist()
+    else:
+        image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling)
+        heads = [JPEG_HEADER_BYTES] * len(segments)
+    sizes = [hd + len(s) + 2 - (_DHT_OFFSET if effective else 0) for hd, s in zip(heads, segments)]
     image = image.cpu().numpy()
     if single:
         return np.rint(image[0] * np.float32(255)).astype(np.uint8) / 255, sizes[0]
     return image, sizes
 
 
-def match_quality(image, target=0.95, match='ssim', subsampling='4:4:4'):
-    """The JPEG quality 1..95 whose SSIM or bpp is closest to `target`, by the reference's bisection (jpeg_helpers.py:26-79)."""
+def match_quality(image, target=0.95, match='ssim', subsampling='4:4:4', optimize=False):
+    """The JPEG quality 1..95 whose SSIM or bpp is closest to `target`, by the reference's bisection (jpeg_helpers.py:26-79); with
+    `optimize` the bpp is that of the file with optimised Huffman tables."""
     from ..helpers import metrics
     assert image.ndim == 3, 'Only RGB images supported'
 
     def ssim_gap(q):
-        return metrics.ssim(image, compress_batch(image, q, subsampling=subsampling)[0].squeeze()) - target
+        return metrics.ssim(image, compress_batch(image, q, subsampling=subsampling, optimize=optimize)[0].squeeze()) - target
 
     def bpp_gap(q):
-        return 8 * np.mean(compress_batch(image, q, subsampling=subsampling)[1]) / image.shape[0] / image.shape[1] - target
+        return 8 * np.mean(compress_batch(image, q, subsampling=subsampling, optimize=optimize)[1]) / image.shape[0] / image.shape[1] - target
 
     if match not in ('ssim', 'bpp'):
         raise ValueError('Invalid argument: match')
@@ -214,24 +280,32 @@ def _qualities_per_call(n, h, w, hs, vs, total):
     return k
 
 
-def _item_round(x, item_q, hs, vs, want_lengths, want_images):
+def _item_round(x, item_q, hs, vs, want_lengths, want_images, optimize=False):
     """One item call: source batch x, one quality per item (item j = image j % n) -> (lengths (items,) int32 device tensor or None,
-    decoded (items,h,w,3) device tensor or None).  Nothing is read back."""
+    decoded (items,h,w,3) device tensor or None).  Nothing is read back.  With `optimize` the lengths are those of the segments coded
+    with each item's optimal tables plus what its header has beyond the 623 bytes (so that _file_bytes holds), and a third value is
+    returned: the status (items,) int32 of JPEG_OPT_STATUS_BITS, or None."""
     _, h, w, _ = x.shape
     ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(len(item_q), h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
     q = ops.jpeg_item_qualities(item_q, len(item_q), x.device)
     coef, _ = ops.jpeg_transform_items(x, q, hs, vs, workspace=ws)
-    lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=1)[1] if want_lengths else None      # byte counts only
+    status = None
+    if want_lengths and optimize:
+        _, lengths, tables, status = _optimised(coef, h, w, hs, vs, 1)                                         # byte counts only
+        lengths = lengths + (tables[:, :, :16].sum(dim=(1, 2), dtype=torch.int32) - 348)
+    else:
+        lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=1)[1] if want_lengths else None      # byte counts only
     y = ops.jpeg_reconstruct_items(coef, h, w, q, hs, vs, workspace=ws)[0] if want_images else None
-    return lengths, y
+    return (lengths, y, status) if optimize else (lengths, y)
 
 
-def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, want_images=False):
+def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, want_images=False, optimize=False):
     """The rate-distortion table of a batch (n,h,w,3) over Q qualities: a dict of (Q, n) arrays 'ssim', 'psnr', 'msssim', 'msssim_db'
     (helpers.metrics of the source against what libjpeg decodes), 'bytes' and 'bpp' (compress_batch's count: the whole file, or from
     the first Huffman table on when `effective`).  With want_images also the decoded (Q,n,h,w,3) device tensor.  The batch is
     uploaded once and coded as Q * n items - one transform, one encode and one reconstruct call, or one set per group of qualities
-    where the workspace would exceed RD_WORKSPACE_BUDGET - and the numbers come back in one download."""
+    where the workspace would exceed RD_WORKSPACE_BUDGET - and the numbers come back in one download.  With `optimize` the byte counts
+    are those of the files with optimised Huffman tables (three more calls per group); everything else is unchanged."""
     from ..helpers import metrics
     q = _check_qualities(qualities)
     hs, vs = ops.jpeg_subsampling(subsampling)
@@ -243,17 +317,20 @@ def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, wan
     rows, images = [], []
     for k0 in range(0, len(q), step):
         part = q[k0:k0 + step]
-        lengths, y = _item_round(x, np.repeat(part, n), hs, vs, True, True)           # quality-major: item j = (part[j // n], image j % n)
+        done = _item_round(x, np.repeat(part, n), hs, vs, True, True, optimize)        # quality-major: item j = (part[j // n], image j % n)
+        lengths, y = done[0], done[1]
+        status = done[2] if optimize else torch.zeros_like(lengths)
         y = y.view(len(part), n, h, w, 3)
         for k in range(len(part)):
             ms = metrics._msssim_device(x, y[k])
             rows.append(torch.stack([ops.ssim(x, y[k], mode='skimage', max_val=1.0).double(),
                                      10.0 * torch.log10(1.0 / metrics._mean_per_image(x, y[k], lambda d: d * d)),
                                      torch.full((n,), float('nan'), dtype=torch.float64, device=x.device) if ms is None else ms.double(),
-                                     lengths[k * n:(k + 1) * n].double()]))
+                                     lengths[k * n:(k + 1) * n].double(), status[k * n:(k + 1) * n].double()]))
         if want_images:
             images.append(y)
-    table = torch.stack(rows).cpu().numpy()                            # (Q, 4, n): the one download
+    table = torch.stack(rows).cpu().numpy()                            # (Q, 5, n): the one download
+    _raise_on_opt_status(table[:, 4].astype(np.int64).reshape(-1))
     size = _file_bytes(table[:, 3].astype(np.int64), effective)
     with np.errstate(divide='ignore'):
         out = {'ssim': table[:, 0], 'psnr': table[:, 1], 'msssim': table[:, 2], 'msssim_db': -10.0 * np.log10(1.0 - table[:, 2]),
@@ -263,11 +340,11 @@ def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, wan
     return out
 
 
-def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4'):
+def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4', optimize=False):
     """match_quality for every image of a batch (n,h,w,3) at once: the reference's bisection over 1..95, where each round is one item
     call in which image i carries its own current quality - 8 calls whatever n is (the two end points share the first).  `target`
     is a scalar or one value per image.  Returns an int array (n,).  An image whose end points do not bracket its target raises the
-    reference's ValueError, naming the first such image."""
+    reference's ValueError, naming the first such image.  With `optimize` the bpp is that of the files with optimised Huffman tables."""
     if match not in ('ssim', 'bpp'):
         raise ValueError('Invalid argument: match')
     shape = tuple(unwrap(batch_x).shape)
@@ -287,8 +364,13 @@ def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4')
             _, y = _item_round(x, item_q, hs, vs, False, True)
             v = torch.cat([ops.ssim(x, y[r * n:(r + 1) * n], mode='skimage', max_val=1.0) for r in range(reps)]).double().cpu().numpy()
         else:
-            lengths, _ = _item_round(x, item_q, hs, vs, True, False)
-            v = 8 * _file_bytes(lengths.cpu().numpy().astype(np.float64), False) / h / w
+            if optimize:
+                lengths, _, status = _item_round(x, item_q, hs, vs, True, False, True)
+                lengths, status = torch.stack([lengths, status]).cpu().numpy()
+                _raise_on_opt_status(status)
+            else:
+                lengths = _item_round(x, item_q, hs, vs, True, False)[0].cpu().numpy()
+            v = 8 * _file_bytes(lengths.astype(np.float64), False) / h / w
         return v - np.tile(target, reps)
 
     low, high = np.full(n, 1, np.int64), np.full(n, 95, np.int64)

@@ -44,16 +44,17 @@ def _write_png(directory, filename, name, image):
     Image.fromarray((255 * image).astype(np.uint8)).save(os.path.join(image_dir, name))
 
 
-def get_jpeg_df(directory, write_files=False, effective_bytes=True, force_calc=False):
+def get_jpeg_df(directory, write_files=False, effective_bytes=True, force_calc=False, optimize=False):
     """The rate-distortion curve of JPEG over the images of `directory` as a pandas DataFrame, saved as <directory>/jpeg.csv; if that
-    file exists it is read and returned instead."""
+    file exists it is read and returned instead.  With `optimize` the byte counts are those of files with optimised Huffman tables and
+    the file is <directory>/jpeg-optimized.csv, so that a cached jpeg.csv is never taken for it."""
     import pandas as pd
-    df_path = os.path.join(directory, 'jpeg.csv')
+    df_path = os.path.join(directory, 'jpeg-optimized.csv' if optimize else 'jpeg.csv')
     if os.path.isfile(df_path) and not force_calc:
         return pd.read_csv(df_path, index_col=False, float_precision='round_trip')
     files, batch_x = _load(directory)
     quality_levels = np.arange(95, 5, -5)
-    rd = jpeg_helpers.rate_distortion(batch_x, quality_levels, effective=effective_bytes, want_images=write_files)
+    rd = jpeg_helpers.rate_distortion(batch_x, quality_levels, effective=effective_bytes, want_images=write_files, optimize=optimize)
     if write_files:
         rd, decoded = rd
         decoded = decoded.cpu().numpy()

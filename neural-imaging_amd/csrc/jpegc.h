@@ -254,3 +254,10 @@ inline bool grid_ok(long items, int per_block) { return (items + per_block - 1) 
 NIMG_HIDDEN int nimg_internal_jpeg_above_one(const float* x, long count, uint32_t* flag, hipStream_t stream);
 // the sample planes of n images (as nimg_jpeg_reconstruct's inverse DCT leaves them) -> y (n,h,w,3)
 NIMG_HIDDEN int nimg_internal_jpeg_colour(uint8_t* planes, float* y, int n, int h, int w, int hs, int vs, hipStream_t stream);
+// nimg_jpeg_encode's passes around the bit-length and the emit pass, for jpegc_opt.hip (a raw buffer of raw_words words per image):
+// off[n][SB] bit lengths -> offsets in place, total[n]; the words of raw the bits will be OR-ed into zeroed
+NIMG_HIDDEN int nimg_internal_jpeg_offsets(uint32_t* off, uint32_t* total, uint32_t* raw, int n, int SB, unsigned raw_words,
+                                           hipStream_t stream);
+// raw -> lengths[n], dst[n], and the stuffed bytes of all images back to back in out, none at or beyond capacity
+NIMG_HIDDEN int nimg_internal_jpeg_pack(const uint32_t* raw, const uint32_t* total, uint32_t* lengths, unsigned long long* dst, uint8_t* out,
+                                        size_t capacity, int n, unsigned raw_words, hipStream_t stream);

@@ -471,3 +471,24 @@ int nimg_internal_jpeg_colour(uint8_t* planes, float* y, int n, int h, int w, in
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
+
+int nimg_internal_jpeg_offsets(uint32_t* off, uint32_t* total, uint32_t* raw, int n, int SB, unsigned raw_words, hipStream_t stream) {
+    hipLaunchKernelGGL(jpeg_bitscan_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, off, total, SB);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_zero_kernel, dim3((raw_words / 4 + 255) / 256, (unsigned)n), dim3(256), 0, stream, raw, (const uint32_t*)total,
+                       raw_words);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_internal_jpeg_pack(const uint32_t* raw, const uint32_t* total, uint32_t* lengths, unsigned long long* dst, uint8_t* out,
+                            size_t capacity, int n, unsigned raw_words, hipStream_t stream) {
+    hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, raw, total, lengths, raw_words);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_imgscan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, (const uint32_t*)lengths, dst, n);
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, raw, total, (const unsigned long long*)dst, out,
+                       (unsigned long long)capacity, raw_words);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}

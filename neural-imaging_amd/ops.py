@@ -2429,3 +2429,71 @@ def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspa
         raise RuntimeError('jpeg_reconstruct_tables: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, (n, h, w, 3)))
     _lib.call('nimg_jpeg_reconstruct_tables', _p(coef), n, h, w, hs, vs, _p(qtabs), _p(y), int(bool(out_u8)), _p(ws), need, _stream())
     return y
+
+
+# optimised Huffman tables: a table is 16 counts + 256 symbols in code order, an image has four of them in
+# DHT-id order 00 (Y DC), 10 (Y AC), 01 (chroma DC), 11 (chroma AC)
+JPEG_TABLE_BYTES = 272
+JPEG_BLOCK_BITS_MAX_TABLES = 1665       # a DC code may take 16 bits: 16 + 11 bits, 63 x (AC 16 + 10)
+
+
+def jpeg_ecd_bound_tables(h, w, hs, vs):
+    """jpeg_ecd_bound for segments coded with caller-supplied tables."""
+    return 2 * -(-jpeg_geometry(h, w, hs, vs)[1] * JPEG_BLOCK_BITS_MAX_TABLES // 8)
+
+
+def jpeg_histogram(coef, h, w, hs=1, vs=1, out=None):
+    """Coefficients of jpeg_transform -> (n, 4, 257) int32: how often jpeg_encode emits each symbol of each table; entry 256 is 0."""
+    _chk(coef)
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('jpeg_histogram: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    hist = torch.empty((n, 4, 257), dtype=torch.int32, device=coef.device) if out is None else out
+    _chk(hist)
+    if hist.dtype != torch.int32 or tuple(hist.shape) != (n, 4, 257):
+        raise RuntimeError('jpeg_histogram: output {} {}, int32 {} needed'.format(hist.dtype, tuple(hist.shape), (n, 4, 257)))
+    _lib.call('nimg_jpeg_histogram', _p(coef), n, h, w, hs, vs, _p(hist), _stream())
+    return hist
+
+
+def jpeg_optimal_tables(hist):
+    """Histograms (..., 257) int32 (the bit patterns of uint32 counts) -> (tables (..., 272) uint8 by libjpeg's jpeg_gen_optimal_table,
+    status (...,) int32: 0, 1 = a code size above 32, 2 = a total of 2^32 or more; a table with a status is all zeros)."""
+    _chk(hist)
+    if hist.dtype != torch.int32 or hist.dim() < 1 or hist.shape[-1] != 257 or hist.numel() == 0:
+        raise RuntimeError('jpeg_optimal_tables: int32 histograms (..., 257) needed, got {} {}'.format(hist.dtype, tuple(hist.shape)))
+    lead = tuple(hist.shape[:-1])
+    m = hist.numel() // 257
+    tables = torch.empty(lead + (JPEG_TABLE_BYTES,), dtype=torch.uint8, device=hist.device)
+    status = torch.empty(lead, dtype=torch.int32, device=hist.device)
+    _lib.call('nimg_jpeg_optimal_tables', _p(hist), m, _p(tables), _p(status), _stream())
+    return tables, status
+
+
+def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None):
+    """jpeg_encode with the Huffman tables of each image given: tables (n, 4, 272) uint8 -> (segments back to back (uint8), lengths
+    (n,) int32, status (n,) int32: bits 1 = tables that are no prefix code (length 0), 2 = a symbol of the image has no code)."""
+    _chk(coef)
+    _chk(tables)
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('jpeg_encode_tables: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    if tables.dtype != torch.uint8 or tuple(tables.shape) != (n, 4, JPEG_TABLE_BYTES):
+        raise RuntimeError('jpeg_encode_tables: tables {} {}, ({}, 4, 272) uint8 needed'.format(tables.dtype, tuple(tables.shape), n))
+    need = int(_lib.load().nimg_jpeg_encode_tables_workspace_bytes(n, h, w, hs, vs))
+    if need == 0:
+        raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=coef.device)
+    _chk(workspace)
+    if workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError('JPEG workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
+    if out is None:
+        out = torch.empty(n * jpeg_ecd_bound_tables(h, w, hs, vs) if capacity is None else int(capacity), dtype=torch.uint8,
+                          device=coef.device)
+    _chk(out)
+    lengths = torch.empty(n, dtype=torch.int32, device=coef.device)
+    status = torch.empty(n, dtype=torch.int32, device=coef.device)
+    _lib.call('nimg_jpeg_encode_tables', _p(coef), n, h, w, hs, vs, _p(tables), _p(out),
+              out.numel() if capacity is None else int(capacity), _p(lengths), _p(status), _p(workspace), need, _stream())
+    return out, lengths, status

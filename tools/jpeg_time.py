@@ -12,8 +12,11 @@ images through Pillow (libjpeg), one after the other, where Pillow is installed;
 and per kernel (prepare, speculate, sync, write, dc - from the profiler's kernel records), the synchronisation rounds,
 nimg_jpeg_reconstruct_tables and decode_batch from bytes to bytes, at subseq_bits 256, 512, 1024, 2048 and at one subsequence per
 image - the sequential decode the parallel one is measured against.  One JSON line per sub-sampling and setting.
+--optimize times writing with optimised Huffman tables: nimg_jpeg_histogram, nimg_jpeg_optimal_tables and
+nimg_jpeg_encode_tables next to nimg_jpeg_encode on the same coefficients, encode_batch with and without optimize from host batch
+to files, and the segment and whole-file bytes either way.  One JSON line per sub-sampling.
 
-    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode]
+    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode | --optimize]
 For the split of the calls into their kernels: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_time.py ...
 """
 import argparse
@@ -139,6 +142,35 @@ def measure_decode(x_host, quality, subsampling, reps, dev):
     return rows
 
 
+def measure_optimize(x_host, quality, subsampling, reps, dev):
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    n, h, w, _ = x_host.shape
+    lib = ops._lib.load()
+    coef = ops.jpeg_transform(torch.from_numpy(x_host).to(dev), quality, hs, vs)
+    ws = torch.empty(int(lib.nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    ws_t = torch.empty(int(lib.nimg_jpeg_encode_tables_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
+    hist = torch.empty((n, 4, 257), dtype=torch.int32, device=dev)
+    ms = {}
+    ms['encode'], (_, base) = timed(lambda: ops.jpeg_encode(coef, h, w, hs, vs, out=out, workspace=ws), reps)
+    base = base.cpu().numpy().astype(np.int64)
+    ms['histogram'], _ = timed(lambda: ops.jpeg_histogram(coef, h, w, hs, vs, out=hist), reps)
+    ms['optimal_tables'], (tables, tstatus) = timed(lambda: ops.jpeg_optimal_tables(hist), reps)
+    ms['encode_tables'], (_, lengths, status) = timed(lambda: ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, out=out, workspace=ws_t), reps)
+    assert int(tstatus.abs().sum()) == 0 and int(status.abs().sum()) == 0
+    lengths = lengths.cpu().numpy().astype(np.int64)
+    ms['encode_batch_total'], plain = timed(lambda: jpeg_helpers.encode_batch(x_host, quality, subsampling), max(3, reps // 4))
+    ms['encode_batch_optimize_total'], files = timed(lambda: jpeg_helpers.encode_batch(x_host, quality, subsampling, optimize=True), max(3, reps // 4))
+    assert [len(f) for f in plain] == (base + jpeg_helpers.JPEG_HEADER_BYTES + 2).tolist()
+    heads = jpeg_helpers._optimised_header_bytes(tables.cpu().numpy())
+    assert [len(f) for f in files] == (lengths + heads + 2).tolist()
+    return {'mode': 'optimize', 'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality,
+            'segment_bytes': int(base.sum()), 'segment_bytes_optimize': int(lengths.sum()),
+            'file_bytes': int(sum(len(f) for f in plain)), 'file_bytes_optimize': int(sum(len(f) for f in files)),
+            'workspace_bytes': ws.numel(), 'workspace_bytes_tables': ws_t.numel(),
+            'ms': {k: round(v, 4) for k, v in ms.items()}, 'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
+
+
 def pillow(x_host, quality, subsampling, reps):
     from PIL import Image
     u8 = np.clip(np.trunc(np.float32(255) * x_host), 0, 255).astype(np.uint8)
@@ -162,6 +194,7 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--pillow', action='store_true', help='time Pillow on the host instead (no GPU needed)')
     ap.add_argument('--decode', action='store_true', help='time the decoder instead, per subseq_bits setting')
+    ap.add_argument('--optimize', action='store_true', help='time writing with optimised Huffman tables next to nimg_jpeg_encode')
     args = ap.parse_args()
     x = natural_images(args.batch, args.size, args.size, seed=1)
     if args.pillow:
@@ -176,6 +209,11 @@ def main():
             measure_decode(x[:4], args.quality, subsampling, 2, dev)                  # warm-up
             for row in measure_decode(x, args.quality, subsampling, args.reps, dev):
                 print(json.dumps(dict(row, csrc_sha16=csrc_sha16())), flush=True)
+        return
+    if args.optimize:
+        for subsampling in SUBSAMPLINGS:
+            measure_optimize(x[:4], args.quality, subsampling, 2, dev)                # warm-up
+            print(json.dumps(dict(measure_optimize(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())), flush=True)
         return
     for subsampling in SUBSAMPLINGS:
         measure(x, args.quality, subsampling, 3, dev)                    # warm-up: code objects, allocator
