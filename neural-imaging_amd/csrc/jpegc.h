@@ -1,62 +1,49 @@
-// What the two units of the baseline JPEG codec share (jpegc.hip: one quality per batch and the entropy coder; jpegc_items.hip: one
-// quality per image): geometry and workspace layout, the quantisation tables, and the device functions of the forward and inverse
-// transform.  Everything here has internal linkage - each unit compiles its own copy.
+// What the units of the JPEG family share (jpegc.hip: one quality per batch and the entropy coder; jpegc_items.hip: one quality per
+// image; jpegd.hip: the tables of each file; jpegc_opt.hip: the coder with the caller's Huffman tables): the workspace layout, the
+// quantisation tables, the bit sink of the two coders, and the forward-transform and inverse-DCT kernels as templates over where their
+// quantisation table comes from - a unit instantiates them with its own table source, so each instantiation knows the address space it
+// reads.  Everything here has internal linkage - each unit compiles its own copy.
 #pragma once
 #include "common.h"
+#include "jpeg_geo.h"
 
 namespace {
 
-constexpr int BLOCK_BITS_MAX = 1658;        // DC 9 + 11, 63 x (AC 16 + 10): the longest block with the Annex K tables
 constexpr int SCAN_THREADS = 1024;
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// ---- geometry ---------------------------------------------------------------------------------------------------------
-struct Geo {
-    int n, h, w, hs, vs, hsh;          // hsh = log2(hs)
-    int bhY, bwY, bhC, bwC;            // real extent in blocks: ceil(ceil(W * h / hmax) / 8), the same for the height
-    int ceh, cew;                      // chroma extent in samples: ceil(H / vs), ceil(W / hs)
-    int my, mx, per;                   // MCU grid; blocks per MCU = hs * vs + 2
-    int nbY, nbC, NB;                  // real blocks per image: Y, one chroma component, all three
-    int SB;                            // blocks per image in scan order, dummies included
-    unsigned raw_words;                // capacity of one image's un-stuffed bit buffer, in 32-bit words
-};
-
-bool make_geo(Geo* g, int n, int h, int w, int hs, int vs) {
-    if (n < 1 || n > 65535 || h < 1 || w < 1 || h > 4096 || w > 4096) return false;
-    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
-    g->n = n; g->h = h; g->w = w; g->hs = hs; g->vs = vs; g->hsh = hs - 1;
-    g->bhY = (h + 7) / 8; g->bwY = (w + 7) / 8;
-    g->ceh = (h + vs - 1) / vs; g->cew = (w + hs - 1) / hs;
-    g->bhC = (g->ceh + 7) / 8; g->bwC = (g->cew + 7) / 8;
-    g->my = (h + 8 * vs - 1) / (8 * vs); g->mx = (w + 8 * hs - 1) / (8 * hs);
-    g->per = hs * vs + 2;
-    g->nbY = g->bhY * g->bwY; g->nbC = g->bhC * g->bwC; g->NB = g->nbY + 2 * g->nbC;
-    g->SB = g->my * g->mx * g->per;
-    const unsigned long words = ((unsigned long)g->SB * BLOCK_BITS_MAX + 31) / 32 + 1;
-    g->raw_words = (unsigned)((words + 3) & ~3ul);
-    return (long)n * g->SB < 0x7fffffffL;
-}
+// ---- geometry and workspace ---------------------------------------------------------------------------------------------
+// The longest block with the Annex K tables: DC 9 + 11, 63 x (AC 16 + 10).  JPEGOPT_BLOCK_BITS_MAX, the bound with a caller's tables, is
+// 7 bits larger because a DC code may then have 16 bits where Annex K's longest has 9; an AC code has up to 16 bits in both.
+constexpr int BLOCK_BITS_MAX = 1658;
 
 struct Workspace {
     uint32_t* flag;                    // transform: non-zero = some float sample exceeds 1
+    uint32_t* codes;                   // coder with the caller's tables: [n][code_words] symbol -> code << 5 | length
     uint32_t* off;                     // [n][SB] bit lengths, then (in place) bit offsets
     uint32_t* total;                   // [n] bits of an image before the final padding
     unsigned long long* dst;           // [n] first byte of an image's segment in the output
     uint32_t* raw;                     // [n][raw_words] the un-stuffed bits, MSB first in every word
+    unsigned raw_words;                // capacity of one image's slot of `raw`: SB blocks of block_bits bits, a multiple of 4 words
     uint8_t* planes;                   // reconstruct: [n][Y | Cb | Cr] sample planes over the real blocks
     size_t bytes;
 };
 
-Workspace carve(const Geo& g, void* base) {
-    Workspace ws;
+// code_words = 0: the workspace of the baseline codec.  Otherwise that of the coder with the caller's tables, which keeps code_words code
+// words per image, never transforms or reconstructs, and so has neither flag nor planes.
+inline Workspace carve(const JpegGeo& g, void* base, int block_bits = BLOCK_BITS_MAX, int code_words = 0) {
+    Workspace ws{};
     uint8_t* p = (uint8_t*)base;
-    ws.flag = (uint32_t*)p; p += 256;
+    const unsigned long words = ((unsigned long)g.SB * block_bits + 31) / 32 + 1;
+    ws.raw_words = (unsigned)((words + 3) & ~3ul);
+    if (code_words) { ws.codes = (uint32_t*)p; p += align256((size_t)g.n * code_words * 4); }
+    else { ws.flag = (uint32_t*)p; p += 256; }
     ws.off = (uint32_t*)p; p += align256((size_t)g.n * g.SB * 4);
     ws.total = (uint32_t*)p; p += align256((size_t)g.n * 4);
     ws.dst = (unsigned long long*)p; p += align256((size_t)g.n * 8);
-    ws.raw = (uint32_t*)p; p += align256((size_t)g.n * g.raw_words * 4);
-    ws.planes = p; p += align256((size_t)g.n * g.NB * 64);
+    ws.raw = (uint32_t*)p; p += align256((size_t)g.n * ws.raw_words * 4);
+    if (!code_words) { ws.planes = p; p += align256((size_t)g.n * g.NB * 64); }
     ws.bytes = (size_t)(p - (uint8_t*)base);
     return ws;
 }
@@ -69,6 +56,16 @@ __constant__ const unsigned char c_nat_of_zz[64] = {0,  1,  8,  16, 9,  2,  3,  
                                                     58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 struct QTabs { uint16_t q[2][64]; };        // [luma | chroma], natural order
+
+// A table source is what the transform and the inverse-DCT kernel are templates over:
+//   table(g, t, item, comp)   the 64 divisors, natural order, of component `comp` of image `item`; t = the thread's block in the batch
+//   source(item)              the image whose pixels item `item` transforms
+// This one passes the tables of one quality for the whole batch by value in the kernel arguments.
+struct BatchTables {
+    QTabs qt;
+    __device__ __forceinline__ const uint16_t* table(const JpegGeo&, long, int, int comp) const { return qt.q[comp ? 1 : 0]; }
+    __device__ __forceinline__ int source(int item) const { return item; }
+};
 
 constexpr int Q_BASE[2][64] = {
     {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -143,7 +140,7 @@ __device__ __forceinline__ void load_rgb(const void* img, int w, int y, int x, b
 // sample (y, x) of component `comp` as the forward DCT sees it: the right edge replicated at full resolution, the bottom row up
 // to a multiple of the vertical factor, chroma down-sampled, then the component's last row replicated downwards
 template <bool U8>
-__device__ __forceinline__ int sample(const void* img, const Geo& g, int comp, int y, int x, bool div) {
+__device__ __forceinline__ int sample(const void* img, const JpegGeo& g, int comp, int y, int x, bool div) {
     int r, gg, b;
     if (comp == 0) {
         load_rgb<U8>(img, g.w, min(y, g.h - 1), min(x, g.w - 1), div, r, gg, b);
@@ -211,7 +208,7 @@ __device__ __forceinline__ void idct8(int* d, int n) {
 }
 
 // real block t of the batch -> image, component, block row / column
-__device__ __forceinline__ void locate(const Geo& g, long t, int& img, int& comp, int& br, int& bc) {
+__device__ __forceinline__ void locate(const JpegGeo& g, long t, int& img, int& comp, int& br, int& bc) {
     img = (int)(t / g.NB);
     int b = (int)(t - (long)img * g.NB);
     if (b < g.nbY) {
@@ -224,14 +221,51 @@ __device__ __forceinline__ void locate(const Geo& g, long t, int& img, int& comp
     }
 }
 
+// one thread per real block
+template <bool U8, class Tables>
+__global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restrict__ x, int16_t* __restrict__ coef, JpegGeo g, Tables tabs,
+                                                             const uint32_t* __restrict__ flag) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.NB) return;
+    int item, comp, br, bc;
+    locate(g, t, item, comp, br, bc);
+    const bool div = !U8 && *flag != 0;
+    const int img = tabs.source(item);
+    const void* base = U8 ? (const void*)((const uint8_t*)x + (long)img * g.h * g.w * 3)
+                          : (const void*)((const float*)x + (long)img * g.h * g.w * 3);
+    const uint16_t* q = tabs.table(g, t, item, comp);
+    int d[64];
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) d[8 * r + c] = sample<U8>(base, g, comp, 8 * br + r, 8 * bc + c, div) - 128;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) fdct8<1, true>(d + 8 * r);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) fdct8<8, false>(d + c);
+    uint32_t o[32];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const int nat = c_nat_of_zz[k];
+        const int v = d[nat], qv = (int)q[nat] << 3;
+        const int m = (int)(((unsigned)abs(v) + (unsigned)(qv >> 1)) / (unsigned)qv);
+        const uint32_t c16 = (uint32_t)(v < 0 ? -m : m) & 0xffffu;
+        if (k & 1) o[k >> 1] |= c16 << 16;
+        else o[k >> 1] = c16;
+    }
+    uint4* dst = reinterpret_cast<uint4*>(coef + t * 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dst[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+}
+
 // ---- reconstruct --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint8_t* plane_of(uint8_t* planes, const Geo& g, int img, int comp) {
+__device__ __forceinline__ uint8_t* plane_of(uint8_t* planes, const JpegGeo& g, int img, int comp) {
     return planes + (size_t)img * g.NB * 64 + (comp ? (size_t)g.nbY * 64 + (size_t)(comp - 1) * g.nbC * 64 : 0);
 }
 
 // chroma sample at full-resolution (y, x): libjpeg's "fancy" triangle filter over the component's real extent; with at most two
 // chroma columns libjpeg replicates instead
-__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const Geo& g, int y, int x) {
+__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const JpegGeo& g, int y, int x) {
     const int stride = 8 * g.bwC;
     if (g.hs == 1) return p[(size_t)y * stride + x];
     const int i = x >> 1, j = g.vs == 2 ? y >> 1 : y;
@@ -244,17 +278,92 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const Ge
     return (3 * si + sn + 8 - (x & 1)) >> 4;
 }
 
+// one thread per real block: dequantise, inverse DCT (columns, then rows), + 128, clamp -> the component's sample plane
+template <class Tables>
+__global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t* __restrict__ coef, uint8_t* __restrict__ planes, JpegGeo g, Tables tabs) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)g.n * g.NB) return;
+    int img, comp, br, bc;
+    locate(g, t, img, comp, br, bc);
+    const uint16_t* q = tabs.table(g, t, img, comp);
+    const uint4* src = reinterpret_cast<const uint4*>(coef + t * 64);
+    uint32_t wds[32];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint4 v = src[j];
+        wds[4 * j] = v.x; wds[4 * j + 1] = v.y; wds[4 * j + 2] = v.z; wds[4 * j + 3] = v.w;
+    }
+    int d[64];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const int nat = c_nat_of_zz[k];
+        d[nat] = (int)(short)(wds[k >> 1] >> (16 * (k & 1))) * (int)q[nat];
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) idct8<8>(d + c, 11);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) idct8<1>(d + 8 * r, 18);
+    const int stride = 8 * (comp ? g.bwC : g.bwY);
+    uint8_t* p = plane_of(planes, g, img, comp) + (size_t)(8 * br) * stride + 8 * bc;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            lo |= (uint32_t)min(max(d[8 * r + c] + 128, 0), 255) << (8 * c);
+            hi |= (uint32_t)min(max(d[8 * r + 4 + c] + 128, 0), 255) << (8 * c);
+        }
+        *reinterpret_cast<uint2*>(p + (size_t)r * stride) = make_uint2(lo, hi);
+    }
+}
+
+// ---- entropy coding -----------------------------------------------------------------------------------------------------
+// bit sink: EMIT = false only counts.  Bits are MSB first; word j of the image's buffer holds bits 32 j .. 32 j + 31.  The first
+// and the last word a block touches may be shared with its neighbours: OR-ed into zeroed memory; the words in between are its own.
+// A coder derives from it and adds symbol(table, symbol, value bits, their number), which jpegopt_walk_block calls.
+template <bool EMIT>
+struct BitSink {
+    uint32_t* base;
+    unsigned widx, cap, count;
+    unsigned long long acc;
+    int nacc;
+    bool first;
+    __device__ __forceinline__ void init(uint32_t* b, unsigned cap_words, unsigned bit0) {
+        base = b; cap = cap_words; widx = bit0 >> 5; nacc = (int)(bit0 & 31u); acc = 0; first = true; count = 0;
+    }
+    __device__ __forceinline__ void put(uint32_t v, int len) {          // len <= 27 (a code of 16 bits + 11 value bits), v < 2^len
+        count += (unsigned)len;
+        if (!EMIT) return;
+        acc = (acc << len) | v;
+        nacc += len;
+        if (nacc >= 32) {
+            const uint32_t word = (uint32_t)(acc >> (nacc - 32));
+            if (widx < cap) {
+                if (first) atomicOr(base + widx, word);
+                else base[widx] = word;
+            }
+            first = false;
+            ++widx;
+            nacc -= 32;
+            acc &= (1ull << nacc) - 1ull;
+        }
+    }
+    __device__ __forceinline__ void finish() {
+        if (EMIT && nacc > 0 && widx < cap) atomicOr(base + widx, (uint32_t)(acc << (32 - nacc)));
+    }
+};
+
 inline bool grid_ok(long items, int per_block) { return (items + per_block - 1) / per_block <= 0x7fffffffL; }
 
 }  // namespace
 
-// ---- launches of jpegc.hip's kernels for jpegc_items.hip: not part of the ABI, and hidden - libnimg.so does not export them -------------
+// ---- launches of jpegc.hip's kernels for the other units: not part of the ABI, and hidden - libnimg.so does not export them -------------
 #define NIMG_HIDDEN __attribute__((visibility("hidden")))
 // *flag |= 1 if any of the `count` floats at x exceeds 1 (flag zeroed here); 0 or NIMG_ERR_LAUNCH
 NIMG_HIDDEN int nimg_internal_jpeg_above_one(const float* x, long count, uint32_t* flag, hipStream_t stream);
-// the sample planes of n images (as nimg_jpeg_reconstruct's inverse DCT leaves them) -> y (n,h,w,3)
-NIMG_HIDDEN int nimg_internal_jpeg_colour(uint8_t* planes, float* y, int n, int h, int w, int hs, int vs, hipStream_t stream);
-// nimg_jpeg_encode's passes around the bit-length and the emit pass, for jpegc_opt.hip (a raw buffer of raw_words words per image):
+// the sample planes of g.n images (as the inverse DCT leaves them) -> y (n,h,w,3): float32 k / 255, or the bytes themselves if u8
+NIMG_HIDDEN int nimg_internal_jpeg_colour(uint8_t* planes, void* y, bool u8, const JpegGeo& g, hipStream_t stream);
+// the coder's passes around its bit-length and its emit pass (a raw buffer of raw_words words per image):
 // off[n][SB] bit lengths -> offsets in place, total[n]; the words of raw the bits will be OR-ed into zeroed
 NIMG_HIDDEN int nimg_internal_jpeg_offsets(uint32_t* off, uint32_t* total, uint32_t* raw, int n, int SB, unsigned raw_words,
                                            hipStream_t stream);

@@ -8,7 +8,10 @@
 //                  count the FF bytes per image | scan the segment lengths | scatter the bytes with their 00 stuffing
 //   reconstruct  coefficients -> float32 NHWC (dequantise, jidctint inverse DCT, fancy chroma up-sampling, colour, k / 255)
 // Nothing here loops over images or blocks on the host, and nothing is read back: the caller synchronises once for `lengths`.
+// The transform and inverse-DCT kernels and the bit sink are jpegc.h's, instantiated here for one quality per batch; the scan-order
+// block walk is csrc/jpegopt.h's, the one tests/jpegopt_host.cpp runs on the host.
 #include "jpegc.h"
+#include "jpegopt.h"
 
 namespace {
 
@@ -57,156 +60,25 @@ __global__ void __launch_bounds__(256) jpeg_above_one_kernel(const float* __rest
     if (__ballot(any) != 0 && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
 
-// one thread per real block
-template <bool U8>
-__global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restrict__ x, int16_t* __restrict__ coef, Geo g, QTabs qt,
-                                                             const uint32_t* __restrict__ flag) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long)g.n * g.NB) return;
-    int img, comp, br, bc;
-    locate(g, t, img, comp, br, bc);
-    const bool div = !U8 && *flag != 0;
-    const void* base = U8 ? (const void*)((const uint8_t*)x + (long)img * g.h * g.w * 3)
-                          : (const void*)((const float*)x + (long)img * g.h * g.w * 3);
-    int d[64];
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) d[8 * r + c] = sample<U8>(base, g, comp, 8 * br + r, 8 * bc + c, div) - 128;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) fdct8<1, true>(d + 8 * r);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) fdct8<8, false>(d + c);
-    const uint16_t* q = qt.q[comp ? 1 : 0];
-    uint32_t o[32];
-#pragma unroll
-    for (int k = 0; k < 64; ++k) {
-        const int nat = c_nat_of_zz[k];
-        const int v = d[nat], qv = (int)q[nat] << 3;
-        const int m = (int)(((unsigned)abs(v) + (unsigned)(qv >> 1)) / (unsigned)qv);
-        const uint32_t c16 = (uint32_t)(v < 0 ? -m : m) & 0xffffu;
-        if (k & 1) o[k >> 1] |= c16 << 16;
-        else o[k >> 1] = c16;
-    }
-    uint4* dst = reinterpret_cast<uint4*>(coef + t * 64);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dst[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
-}
-
 // ---- entropy coding -----------------------------------------------------------------------------------------------------
-// bit sink: EMIT = false only counts.  Bits are MSB first; word j of the image's buffer holds bits 32 j .. 32 j + 31.  The first
-// and the last word a block touches may be shared with its neighbours: OR-ed into zeroed memory; the words in between are its own.
+// the shared bit sink behind the Annex K codes in constant memory; table = 0 Y DC, 1 Y AC, 2 chroma DC, 3 chroma AC
 template <bool EMIT>
-struct BitSink {
-    uint32_t* base;
-    unsigned widx, cap, count;
-    unsigned long long acc;
-    int nacc;
-    bool first;
-    __device__ __forceinline__ void init(uint32_t* b, unsigned cap_words, unsigned bit0) {
-        base = b; cap = cap_words; widx = bit0 >> 5; nacc = (int)(bit0 & 31u); acc = 0; first = true; count = 0;
-    }
-    __device__ __forceinline__ void put(uint32_t v, int len) {          // len <= 26, v < 2^len
-        count += (unsigned)len;
-        if (!EMIT) return;
-        acc = (acc << len) | v;
-        nacc += len;
-        if (nacc >= 32) {
-            const uint32_t word = (uint32_t)(acc >> (nacc - 32));
-            if (widx < cap) {
-                if (first) atomicOr(base + widx, word);
-                else base[widx] = word;
-            }
-            first = false;
-            ++widx;
-            nacc -= 32;
-            acc &= (1ull << nacc) - 1ull;
-        }
-    }
-    __device__ __forceinline__ void finish() {
-        if (EMIT && nacc > 0 && widx < cap) atomicOr(base + widx, (uint32_t)(acc << (32 - nacc)));
+struct HuffSink : BitSink<EMIT> {
+    __device__ __forceinline__ void symbol(int table, int sym, uint32_t value, int nbits) {
+        const uint32_t e = (table & 1) ? c_huff.ac[table >> 1][sym] : c_huff.dc[table >> 1][sym];
+        this->put(((e >> 5) << nbits) | value, (int)(e & 31u) + nbits);
     }
 };
 
-__device__ __forceinline__ int category(int a) { return 32 - __clz(a); }        // of |value|; 0 for 0
-
-// the DC of Y block k of MCU (mr, mc) as it is coded: a dummy block (beyond the real extent, to the right or below) carries the DC
-// of the block before it in the MCU; block 0 of an MCU is always real
-__device__ __forceinline__ int y_dc(const int16_t* __restrict__ cy, const Geo& g, int mr, int mc, int k, bool& real) {
-    real = true;
-    for (;; --k) {
-        const int br = mr * g.vs + (k >> g.hsh), bc = mc * g.hs + (k & (g.hs - 1));
-        if ((br < g.bhY && bc < g.bwY) || k == 0) return cy[((long)br * g.bwY + bc) * 64];
-        real = false;
-    }
-}
-
-// codes scan block s of one image into `sink`; returns nothing - the sink counts
-template <bool EMIT>
-__device__ __forceinline__ void code_block(const int16_t* __restrict__ ci, const Geo& g, int s, BitSink<EMIT>& sink) {
-    const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.per - 2;
-    const int16_t* blk;
-    int dc, pred, t;
-    bool real = true;
-    if (k < ny) {
-        t = 0;
-        bool dummy_real;
-        dc = y_dc(ci, g, mr, mc, k, dummy_real);
-        real = dummy_real;
-        if (k > 0) pred = y_dc(ci, g, mr, mc, k - 1, dummy_real);
-        else if (m > 0) pred = y_dc(ci, g, (m - 1) / g.mx, (m - 1) % g.mx, ny - 1, dummy_real);
-        else pred = 0;
-        blk = ci + ((long)(mr * g.vs + (k >> g.hsh)) * g.bwY + mc * g.hs + (k & (g.hs - 1))) * 64;
-    } else {                       // the chroma grid is the MCU grid: block m, never a dummy
-        t = 1;
-        blk = ci + ((long)g.nbY + (long)(k - ny) * g.nbC + m) * 64;
-        dc = blk[0];
-        pred = m > 0 ? blk[-64] : 0;
-    }
-    // values beyond what baseline coding can carry are clamped, so a block never exceeds BLOCK_BITS_MAX bits
-    const int diff = min(max(dc - pred, -2047), 2047);
-    int sz = category(abs(diff));
-    uint32_t e = c_huff.dc[t][sz];
-    sink.put(((e >> 5) << sz) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << sz) - 1u)), (int)(e & 31u) + sz);
-    int run = 0;
-    if (real) {
-        const uint4* p = reinterpret_cast<const uint4*>(blk);
-        for (int c = 0; c < 8; ++c) {
-            const uint4 q = p[c];
-            const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (c == 0 && j == 0) continue;
-                int v = (int)(short)(wds[j >> 1] >> (16 * (j & 1)));
-                if (v == 0) { ++run; continue; }
-                v = min(max(v, -1023), 1023);
-                while (run >= 16) {
-                    e = c_huff.ac[t][0xf0];
-                    sink.put(e >> 5, (int)(e & 31u));
-                    run -= 16;
-                }
-                sz = category(abs(v));
-                e = c_huff.ac[t][(run << 4) | sz];
-                sink.put(((e >> 5) << sz) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << sz) - 1u)), (int)(e & 31u) + sz);
-                run = 0;
-            }
-        }
-    } else {
-        run = 63;
-    }
-    if (run > 0) {
-        e = c_huff.ac[t][0];
-        sink.put(e >> 5, (int)(e & 31u));
-    }
-}
-
-__global__ void __launch_bounds__(256) jpeg_bitlen_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, Geo g) {
+// one thread per scan-order block, dummy blocks included; the walk is jpegopt.h's, which clamps what baseline coding cannot carry, so
+// a block never exceeds BLOCK_BITS_MAX bits
+__global__ void __launch_bounds__(256) jpeg_bitlen_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ len, JpegGeo g) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)g.n * g.SB) return;
     const int img = (int)(t / g.SB), s = (int)(t - (long)img * g.SB);
-    BitSink<false> sink;
+    HuffSink<false> sink;
     sink.init(nullptr, 0, 0);
-    code_block<false>(coef + (long)img * g.NB * 64, g, s, sink);
+    jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
     len[t] = sink.count;
 }
 
@@ -236,13 +108,14 @@ __global__ void __launch_bounds__(256) jpeg_zero_kernel(uint32_t* __restrict__ r
 }
 
 __global__ void __launch_bounds__(256) jpeg_emit_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off,
-                                                        const uint32_t* __restrict__ total, uint32_t* __restrict__ raw, Geo g) {
+                                                        const uint32_t* __restrict__ total, uint32_t* __restrict__ raw, JpegGeo g,
+                                                        unsigned raw_words) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)g.n * g.SB) return;
     const int img = (int)(t / g.SB), s = (int)(t - (long)img * g.SB);
-    BitSink<true> sink;
-    sink.init(raw + (size_t)img * g.raw_words, g.raw_words, off[t]);
-    code_block<true>(coef + (long)img * g.NB * 64, g, s, sink);
+    HuffSink<true> sink;
+    sink.init(raw + (size_t)img * raw_words, raw_words, off[t]);
+    jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
     if (s == g.SB - 1) {                                 // the last byte is filled up with 1-bits
         const int pad = (int)((0u - total[img]) & 7u);
         if (pad) sink.put((1u << pad) - 1u, pad);
@@ -316,59 +189,27 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpeg_stuff_kernel(const uint32_t
 }
 
 // ---- reconstruct --------------------------------------------------------------------------------------------------------
-// one thread per real block: dequantise, inverse DCT (columns, then rows), + 128, clamp -> the component's sample plane
-__global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t* __restrict__ coef, uint8_t* __restrict__ planes, Geo g, QTabs qt) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long)g.n * g.NB) return;
-    int img, comp, br, bc;
-    locate(g, t, img, comp, br, bc);
-    const uint16_t* q = qt.q[comp ? 1 : 0];
-    const uint4* src = reinterpret_cast<const uint4*>(coef + t * 64);
-    uint32_t wds[32];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint4 v = src[j];
-        wds[4 * j] = v.x; wds[4 * j + 1] = v.y; wds[4 * j + 2] = v.z; wds[4 * j + 3] = v.w;
-    }
-    int d[64];
-#pragma unroll
-    for (int k = 0; k < 64; ++k) {
-        const int nat = c_nat_of_zz[k];
-        d[nat] = (int)(short)(wds[k >> 1] >> (16 * (k & 1))) * (int)q[nat];
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) idct8<8>(d + c, 11);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) idct8<1>(d + 8 * r, 18);
-    const int stride = 8 * (comp ? g.bwC : g.bwY);
-    uint8_t* p = plane_of(planes, g, img, comp) + (size_t)(8 * br) * stride + 8 * bc;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            lo |= (uint32_t)min(max(d[8 * r + c] + 128, 0), 255) << (8 * c);
-            hi |= (uint32_t)min(max(d[8 * r + 4 + c] + 128, 0), 255) << (8 * c);
-        }
-        *reinterpret_cast<uint2*>(p + (size_t)r * stride) = make_uint2(lo, hi);
-    }
-}
-
-// one thread per pixel
-__global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ planes, float* __restrict__ out, Geo g) {
+// one thread per pixel: clamp, then k / 255 in float32 or the byte itself
+template <bool U8>
+__global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ planes, void* __restrict__ out, JpegGeo g) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)g.n * g.h * g.w) return;
     const int img = (int)(t / ((long)g.h * g.w)), r = (int)(t - (long)img * g.h * g.w), y = r / g.w, x = r - y * g.w;
     const int yy = plane_of(planes, g, img, 0)[(size_t)y * 8 * g.bwY + x];
     const int cb = chroma_at(plane_of(planes, g, img, 1), g, y, x) - 128;
     const int cr = chroma_at(plane_of(planes, g, img, 2), g, y, x) - 128;
-    const int R = yy + ((91881 * cr + 32768) >> 16);
-    const int G = yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-    const int B = yy + ((116130 * cb + 32768) >> 16);
-    float* o = out + t * 3;
-    o[0] = __fdiv_rn((float)min(max(R, 0), 255), 255.0f);
-    o[1] = __fdiv_rn((float)min(max(G, 0), 255), 255.0f);
-    o[2] = __fdiv_rn((float)min(max(B, 0), 255), 255.0f);
+    const int R = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
+    const int G = min(max(yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16), 0), 255);
+    const int B = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
+    if (U8) {
+        uint8_t* o = (uint8_t*)out + t * 3;
+        o[0] = (uint8_t)R; o[1] = (uint8_t)G; o[2] = (uint8_t)B;
+    } else {
+        float* o = (float*)out + t * 3;
+        o[0] = __fdiv_rn((float)R, 255.0f);
+        o[1] = __fdiv_rn((float)G, 255.0f);
+        o[2] = __fdiv_rn((float)B, 255.0f);
+    }
 }
 
 }  // namespace
@@ -376,31 +217,28 @@ __global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ 
 extern "C" {
 
 size_t nimg_jpeg_workspace_bytes(int n, int h, int w, int hs, int vs) {
-    Geo g;
+    JpegGeo g;
     if (!make_geo(&g, n, h, w, hs, vs)) return 0;
     return carve(g, nullptr).bytes;
 }
 
 int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, int vs, int quality, int16_t* coef, void* workspace,
                         size_t workspace_bytes, void* stream) {
-    Geo g;
+    JpegGeo g;
     if (!x || !coef || !workspace || quality < 1 || quality > 100 || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     const long blocks = (long)n * g.NB;
     if (!grid_ok(blocks, 256)) return NIMG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const QTabs qt = make_qtabs(quality);
+    const BatchTables tabs{make_qtabs(quality)};
     const unsigned grid = (unsigned)((blocks + 255) / 256);
     if (is_u8) {
-        hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(grid), dim3(256), 0, st, x, coef, g, qt, (const uint32_t*)ws.flag);
+        hipLaunchKernelGGL((jpeg_transform_kernel<true, BatchTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, (const uint32_t*)ws.flag);
     } else {
-        const long count = (long)n * h * w * 3;
-        if (hipMemsetAsync(ws.flag, 0, 4, st) != hipSuccess) return NIMG_ERR_LAUNCH;
-        hipLaunchKernelGGL(jpeg_above_one_kernel, dim3((unsigned)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096)), dim3(256), 0, st, (const float*)x,
-                           count, ws.flag);
-        NIMG_CHECK_LAUNCH();
-        hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(grid), dim3(256), 0, st, x, coef, g, qt, (const uint32_t*)ws.flag);
+        const int rc = nimg_internal_jpeg_above_one((const float*)x, (long)n * h * w * 3, ws.flag, st);
+        if (rc != NIMG_OK) return rc;
+        hipLaunchKernelGGL((jpeg_transform_kernel<false, BatchTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, (const uint32_t*)ws.flag);
     }
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -408,7 +246,7 @@ int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, i
 
 int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, uint8_t* out, size_t out_capacity, uint32_t* lengths,
                      void* workspace, size_t workspace_bytes, void* stream) {
-    Geo g;
+    JpegGeo g;
     if (!coef || !out || !lengths || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
@@ -417,40 +255,27 @@ int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, u
     const unsigned grid = (unsigned)((blocks + 255) / 256);
     hipLaunchKernelGGL(jpeg_bitlen_kernel, dim3(grid), dim3(256), 0, st, coef, ws.off, g);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_bitscan_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, ws.off, ws.total, g.SB);
-    NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_zero_kernel, dim3((g.raw_words / 4 + 255) / 256, (unsigned)n), dim3(256), 0, st, ws.raw,
-                       (const uint32_t*)ws.total, g.raw_words);
-    NIMG_CHECK_LAUNCH();
+    const int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, n, g.SB, ws.raw_words, st);
+    if (rc != NIMG_OK) return rc;
     hipLaunchKernelGGL(jpeg_emit_kernel, dim3(grid), dim3(256), 0, st, coef, (const uint32_t*)ws.off, (const uint32_t*)ws.total, ws.raw,
-                       g);
+                       g, ws.raw_words);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, (const uint32_t*)ws.raw,
-                       (const uint32_t*)ws.total, lengths, g.raw_words);
-    NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_imgscan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, (const uint32_t*)lengths, ws.dst, n);
-    NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, (const uint32_t*)ws.raw,
-                       (const uint32_t*)ws.total, (const unsigned long long*)ws.dst, out, (unsigned long long)out_capacity, g.raw_words);
-    NIMG_CHECK_LAUNCH();
-    return NIMG_OK;
+    return nimg_internal_jpeg_pack(ws.raw, ws.total, lengths, ws.dst, out, out_capacity, n, ws.raw_words, st);
 }
 
 int nimg_jpeg_reconstruct(const int16_t* coef, int n, int h, int w, int hs, int vs, int quality, float* y, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    Geo g;
+    JpegGeo g;
     if (!coef || !y || !workspace || quality < 1 || quality > 100 || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     const long blocks = (long)n * g.NB, pixels = (long)n * h * w;
     if (!grid_ok(blocks, 256) || !grid_ok(pixels, 256)) return NIMG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g,
-                       make_qtabs(quality));
+    hipLaunchKernelGGL(jpeg_idct_kernel<BatchTables>, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g,
+                       BatchTables{make_qtabs(quality)});
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, ws.planes, y, g);
-    NIMG_CHECK_LAUNCH();
-    return NIMG_OK;
+    return nimg_internal_jpeg_colour(ws.planes, y, false, g, st);
 }
 
 }  // extern "C"
@@ -463,11 +288,12 @@ int nimg_internal_jpeg_above_one(const float* x, long count, uint32_t* flag, hip
     return NIMG_OK;
 }
 
-int nimg_internal_jpeg_colour(uint8_t* planes, float* y, int n, int h, int w, int hs, int vs, hipStream_t stream) {
-    Geo g;
-    const long pixels = (long)n * h * w;
-    if (!make_geo(&g, n, h, w, hs, vs) || !grid_ok(pixels, 256)) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, stream, planes, y, g);
+int nimg_internal_jpeg_colour(uint8_t* planes, void* y, bool u8, const JpegGeo& g, hipStream_t stream) {
+    const long pixels = (long)g.n * g.h * g.w;
+    if (!grid_ok(pixels, 256)) return NIMG_ERR_ARG;
+    const dim3 grid((unsigned)((pixels + 255) / 256));
+    if (u8) hipLaunchKernelGGL(jpeg_colour_kernel<true>, grid, dim3(256), 0, stream, planes, y, g);
+    else hipLaunchKernelGGL(jpeg_colour_kernel<false>, grid, dim3(256), 0, stream, planes, y, g);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }

@@ -8,18 +8,12 @@
 //   encode_tables   derive the code words of every image into the workspace | bit length of every block | jpegc.hip's scan and zero
 //                   passes | emit | jpegc.hip's count, image scan and stuff passes.  The bit-length and the emit kernel keep their
 //                   image's 544 code words in LDS, so a workgroup never spans two images.
-// The block walk, the length limiting and the derive step are csrc/jpegopt.h's, which tests/jpegopt_host.cpp runs on the host.  The bit
-// sink repeats jpegc.hip's few lines: moving them into jpegc.h would rebuild that unit's kernels around a shared function.
+// The block walk, the length limiting and the derive step are csrc/jpegopt.h's, which tests/jpegopt_host.cpp runs on the host; the bit
+// sink and the workspace layout are jpegc.h's, shared with jpegc.hip.
 #include "jpegc.h"
 #include "jpegopt.h"
 
 namespace {
-
-JpegoptGeo walk_geo(const Geo& g) {
-    JpegoptGeo o;
-    o.per = g.per; o.hs = g.hs; o.vs = g.vs; o.hsh = g.hsh; o.mx = g.mx; o.bhY = g.bhY; o.bwY = g.bwY; o.nbY = g.nbY; o.nbC = g.nbC;
-    return o;
-}
 
 // ---- histogram ----------------------------------------------------------------------------------------------------------
 struct HistSink {
@@ -28,15 +22,14 @@ struct HistSink {
 };
 
 // grid (ceil(SB / 256), n)
-__global__ void __launch_bounds__(256) jpeg_histogram_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, JpegoptGeo g,
-                                                             int SB, long image_coefs) {
+__global__ void __launch_bounds__(256) jpeg_histogram_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ hist, JpegGeo g) {
     __shared__ uint32_t s_hist[4 * JPEGOPT_HIST];
     for (int i = threadIdx.x; i < 4 * JPEGOPT_HIST; i += 256) s_hist[i] = 0;
     __syncthreads();
     const int img = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
-    if (s < SB) {
+    if (s < g.SB) {
         HistSink sink{s_hist};
-        jpegopt_walk_block(coef + (long)img * image_coefs, g, s, sink);
+        jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
     }
     __syncthreads();
     uint32_t* dst = hist + (size_t)img * 4 * JPEGOPT_HIST;
@@ -156,30 +149,6 @@ __global__ void __launch_bounds__(256) jpeg_optimal_tables_kernel(const uint32_t
 }
 
 // ---- entropy coding with the tables of each image ----------------------------------------------------------------------------
-struct TabWorkspace {
-    uint32_t* codes;                   // [n][544] symbol -> code << 5 | length
-    uint32_t* off;                     // [n][SB] bit lengths, then (in place) bit offsets
-    uint32_t* total;                   // [n] bits of an image before the final padding
-    unsigned long long* dst;           // [n] first byte of an image's segment in the output
-    uint32_t* raw;                     // [n][raw_words] the un-stuffed bits, MSB first in every word
-    unsigned raw_words;                // sized for JPEGOPT_BLOCK_BITS_MAX bits a block, a multiple of 4
-    size_t bytes;
-};
-
-TabWorkspace carve_tables(const Geo& g, void* base) {
-    TabWorkspace ws;
-    uint8_t* p = (uint8_t*)base;
-    const unsigned long words = ((unsigned long)g.SB * JPEGOPT_BLOCK_BITS_MAX + 31) / 32 + 1;
-    ws.raw_words = (unsigned)((words + 3) & ~3ul);
-    ws.codes = (uint32_t*)p; p += align256((size_t)g.n * JPEGOPT_CODE_WORDS * 4);
-    ws.off = (uint32_t*)p; p += align256((size_t)g.n * g.SB * 4);
-    ws.total = (uint32_t*)p; p += align256((size_t)g.n * 4);
-    ws.dst = (unsigned long long*)p; p += align256((size_t)g.n * 8);
-    ws.raw = (uint32_t*)p; p += align256((size_t)g.n * ws.raw_words * 4);
-    ws.bytes = (size_t)(p - (uint8_t*)base);
-    return ws;
-}
-
 // one thread per image: status[image] = JPEGOPT_ST_TABLE or 0 (the call's only plain store to it; the bit-length pass ORs into it)
 __global__ void __launch_bounds__(64) jpeg_derive_kernel(const uint8_t* __restrict__ tables, uint32_t* __restrict__ codes,
                                                          uint32_t* __restrict__ status, int n) {
@@ -189,42 +158,15 @@ __global__ void __launch_bounds__(64) jpeg_derive_kernel(const uint8_t* __restri
     status[img] = ok ? 0u : JPEGOPT_ST_TABLE;
 }
 
-// the bit sink of jpegc.hip (see there) behind the code words of one image; a symbol without a code puts nothing and sets `missing`
+// jpegc.h's bit sink behind the code words of one image; a symbol without a code puts nothing and sets `missing`
 template <bool EMIT>
-struct CodeSink {
+struct CodeSink : BitSink<EMIT> {
     const uint32_t* codes;             // LDS
-    uint32_t* base;
-    unsigned widx, cap, count;
-    unsigned long long acc;
-    int nacc;
-    bool first, missing;
-    __device__ __forceinline__ void init(const uint32_t* c, uint32_t* b, unsigned cap_words, unsigned bit0) {
-        codes = c; base = b; cap = cap_words; widx = bit0 >> 5; nacc = (int)(bit0 & 31u); acc = 0; first = true; count = 0; missing = false;
-    }
-    __device__ __forceinline__ void put(uint32_t v, int len) {          // len <= 27, v < 2^len
-        count += (unsigned)len;
-        if (!EMIT) return;
-        acc = (acc << len) | v;
-        nacc += len;
-        if (nacc >= 32) {
-            const uint32_t word = (uint32_t)(acc >> (nacc - 32));
-            if (widx < cap) {
-                if (first) atomicOr(base + widx, word);
-                else base[widx] = word;
-            }
-            first = false;
-            ++widx;
-            nacc -= 32;
-            acc &= (1ull << nacc) - 1ull;
-        }
-    }
-    __device__ __forceinline__ void finish() {
-        if (EMIT && nacc > 0 && widx < cap) atomicOr(base + widx, (uint32_t)(acc << (32 - nacc)));
-    }
+    bool missing = false;
     __device__ __forceinline__ void symbol(int table, int sym, uint32_t value, int nbits) {
         const uint32_t e = codes[jpegopt_code_index(table, sym)];
         if (e == 0) { missing = true; return; }
-        put(((e >> 5) << nbits) | value, (int)(e & 31u) + nbits);
+        this->put(((e >> 5) << nbits) | value, (int)(e & 31u) + nbits);
     }
 };
 
@@ -235,32 +177,33 @@ __device__ __forceinline__ void load_codes(uint32_t* s_codes, const uint32_t* __
 
 // grid (ceil(SB / 256), n).  An image whose tables were refused gets length 0 for every block.
 __global__ void __launch_bounds__(256) jpeg_bitlen_tables_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ codes,
-                                                                 uint32_t* __restrict__ len, uint32_t* __restrict__ status, JpegoptGeo g,
-                                                                 int SB, long image_coefs) {
+                                                                 uint32_t* __restrict__ len, uint32_t* __restrict__ status, JpegGeo g) {
     __shared__ uint32_t s_codes[JPEGOPT_CODE_WORDS];
     const int img = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
     load_codes(s_codes, codes, img);
-    if (s >= SB) return;
+    if (s >= g.SB) return;
     CodeSink<false> sink;
-    sink.init(s_codes, nullptr, 0, 0);
+    sink.codes = s_codes;
+    sink.init(nullptr, 0, 0);
     const bool refused = (status[img] & JPEGOPT_ST_TABLE) != 0;          // written by the derive pass, before this kernel began
-    if (!refused) jpegopt_walk_block(coef + (long)img * image_coefs, g, s, sink);
-    len[(size_t)img * SB + s] = sink.count;
+    if (!refused) jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
+    len[(size_t)img * g.SB + s] = sink.count;
     if (sink.missing) atomicOr(status + img, JPEGOPT_ST_SYMBOL);
 }
 
 __global__ void __launch_bounds__(256) jpeg_emit_tables_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ codes,
                                                                const uint32_t* __restrict__ off, const uint32_t* __restrict__ total,
                                                                const uint32_t* __restrict__ status, uint32_t* __restrict__ raw,
-                                                               JpegoptGeo g, int SB, long image_coefs, unsigned raw_words) {
+                                                               JpegGeo g, unsigned raw_words) {
     __shared__ uint32_t s_codes[JPEGOPT_CODE_WORDS];
     const int img = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
     load_codes(s_codes, codes, img);
-    if (s >= SB || (status[img] & JPEGOPT_ST_TABLE) != 0) return;
+    if (s >= g.SB || (status[img] & JPEGOPT_ST_TABLE) != 0) return;
     CodeSink<true> sink;
-    sink.init(s_codes, raw + (size_t)img * raw_words, raw_words, off[(size_t)img * SB + s]);
-    jpegopt_walk_block(coef + (long)img * image_coefs, g, s, sink);
-    if (s == SB - 1) {                                   // the last byte is filled up with 1-bits
+    sink.codes = s_codes;
+    sink.init(raw + (size_t)img * raw_words, raw_words, off[(size_t)img * g.SB + s]);
+    jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
+    if (s == g.SB - 1) {                                   // the last byte is filled up with 1-bits
         const int pad = (int)((0u - total[img]) & 7u);
         if (pad) sink.put((1u << pad) - 1u, pad);
     }
@@ -272,12 +215,11 @@ __global__ void __launch_bounds__(256) jpeg_emit_tables_kernel(const int16_t* __
 extern "C" {
 
 int nimg_jpeg_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, uint32_t* hist, void* stream) {
-    Geo g;
+    JpegGeo g;
     if (!coef || !hist || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(hist, 0, (size_t)n * 4 * JPEGOPT_HIST * 4, st) != hipSuccess) return NIMG_ERR_LAUNCH;
-    hipLaunchKernelGGL(jpeg_histogram_kernel, dim3((unsigned)((g.SB + 255) / 256), (unsigned)n), dim3(256), 0, st, coef, hist, walk_geo(g),
-                       g.SB, (long)g.NB * 64);
+    hipLaunchKernelGGL(jpeg_histogram_kernel, dim3((unsigned)((g.SB + 255) / 256), (unsigned)n), dim3(256), 0, st, coef, hist, g);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -291,31 +233,28 @@ int nimg_jpeg_optimal_tables(const uint32_t* hist, int n_tables, uint8_t* tables
 }
 
 size_t nimg_jpeg_encode_tables_workspace_bytes(int n, int h, int w, int hs, int vs) {
-    Geo g;
+    JpegGeo g;
     if (!make_geo(&g, n, h, w, hs, vs)) return 0;
-    return carve_tables(g, nullptr).bytes;
+    return carve(g, nullptr, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS).bytes;
 }
 
 int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint8_t* tables, uint8_t* out,
                             size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
                             void* stream) {
-    Geo g;
+    JpegGeo g;
     if (!coef || !tables || !out || !lengths || !status || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
-    const TabWorkspace ws = carve_tables(g, workspace);
+    const Workspace ws = carve(g, workspace, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const JpegoptGeo wg = walk_geo(g);
     const dim3 grid((unsigned)((g.SB + 255) / 256), (unsigned)n);
-    const long image_coefs = (long)g.NB * 64;
     hipLaunchKernelGGL(jpeg_derive_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, tables, ws.codes, status, n);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_bitlen_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, ws.off, status, wg, g.SB,
-                       image_coefs);
+    hipLaunchKernelGGL(jpeg_bitlen_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, ws.off, status, g);
     NIMG_CHECK_LAUNCH();
     int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, n, g.SB, ws.raw_words, st);
     if (rc != NIMG_OK) return rc;
     hipLaunchKernelGGL(jpeg_emit_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, (const uint32_t*)ws.off,
-                       (const uint32_t*)ws.total, (const uint32_t*)status, ws.raw, wg, g.SB, image_coefs, ws.raw_words);
+                       (const uint32_t*)ws.total, (const uint32_t*)status, ws.raw, g, ws.raw_words);
     NIMG_CHECK_LAUNCH();
     return nimg_internal_jpeg_pack(ws.raw, ws.total, lengths, ws.dst, out, out_capacity, n, ws.raw_words, st);
 }

@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "jpeg_geo.h"
+
 #if defined(__HIPCC__)
 #define JPEGD_HD __host__ __device__
 #else
@@ -33,15 +35,6 @@ struct JpegdTable {
     int32_t valoff[17];           // [l]: index of the first symbol of length l minus its code
     uint16_t look[256];           // the next 8 bits -> length << 8 | symbol of a code of up to 8 bits, 0 for a longer one
     uint8_t sym[256];
-};
-
-// what the core needs of the geometry (csrc/jpegc.h Geo has the same numbers)
-struct JpegdGeo {
-    int per, hs, vs, hsh;         // blocks per MCU = hs * vs + 2; hsh = log2(hs)
-    int mx;                       // MCUs per row
-    int bhY, bwY, bwC;            // real extent in blocks
-    int nbY, nbC;                 // real blocks of Y / of one chroma component
-    int SB;                       // blocks per image in scan order, dummies included
 };
 
 // between two symbols: p = bit position in the un-stuffed stream (JPEGD_INVALID after an invalid symbol), mz = m << 8 | z with
@@ -101,7 +94,7 @@ JPEGD_HD inline int jpegd_symbol(const JpegdTable& t, uint32_t window, int& len)
 
 // scan-order block b -> the offset (in blocks) of its coefficients in the image's [Y | Cb | Cr][row][col] tensor, -1 for a dummy
 // block; comp = its component
-JPEGD_HD inline long jpegd_place(const JpegdGeo& g, uint32_t b, int& comp) {
+JPEGD_HD inline long jpegd_place(const JpegGeo& g, uint32_t b, int& comp) {
     const int mcu = (int)(b / (uint32_t)g.per), k = (int)(b - (uint32_t)mcu * (uint32_t)g.per), ny = g.per - 2;
     if (k >= ny) {                                     // the chroma grid is the MCU grid
         comp = k - ny + 1;
@@ -121,7 +114,7 @@ JPEGD_HD inline long jpegd_place(const JpegdGeo& g, uint32_t b, int& comp) {
 // block SB - 1, and nothing at or beyond SB is stored.  Not WRITE: coef, dcdiff and status are not touched.
 template <bool WRITE>
 JPEGD_HD inline void jpegd_run(const uint32_t* bits, uint32_t nwords, uint32_t total_bits, uint32_t limit, const JpegdTable* tabs,
-                               const JpegdGeo& g, JpegdState& s, uint32_t& begun, uint32_t block, int16_t* coef, int32_t* dcdiff,
+                               const JpegGeo& g, JpegdState& s, uint32_t& begun, uint32_t block, int16_t* coef, int32_t* dcdiff,
                                uint32_t& status) {
     begun = 0;
     uint32_t p = s.p;

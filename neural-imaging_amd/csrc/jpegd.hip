@@ -36,7 +36,7 @@ struct DLayout {
     size_t raw_words, slots, bytes;
 };
 
-DLayout carve_d(const Geo& g, uint64_t ecd_bytes, uint32_t sb, void* base) {
+DLayout carve_d(const JpegGeo& g, uint64_t ecd_bytes, uint32_t sb, void* base) {
     DLayout d;
     uint8_t* p = (uint8_t*)base;
     d.total_bits = (uint32_t*)p; p += align256((size_t)g.n * 4);
@@ -58,21 +58,13 @@ bool subseq_ok(int subseq_bits, uint32_t* sb) {
     return true;
 }
 
-JpegdGeo core_geo(const Geo& g) {
-    JpegdGeo c;
-    c.per = g.per; c.hs = g.hs; c.vs = g.vs; c.hsh = g.hsh; c.mx = g.mx; c.bhY = g.bhY; c.bwY = g.bwY; c.bwC = g.bwC;
-    c.nbY = g.nbY; c.nbC = g.nbC; c.SB = g.SB;
-    return c;
-}
-
 struct DArgs {
     const uint8_t* ecd;
     const uint64_t* off;
     const uint8_t* huffman;
     uint64_t ecd_cap;            // the segment bytes the workspace was sized for
     uint32_t sb;
-    int n, NB;
-    JpegdGeo g;
+    JpegGeo g;
     int16_t* coef;
     uint32_t* status;
     uint32_t* rounds;
@@ -162,7 +154,7 @@ __global__ void __launch_bounds__(DEC_THREADS) jpegd_decode_kernel(DArgs a, DLay
         const uint32_t limit = min((i + 1u) * a.sb, total);
         uint32_t begun;
         jpegd_run<WRITE>(bits, nwords, total, limit, tabs, a.g, s, begun, WRITE ? cnt[i] : 0u,
-                         a.coef + (size_t)img * a.NB * 64, d.dcdiff + (size_t)img * a.g.SB, status);
+                         a.coef + (size_t)img * a.g.NB * 64, d.dcdiff + (size_t)img * a.g.SB, status);
         if (!WRITE) { ex[i] = s; cnt[i] = begun; }
     }
     if (WRITE && status) atomicOr(a.status + img, status);
@@ -229,7 +221,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout
     if (d.nsub[img] == 0) return;
     const int ny = a.g.per - 2, mcus = a.g.SB / a.g.per, count = comp ? mcus : mcus * ny;
     const int32_t* diff = d.dcdiff + (size_t)img * a.g.SB;
-    int16_t* coef = a.coef + (size_t)img * a.NB * 64;
+    int16_t* coef = a.coef + (size_t)img * a.g.NB * 64;
     int carry = 0;
     bool bad = false;
     for (int base = 0; base < count; base += SCAN_THREADS) {
@@ -250,74 +242,18 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout
 }
 
 // ---- reconstruct with the tables of each image ----------------------------------------------------------------------------------
-// one thread per real block (jpeg_idct_kernel with the table of (image, component) read from memory)
-__global__ void __launch_bounds__(256) jpegd_idct_tables_kernel(const int16_t* __restrict__ coef, uint8_t* __restrict__ planes, Geo g,
-                                                                const uint16_t* __restrict__ qtabs) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long)g.n * g.NB) return;
-    int img, comp, br, bc;
-    locate(g, t, img, comp, br, bc);
-    const uint16_t* q = qtabs + ((size_t)img * 3 + comp) * 64;
-    const uint4* src = reinterpret_cast<const uint4*>(coef + t * 64);
-    uint32_t wds[32];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint4 v = src[j];
-        wds[4 * j] = v.x; wds[4 * j + 1] = v.y; wds[4 * j + 2] = v.z; wds[4 * j + 3] = v.w;
-    }
-    int d[64];
-#pragma unroll
-    for (int k = 0; k < 64; ++k) {
-        const int nat = c_nat_of_zz[k];
-        d[nat] = (int)(short)(wds[k >> 1] >> (16 * (k & 1))) * (int)q[nat];
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) idct8<8>(d + c, 11);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) idct8<1>(d + 8 * r, 18);
-    const int stride = 8 * (comp ? g.bwC : g.bwY);
-    uint8_t* p = plane_of(planes, g, img, comp) + (size_t)(8 * br) * stride + 8 * bc;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            lo |= (uint32_t)min(max(d[8 * r + c] + 128, 0), 255) << (8 * c);
-            hi |= (uint32_t)min(max(d[8 * r + 4 + c] + 128, 0), 255) << (8 * c);
-        }
-        *reinterpret_cast<uint2*>(p + (size_t)r * stride) = make_uint2(lo, hi);
-    }
-}
-
-// one thread per pixel (jpeg_colour_kernel, which can also leave the bytes as they are)
-template <bool U8>
-__global__ void __launch_bounds__(256) jpegd_colour_kernel(uint8_t* __restrict__ planes, void* __restrict__ out, Geo g) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long)g.n * g.h * g.w) return;
-    const int img = (int)(t / ((long)g.h * g.w)), r = (int)(t - (long)img * g.h * g.w), y = r / g.w, x = r - y * g.w;
-    const int yy = plane_of(planes, g, img, 0)[(size_t)y * 8 * g.bwY + x];
-    const int cb = chroma_at(plane_of(planes, g, img, 1), g, y, x) - 128;
-    const int cr = chroma_at(plane_of(planes, g, img, 2), g, y, x) - 128;
-    const int R = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
-    const int G = min(max(yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16), 0), 255);
-    const int B = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
-    if (U8) {
-        uint8_t* o = (uint8_t*)out + t * 3;
-        o[0] = (uint8_t)R; o[1] = (uint8_t)G; o[2] = (uint8_t)B;
-    } else {
-        float* o = (float*)out + t * 3;
-        o[0] = __fdiv_rn((float)R, 255.0f);
-        o[1] = __fdiv_rn((float)G, 255.0f);
-        o[2] = __fdiv_rn((float)B, 255.0f);
-    }
-}
+// jpegc.h's table source for the tables of each file: qtabs[image][component][64], natural order, in global memory
+struct FileTables {
+    const uint16_t* qtabs;
+    __device__ __forceinline__ const uint16_t* table(const JpegGeo&, long, int img, int comp) const { return qtabs + ((size_t)img * 3 + comp) * 64; }
+};
 
 }  // namespace
 
 extern "C" {
 
 size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, size_t ecd_bytes, int subseq_bits) {
-    Geo g;
+    JpegGeo g;
     uint32_t sb;
     if (!make_geo(&g, n, h, w, hs, vs) || !subseq_ok(subseq_bits, &sb) || ecd_bytes > (size_t)n * ECD_MAX) return 0;
     return carve_d(g, ecd_bytes, sb, nullptr).bytes;
@@ -326,7 +262,7 @@ size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, siz
 int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
                      int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
                      void* stream) {
-    Geo g;
+    JpegGeo g;
     uint32_t sb;
     if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs) || !subseq_ok(subseq_bits, &sb))
         return NIMG_ERR_ARG;
@@ -340,7 +276,7 @@ int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t*
     }
     const DLayout d = carve_d(g, lo, sb, workspace);
     DArgs a;
-    a.ecd = ecd; a.off = ecd_off; a.huffman = huffman; a.ecd_cap = lo; a.sb = sb; a.n = n; a.NB = g.NB; a.g = core_geo(g);
+    a.ecd = ecd; a.off = ecd_off; a.huffman = huffman; a.ecd_cap = lo; a.sb = sb; a.g = g;
     a.coef = coef; a.status = status; a.rounds = rounds;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(status, 0, (size_t)n * 4, st) != hipSuccess || hipMemsetAsync(coef, 0, (size_t)n * g.NB * 128, st) != hipSuccess ||
@@ -364,19 +300,17 @@ int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t*
 
 int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    Geo g;
+    JpegGeo g;
     if (!coef || !y || !qtabs || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     const long blocks = (long)n * g.NB, pixels = (long)n * h * w;
     if (!grid_ok(blocks, 256) || !grid_ok(pixels, 256)) return NIMG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(jpegd_idct_tables_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g, qtabs);
+    hipLaunchKernelGGL(jpeg_idct_kernel<FileTables>, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g,
+                       FileTables{qtabs});
     NIMG_CHECK_LAUNCH();
-    if (out_u8) hipLaunchKernelGGL(jpegd_colour_kernel<true>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, ws.planes, y, g);
-    else hipLaunchKernelGGL(jpegd_colour_kernel<false>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, ws.planes, y, g);
-    NIMG_CHECK_LAUNCH();
-    return NIMG_OK;
+    return nimg_internal_jpeg_colour(ws.planes, y, out_u8 != 0, g, st);
 }
 
 }  // extern "C"

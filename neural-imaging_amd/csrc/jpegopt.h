@@ -1,11 +1,14 @@
-// The sequential core of writing JPEG files with optimised Huffman tables: the symbols of one scan-order block,
-// libjpeg's jpeg_gen_optimal_table over a 257-entry histogram, and the step from a table as a DHT segment has it to the code words the
-// coder looks up.  jpegc_opt.hip runs the block walk one thread per block and the length limiting and the derive step one thread per
-// table; the merging it does a wave per table, and jpegopt_optimal_table below is that merging in its sequential form.  Everything here
+// The sequential core of the JPEG entropy coders (DESIGN.md sections 4c and 4f): the symbols of one scan-order block - the one block
+// walk of the baseline coder (jpegc.hip), the histogram and the coder with the caller's tables (jpegc_opt.hip) -, libjpeg's
+// jpeg_gen_optimal_table over a 257-entry histogram, and the step from a table as a DHT segment has it to the code words the coder
+// looks up.  The kernels run the block walk one thread per block and the length limiting and the derive step one thread per
+// table; the merging jpegc_opt.hip does a wave per table, and jpegopt_optimal_table below is that merging in its sequential form.  Everything here
 // is `__host__ __device__` under hipcc and plain C++ otherwise, so that a host compiler can build it into a stand-alone program
 // (tests/jpegopt_host.cpp) and hold it to sanitizers.
 #pragma once
 #include <stdint.h>
+
+#include "jpeg_geo.h"
 
 #if defined(__HIPCC__)
 #define JPEGOPT_HD __host__ __device__
@@ -25,21 +28,13 @@
 #define JPEGOPT_ST_TABLE 1u              // counts that are no prefix code of lengths 1..16 with at most 256 symbols
 #define JPEGOPT_ST_SYMBOL 2u             // a symbol that occurs in the image has no code
 
-// what the block walk needs of the geometry (csrc/jpegc.h Geo has the same numbers)
-struct JpegoptGeo {
-    int per, hs, vs, hsh;         // blocks per MCU = hs * vs + 2; hsh = log2(hs)
-    int mx;                       // MCUs per row
-    int bhY, bwY;                 // real extent of Y in blocks
-    int nbY, nbC;                 // real blocks of Y / of one chroma component
-};
-
 JPEGOPT_HD inline int jpegopt_category(int a) {        // of |value|; 0 for 0
     return a ? 32 - __builtin_clz((unsigned)a) : 0;
 }
 
 // the DC of Y block k of MCU (mr, mc) as it is coded: a dummy block (beyond the real extent, to the right or below) carries the DC of
 // the block before it in the MCU; block 0 of an MCU is always real
-JPEGOPT_HD inline int jpegopt_y_dc(const int16_t* cy, const JpegoptGeo& g, int mr, int mc, int k, bool& real) {
+JPEGOPT_HD inline int jpegopt_y_dc(const int16_t* cy, const JpegGeo& g, int mr, int mc, int k, bool& real) {
     real = true;
     for (;; --k) {
         const int br = mr * g.vs + (k >> g.hsh), bc = mc * g.hs + (k & (g.hs - 1));
@@ -52,7 +47,7 @@ JPEGOPT_HD inline int jpegopt_y_dc(const int16_t* cy, const JpegoptGeo& g, int m
 // difference +-2047, AC +-1023): sink.symbol(table, symbol, value bits, their number) with table = 0 Y DC, 1 Y AC, 2 chroma DC,
 // 3 chroma AC - the DHT-id order 00 10 01 11.  A dummy block is its DC difference and one end-of-block.
 template <typename Sink>
-JPEGOPT_HD inline void jpegopt_walk_block(const int16_t* ci, const JpegoptGeo& g, int s, Sink& sink) {
+JPEGOPT_HD inline void jpegopt_walk_block(const int16_t* ci, const JpegGeo& g, int s, Sink& sink) {
     const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.per - 2;
     const int16_t* blk;
     int dc, pred, t;
@@ -73,23 +68,23 @@ JPEGOPT_HD inline void jpegopt_walk_block(const int16_t* ci, const JpegoptGeo& g
     }
     int diff = dc - pred;
     diff = diff < -2047 ? -2047 : (diff > 2047 ? 2047 : diff);
-    int sz = jpegopt_category(diff < 0 ? -diff : diff);
+    int sz = jpegopt_category(__builtin_abs(diff));
     sink.symbol(t, sz, (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << sz) - 1u), sz);
     int run = 0;
     if (real) {
         for (int c = 0; c < 8; ++c) {
-            int16_t row[8];
+            uint32_t row[4];                           // eight coefficients, the even one in the low half (little endian)
             __builtin_memcpy(row, __builtin_assume_aligned(blk + 8 * c, 16), 16);
             for (int j = 0; j < 8; ++j) {
                 if (c == 0 && j == 0) continue;
-                int v = row[j];
+                int v = (int16_t)(row[j >> 1] >> (16 * (j & 1)));
                 if (v == 0) { ++run; continue; }
                 v = v < -1023 ? -1023 : (v > 1023 ? 1023 : v);
                 while (run >= 16) {
                     sink.symbol(t + 1, 0xf0, 0u, 0);
                     run -= 16;
                 }
-                sz = jpegopt_category(v < 0 ? -v : v);
+                sz = jpegopt_category(__builtin_abs(v));
                 sink.symbol(t + 1, (run << 4) | sz, (uint32_t)(v < 0 ? v - 1 : v) & ((1u << sz) - 1u), sz);
                 run = 0;
             }

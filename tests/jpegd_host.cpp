@@ -11,26 +11,12 @@
 
 #include "jpegd.h"
 
-static JpegdGeo make_geo(int h, int w, int hs, int vs, int* NB) {
-    JpegdGeo g;
-    g.hs = hs; g.vs = vs; g.hsh = hs - 1; g.per = hs * vs + 2;
-    g.bhY = (h + 7) / 8; g.bwY = (w + 7) / 8;
-    const int ceh = (h + vs - 1) / vs, cew = (w + hs - 1) / hs, bhC = (ceh + 7) / 8;
-    g.bwC = (cew + 7) / 8;
-    const int my = (h + 8 * vs - 1) / (8 * vs);
-    g.mx = (w + 8 * hs - 1) / (8 * hs);
-    g.nbY = g.bhY * g.bwY; g.nbC = bhC * g.bwC;
-    g.SB = my * g.mx * g.per;
-    *NB = g.nbY + 2 * g.nbC;
-    return g;
-}
-
 struct Result {
     uint32_t status, rounds, subsequences;
     std::vector<int16_t> coef;
 };
 
-static Result decode(const JpegdGeo& g, int NB, const uint8_t* huffman, const uint8_t* ecd, uint32_t len, uint32_t sb) {
+static Result decode(const JpegGeo& g, const uint8_t* huffman, const uint8_t* ecd, uint32_t len, uint32_t sb) {
     Result r;
     r.status = 0;
     JpegdTable tabs[6];
@@ -83,7 +69,7 @@ static Result decode(const JpegdGeo& g, int NB, const uint8_t* huffman, const ui
     }
     if (blocks < (uint32_t)g.SB) r.status |= JPEGD_ST_BLOCKS;
     // 5. write: buffers of exactly the size the device gives them
-    r.coef.assign((size_t)NB * 64, 0);
+    r.coef.assign((size_t)g.NB * 64, 0);
     std::vector<int32_t> dcdiff(g.SB, 0);
     for (uint32_t i = 0; i < S; ++i) {
         JpegdState s = {0, 0};
@@ -121,10 +107,10 @@ int main(int argc, char** argv) {
             return 2;
         std::vector<uint8_t> ecd(len);                 // exactly len bytes: a read past the segment is a sanitizer finding
         if (len && fread(ecd.data(), 1, len, in) != len) return 2;
-        int NB;
-        const JpegdGeo g = make_geo(head[0], head[1], head[2], head[3], &NB);
+        JpegGeo g;
+        if (!make_geo(&g, 1, head[0], head[1], head[2], head[3])) return 2;
         for (int a = 3; a < argc; ++a) {
-            const Result r = decode(g, NB, huffman.data(), ecd.data(), len, (uint32_t)strtoul(argv[a], nullptr, 10));
+            const Result r = decode(g, huffman.data(), ecd.data(), len, (uint32_t)strtoul(argv[a], nullptr, 10));
             const uint32_t rec[4] = {r.status, r.rounds, r.subsequences, (uint32_t)r.coef.size()};
             fwrite(rec, 4, 4, out);
             fwrite(r.coef.data(), 2, r.coef.size(), out);

@@ -70,19 +70,14 @@ int main(int argc, char** argv) {
         in.take(dims, 16);
         const int h = dims[0], w = dims[1], hs = dims[2], vs = dims[3];
         const uint32_t count = in.u32();
-        JpegoptGeo g;
-        g.per = hs * vs + 2; g.hs = hs; g.vs = vs; g.hsh = hs - 1;
-        g.mx = (w + 8 * hs - 1) / (8 * hs);
-        g.bhY = (h + 7) / 8; g.bwY = (w + 7) / 8;
-        g.nbY = g.bhY * g.bwY;
-        g.nbC = (((h + vs - 1) / vs + 7) / 8) * (((w + hs - 1) / hs + 7) / 8);
-        const int my = (h + 8 * vs - 1) / (8 * vs), SB = my * g.mx * g.per;
-        if (count != (uint32_t)(g.nbY + 2 * g.nbC) * 64u) { std::fprintf(stderr, "image %u: %u coefficients\n", k, count); return 2; }
+        JpegGeo g;
+        if (!make_geo(&g, 1, h, w, hs, vs)) { std::fprintf(stderr, "image %u: no geometry\n", k); return 2; }
+        if (count != (uint32_t)g.NB * 64u) { std::fprintf(stderr, "image %u: %u coefficients\n", k, count); return 2; }
         std::vector<int16_t> coef(count);
         in.take(coef.data(), 2 * (size_t)count);
         std::vector<uint32_t> hist(4 * JPEGOPT_HIST, 0u);
         HistSink sink{hist.data()};
-        for (int s = 0; s < SB; ++s) jpegopt_walk_block(coef.data(), g, s, sink);
+        for (int s = 0; s < g.SB; ++s) jpegopt_walk_block(coef.data(), g, s, sink);
         std::vector<uint8_t> tabs(4 * JPEGOPT_TABLE_BYTES);
         uint32_t st[5];
         for (int t = 0; t < 4; ++t) st[t] = jpegopt_optimal_table(hist.data() + t * JPEGOPT_HIST, tabs.data() + t * JPEGOPT_TABLE_BYTES);
