@@ -56,7 +56,8 @@ extern "C" {
  * gained out_bf16_copy and stride; 5: the arg-max of nimg_conv1_pool_fwd_c4 / nimg_conv1_wgrad_c4 / nimg_conv1_dgrad_pooled is 2 bits
  * per value; 6: the nimg_l3ic_* bitstream entry points; 7: the nimg_jpeg_* baseline codec entry points; 8: the per-item
  * nimg_jpeg_*_items forms and nimg_msssim; version 8 also carries the later, purely added nimg_jpeg_decode* and
- * nimg_jpeg_reconstruct_tables entry points and the nimg_jpeg_histogram / _optimal_tables / _encode_tables ones).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
+ * nimg_jpeg_reconstruct_tables entry points, the nimg_jpeg_histogram / _optimal_tables / _encode_tables ones and
+ * nimg_jpeg_transform_tables / nimg_jpeg_tables_from_float).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
  * written against. */
 #define NIMG_ABI_VERSION 8
 int nimg_abi_version(void);
@@ -778,6 +779,22 @@ size_t nimg_jpeg_encode_tables_workspace_bytes(int n, int h, int w, int hs, int 
 int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint8_t* tables, uint8_t* out,
                             size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
                             void* stream);
+
+/* Writing files with any quantisation tables: the tables are an input of the transform instead of a quality.
+ *   transform_tables   nimg_jpeg_transform_items with qtabs (device) [n_items][3][64] uint16 in natural order - the layout of
+ *                      nimg_jpeg_reconstruct_tables - in place of the qualities: item j = source image j % n_src of x (n_src,h,w,3)
+ *                      divided by its own three tables (Y, Cb, Cr).  One table set for a batch is n_items = n_src, K sets over N
+ *                      images n_items = K * N.  An entry outside 1..255 is clamped to that range - no thread divides by zero - and
+ *                      *err (device, zeroed by the caller) |= 1.  The "any value above 1" flag of float input is one per call, over
+ *                      the n_src source images.  Workspace: nimg_jpeg_workspace_bytes(n_items, ...).  nimg_jpeg_encode,
+ *                      nimg_jpeg_encode_tables and nimg_jpeg_reconstruct_tables serve the result as they are.
+ *   tables_from_float  t (device) float32 [n_sets][n_tabs][64], natural order, n_tabs 2 (luma, chroma) or 3 (Y, Cb, Cr) -> qtabs
+ *                      (device) uint16 [n_sets][3][64]; with two tables component 2 takes table 1.  An entry becomes rintf(v) (ties
+ *                      to even) clamped to 1..255.  status (device) [n_sets], written: bits 1 = an entry was raised to 1 | 2 = an
+ *                      entry was lowered to 255 | 4 = a non-finite entry (NaN and -inf become 1, +inf 255).  n_sets <= 65535. */
+int nimg_jpeg_transform_tables(const void* x, int is_u8, int n_src, int h, int w, int hs, int vs, const uint16_t* qtabs, int n_items,
+                               int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream);
+int nimg_jpeg_tables_from_float(const float* t, int n_sets, int n_tabs, uint16_t* qtabs, uint32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,10 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
                                                         decoder of DESIGN.md section 4e (nimg_jpeg_decode, nimg_jpeg_reconstruct_tables)
   rate_distortion, match_quality_batch                  new: a whole quality sweep / the bisection of every image of a batch through
                                                         the item kernels (one quality per item)
+  qtables= (jpeg_header, device_codec, encode_batch,    new: files with any 8-bit quantisation tables in place of a quality - learned
+  compress_batch), check_qtables,                       ones, the differentiable codec's, a foreign file's (DESIGN.md section 4h);
+  rate_distortion_tables, transcode_batch               K table sets over a batch in one item call; a file written again with its
+                                                        coefficients and tables untouched and optimal (or Annex K) Huffman tables
   JPEGMarkerStats (:133-250)                            host parsing of a file's segments
 
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
@@ -27,8 +31,9 @@ import torch
 from .. import ops
 from ..device import default_device, unwrap
 
-JPEG_HEADER_BYTES = 623           # SOI .. SOS of every file written here
+JPEG_HEADER_BYTES = 623           # SOI .. SOS of every file written here with two quantisation tables
 _DHT_OFFSET = 177
+_DQT_BYTES = 69                   # a third quantisation table (qtables= with three): one more DQT segment in front of SOF0
 
 # The four Annex K Huffman table segments as libjpeg writes them (ids 00, 10, 01, 11): 16 counts, then the symbols.
 _DHT = tuple(bytes.fromhex(t) for t in (
@@ -84,16 +89,70 @@ def libjpeg_qtable(quality, channel=0):
     return np.clip(t, 1, 255).reshape(8, 8)
 
 
-def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None):
+def check_qtables(qtables):
+    """Quantisation tables as a baseline file carries them: two (luma, chroma) or three (Y, Cb, Cr) tables of 64 integers 1..255 in
+    natural (row-major) order, given as (T, 64) or (T, 8, 8) -> (T, 64) uint16.  Everything else is a ValueError that names the
+    table and the entry.  (Larger entries would need 16-bit DQT segments and an SOF1 frame: not written here.)"""
+    try:
+        t = np.asarray(qtables)
+        numeric = np.issubdtype(t.dtype, np.number) or t.dtype == np.bool_
+    except Exception:
+        numeric = False
+    if not numeric:
+        raise ValueError('qtables: two or three tables of 64 numbers needed, got {}'.format(type(qtables).__name__))
+    if t.ndim == 3 and t.shape[1:] == (8, 8):
+        t = t.reshape(t.shape[0], 64)
+    if t.ndim != 2 or t.shape[1] != 64:
+        raise ValueError('qtables: shape (T, 64) or (T, 8, 8) needed, got {}'.format(tuple(np.shape(qtables))))
+    if t.shape[0] not in (2, 3):
+        raise ValueError('qtables: 2 tables (luma, chroma) or 3 (Y, Cb, Cr) needed, got {}'.format(t.shape[0]))
+    t = t.astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        bad = ~np.isfinite(t) | (t != np.rint(t)) | (t < 1) | (t > 255)
+    if bad.any():
+        k, e = (int(v[0]) for v in np.nonzero(bad))
+        raise ValueError('qtables: entry {} (row {}, column {}) of table {} is {}: integers 1..255 needed (a baseline file has 8-bit '
+                         'tables)'.format(e, e // 8, e % 8, k, t[k, e]))
+    return t.astype(np.uint16)
+
+
+def _quality_or_tables(quality, qtables, clamp=False):
+    """Exactly one of the two says what a file is quantised with -> (quality 1..100 or None, (T, 64) uint16 or None); checked on the
+    host, before anything is uploaded.  A quality outside 1..100 is refused, or with `clamp` left to libjpeg_qtable's clamp."""
+    if (quality is None) == (qtables is None):
+        raise ValueError('either a quality or qtables= is needed, {} were given'.format('both' if qtables is not None else 'neither'))
+    if qtables is not None:
+        return None, check_qtables(qtables)
+    if clamp:
+        return quality, None
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError('Invalid JPEG quality: {}'.format(q))
+    return q, None
+
+
+def _header_bytes(tables):
+    """(bytes from SOI to the end of SOS with the Annex K Huffman tables, offset of the first DHT segment) of a file with
+    `tables` = None or (2, 64): 623 and 177; (3, 64): one DQT segment more."""
+    extra = _DQT_BYTES if tables is not None and len(tables) == 3 else 0
+    return JPEG_HEADER_BYTES + extra, _DHT_OFFSET + extra
+
+
+def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None):
     """The bytes from SOI to the end of SOS as libjpeg writes them: 623 with default settings.  huffman: one image's four tables in
     DHT-id order 00 10 01 11 as (4, 272) bytes (16 counts, then the symbols in code order) - what libjpeg writes with optimize_coding:
-    four DHT segments of 21 bytes + the table's symbols each.  The first DHT segment stays at offset 177."""
+    four DHT segments of 21 bytes + the table's symbols each.  The first DHT segment stays at offset 177.  qtables (with quality None,
+    see check_qtables): these tables instead of a quality's, as libjpeg writes a caller's - zig-zag, one DQT segment each; a third
+    table goes to Cr (selector 2 in SOF0) and moves everything behind it by 69 bytes: 692 in all, the first DHT at 246."""
     hs, vs = ops.jpeg_subsampling(subsampling)
+    quality, qtables = _quality_or_tables(quality, qtables, clamp=True)
+    if qtables is None:
+        qtables = np.stack([libjpeg_qtable(quality, t).ravel() for t in (0, 1)])
     order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
     out = bytes.fromhex('ffd8' 'ffe00010' '4a46494600' '0101' '00' '0001' '0001' '0000')
-    for t in (0, 1):
-        out += bytes.fromhex('ffdb0043') + bytes([t]) + libjpeg_qtable(quality, t).ravel()[order].astype(np.uint8).tobytes()
-    out += bytes.fromhex('ffc00011' '08') + struct.pack('>HH', h, w) + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, 1])
+    for t, table in enumerate(qtables):
+        out += bytes.fromhex('ffdb0043') + bytes([t]) + table[order].astype(np.uint8).tobytes()
+    out += bytes.fromhex('ffc00011' '08') + struct.pack('>HH', h, w) + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, len(qtables) - 1])
     tables = _DHT
     if huffman is not None:
         huffman = np.asarray(huffman)
@@ -153,74 +212,102 @@ def _device_codec_optimised(coef, n, h, w, hs, vs):
     return [blob[ends[i]:ends[i + 1]] for i in range(n)], tables
 
 
-def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True, optimize=False):
+def _device_codec_plain(coef, n, h, w, hs, vs, ws=None):
+    """[segment bytes] with the Annex K tables: one download for the lengths, one for the segments."""
+    # room for 3 bytes per sample (random noise at quality 100 needs about 2); the bound is 6.5, and a batch that needs more
+    # than it was given reports so through its lengths and is coded again with exactly what it needs
+    scan = ops.jpeg_geometry(h, w, hs, vs)[1]
+    capacity = n * min(ops.jpeg_ecd_bound(h, w, hs, vs), 192 * scan + 1024)
+    data, lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=capacity)
+    lengths = lengths.cpu().numpy().astype(np.int64)
+    if int(lengths.sum()) > capacity:
+        data, _ = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=int(lengths.sum()))
+    blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
+    ends = np.concatenate([[0], np.cumsum(lengths)])
+    return [blob[ends[i]:ends[i + 1]] for i in range(n)]
+
+
+def _device_tables(tables, items, device):
+    """Table sets (K, T, 64) uint16 of check_qtables -> the (K * items, 3, 64) device tensor the table kernels read, set-major: every
+    set repeated for `items` consecutive items; with two tables Cr takes the chroma table."""
+    t = np.asarray(tables)
+    t = t[:, [0, 1, 1]] if t.shape[1] == 2 else t
+    return torch.from_numpy(np.repeat(t, items, axis=0).view(np.int16)).to(device)
+
+
+def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True, optimize=False, *, qtables=None):
     """One batch through the GPU codec: x (n,h,w,3) device tensor, float32 or uint8 -> (decoded (n,h,w,3) float32 device tensor or
     None, list of the entropy-coded segments as bytes or None).  One host synchronisation (for the lengths) when want_bytes.
     With `optimize` the segments are coded with per-image optimal Huffman tables (histogram -> optimal tables -> encode_tables, the
-    tables and the lengths coming back together) and a third value is returned: the tables, (n, 4, 272) uint8, or None."""
+    tables and the lengths coming back together) and a third value is returned: the tables, (n, 4, 272) uint8, or None.
+    qtables (with quality None, see check_qtables): the whole batch is quantised with these tables instead of a quality's
+    (ops.jpeg_transform_tables, ops.jpeg_reconstruct_tables)."""
     hs, vs = ops.jpeg_subsampling(subsampling)
-    quality = int(quality)
-    if not 1 <= quality <= 100:
-        raise ValueError('Invalid JPEG quality: {}'.format(quality))
+    quality, qtables = _quality_or_tables(quality, qtables)
     n, h, w, _ = x.shape
     ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
-    coef = ops.jpeg_transform(x, quality, hs, vs, workspace=ws)
+    if qtables is None:
+        coef = ops.jpeg_transform(x, quality, hs, vs, workspace=ws)
+    else:
+        qt = _device_tables(qtables[None], n, x.device)
+        coef = ops.jpeg_transform_tables(x, qt, hs, vs, workspace=ws)[0]          # (check_qtables has seen every entry: no flag to read)
     segments = tables = None
     if want_bytes and optimize:
         segments, tables = _device_codec_optimised(coef, n, h, w, hs, vs)
     elif want_bytes:
-        # room for 3 bytes per sample (random noise at quality 100 needs about 2); the bound is 6.5, and a batch that needs more
-        # than it was given reports so through its lengths and is coded again with exactly what it needs
-        scan = ops.jpeg_geometry(h, w, hs, vs)[1]
-        capacity = n * min(ops.jpeg_ecd_bound(h, w, hs, vs), 192 * scan + 1024)
-        data, lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=capacity)
-        lengths = lengths.cpu().numpy().astype(np.int64)
-        if int(lengths.sum()) > capacity:
-            data, _ = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=int(lengths.sum()))
-        blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
-        ends = np.concatenate([[0], np.cumsum(lengths)])
-        segments = [blob[ends[i]:ends[i + 1]] for i in range(n)]
-    image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if want_image else None
+        segments = _device_codec_plain(coef, n, h, w, hs, vs, ws)
+    image = None
+    if want_image:
+        image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if qtables is None else \
+            ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, workspace=ws)
     return (image, segments, tables) if optimize else (image, segments)
 
 
-def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False):
+def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtables=None):
     """The JPEG files of a batch (n,h,w,3) or one image (h,w,3), a list of bytes.  uint8 input is coded as it is; float input goes
     through the reference's conversion (x / 255 first if its maximum exceeds 1, then (255 x) truncated).  `optimize`: every file with
-    Huffman tables of its own, the files libjpeg writes with optimize_coding (Pillow: optimize=True)."""
+    Huffman tables of its own, the files libjpeg writes with optimize_coding (Pillow: optimize=True).  qtables (with quality None, see
+    check_qtables): the files libjpeg writes with these quantisation tables (Pillow: qtables=[...])."""
+    quality, qtables = _quality_or_tables(quality, qtables)
     x = _device_batch(batch_x, keep_bytes=True)
     if x.dim() == 3:
         x = x[None]
     if optimize:
-        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, optimize=True)
-        return [jpeg_header(x.shape[1], x.shape[2], quality, subsampling, huffman=t) + s + b'\xff\xd9' for s, t in zip(segments, tables)]
-    _, segments = device_codec(x, quality, subsampling, want_image=False)
-    head = jpeg_header(x.shape[1], x.shape[2], quality, subsampling)
+        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, optimize=True, qtables=qtables)
+        return [jpeg_header(x.shape[1], x.shape[2], quality, subsampling, huffman=t, qtables=qtables) + s + b'\xff\xd9'
+                for s, t in zip(segments, tables)]
+    _, segments = device_codec(x, quality, subsampling, want_image=False, qtables=qtables)
+    head = jpeg_header(x.shape[1], x.shape[2], quality, subsampling, qtables=qtables)
     return [head + s + b'\xff\xd9' for s in segments]
 
 
-def _optimised_header_bytes(tables):
-    """SOI .. SOS with the DHT segments of `tables` (..., 4, 272): 623 with each table's symbols in place of Annex K's 348."""
-    return JPEG_HEADER_BYTES - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)
+def _optimised_header_bytes(tables, base=JPEG_HEADER_BYTES):
+    """SOI .. SOS with the DHT segments of `tables` (..., 4, 272): `base` (623, or 692 with three quantisation tables) with each
+    table's symbols in place of Annex K's 348."""
+    return base - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)
 
 
-def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False):
+def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False, *, qtables=None):
     """Compress an image or a batch with the standard JPEG codec (jpeg_helpers.py:82-114).  (h,w,3) -> (float64 image, bytes);
     (n,h,w,3) -> (float32 batch, list of bytes).  `effective` counts from the first Huffman table on instead of the whole file.
     Every input, uint8 included, goes through the reference's conversion: x / 255 in float32 if the maximum exceeds 1, then
     (255 x) truncated - a byte k can come out as k - 1.  Values that numpy's cast would wrap are clamped to 0..255.
-    `optimize`: the sizes are those of the files with optimised Huffman tables (encode_batch(optimize=True)); the image is the same."""
+    `optimize`: the sizes are those of the files with optimised Huffman tables (encode_batch(optimize=True)); the image is the same.
+    qtables (with jpeg_quality None, see check_qtables): the codec with these quantisation tables instead of a quality's; the sizes
+    are those of encode_batch(qtables=) - a third table costs 69 bytes of header, none of the effective size."""
+    jpeg_quality, qtables = _quality_or_tables(jpeg_quality, qtables)
     x = _device_batch(batch_x, keep_bytes=False)
     if x.dim() not in (3, 4):
         raise ValueError('compress_batch needs an (h,w,3) image or an (n,h,w,3) batch')
     single = x.dim() == 3
+    head, dht = _header_bytes(qtables)
     if optimize:
-        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=True)
-        heads = _optimised_header_bytes(tables).tolist()
+        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=True, qtables=qtables)
+        heads = _optimised_header_bytes(tables, head).tolist()
     else:
-        image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling)
-        heads = [JPEG_HEADER_BYTES] * len(segments)
-    sizes = [hd + len(s) + 2 - (_DHT_OFFSET if effective else 0) for hd, s in zip(heads, segments)]
+        image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling, qtables=qtables)
+        heads = [head] * len(segments)
+    sizes = [hd + len(s) + 2 - (dht if effective else 0) for hd, s in zip(heads, segments)]
     image = image.cpu().numpy()
     if single:
         return np.rint(image[0] * np.float32(255)).astype(np.uint8) / 255, sizes[0]
@@ -267,8 +354,9 @@ def _check_qualities(qualities):
     return q.astype(np.int64)
 
 
-def _file_bytes(lengths, effective):
-    return JPEG_HEADER_BYTES + lengths + 2 - (_DHT_OFFSET if effective else 0)
+def _file_bytes(lengths, effective, tables=None):
+    head, dht = _header_bytes(tables)
+    return head + lengths + 2 - (dht if effective else 0)
 
 
 def _qualities_per_call(n, h, w, hs, vs, total):
@@ -280,22 +368,30 @@ def _qualities_per_call(n, h, w, hs, vs, total):
     return k
 
 
-def _item_round(x, item_q, hs, vs, want_lengths, want_images, optimize=False):
+def _item_round(x, item_q, hs, vs, want_lengths, want_images, optimize=False, item_tables=None):
     """One item call: source batch x, one quality per item (item j = image j % n) -> (lengths (items,) int32 device tensor or None,
     decoded (items,h,w,3) device tensor or None).  Nothing is read back.  With `optimize` the lengths are those of the segments coded
     with each item's optimal tables plus what its header has beyond the 623 bytes (so that _file_bytes holds), and a third value is
-    returned: the status (items,) int32 of JPEG_OPT_STATUS_BITS, or None."""
+    returned: the status (items,) int32 of JPEG_OPT_STATUS_BITS, or None.  item_tables (items, 3, 64): one table set per item on the
+    device in place of the qualities (item_q is None then)."""
     _, h, w, _ = x.shape
-    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(len(item_q), h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
-    q = ops.jpeg_item_qualities(item_q, len(item_q), x.device)
-    coef, _ = ops.jpeg_transform_items(x, q, hs, vs, workspace=ws)
+    items = len(item_q) if item_tables is None else item_tables.shape[0]
+    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(items, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
+    if item_tables is None:
+        q = ops.jpeg_item_qualities(item_q, items, x.device)
+        coef, _ = ops.jpeg_transform_items(x, q, hs, vs, workspace=ws)
+    else:
+        coef, _ = ops.jpeg_transform_tables(x, item_tables, hs, vs, workspace=ws)
     status = None
     if want_lengths and optimize:
         _, lengths, tables, status = _optimised(coef, h, w, hs, vs, 1)                                         # byte counts only
         lengths = lengths + (tables[:, :, :16].sum(dim=(1, 2), dtype=torch.int32) - 348)
     else:
         lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=1)[1] if want_lengths else None      # byte counts only
-    y = ops.jpeg_reconstruct_items(coef, h, w, q, hs, vs, workspace=ws)[0] if want_images else None
+    y = None
+    if want_images:
+        y = ops.jpeg_reconstruct_items(coef, h, w, q, hs, vs, workspace=ws)[0] if item_tables is None else \
+            ops.jpeg_reconstruct_tables(coef, h, w, item_tables, hs, vs, workspace=ws)
     return (lengths, y, status) if optimize else (lengths, y)
 
 
@@ -306,18 +402,28 @@ def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, wan
     uploaded once and coded as Q * n items - one transform, one encode and one reconstruct call, or one set per group of qualities
     where the workspace would exceed RD_WORKSPACE_BUDGET - and the numbers come back in one download.  With `optimize` the byte counts
     are those of the files with optimised Huffman tables (three more calls per group); everything else is unchanged."""
-    from ..helpers import metrics
     q = _check_qualities(qualities)
     hs, vs = ops.jpeg_subsampling(subsampling)
     x = _device_batch(batch_x, keep_bytes=False)
     if x.dim() != 4 or x.shape[3] != 3:
         raise ValueError('rate_distortion needs an (n,h,w,3) batch')
+    n = x.shape[0]
+    # quality-major: item j = (part[j // n], image j % n)
+    return _rate_distortion(x, len(q), hs, vs, lambda k0, k1: _item_round(x, np.repeat(q[k0:k1], n), hs, vs, True, True, optimize),
+                            effective, want_images, optimize, None)
+
+
+def _rate_distortion(x, total, hs, vs, item_round, effective, want_images, optimize, tables):
+    """The table of rate_distortion over `total` rows (qualities or table sets) of the device batch x: item_round(k0, k1) codes rows
+    k0 .. k1 - 1 as (k1 - k0) * n items, row-major, and returns what _item_round does; `tables` is what _file_bytes counts the
+    header from."""
+    from ..helpers import metrics
     n, h, w, _ = x.shape
-    step = _qualities_per_call(n, h, w, hs, vs, len(q))
+    step = _qualities_per_call(n, h, w, hs, vs, total)
     rows, images = [], []
-    for k0 in range(0, len(q), step):
-        part = q[k0:k0 + step]
-        done = _item_round(x, np.repeat(part, n), hs, vs, True, True, optimize)        # quality-major: item j = (part[j // n], image j % n)
+    for k0 in range(0, total, step):
+        part = range(k0, min(k0 + step, total))
+        done = item_round(part.start, part.stop)
         lengths, y = done[0], done[1]
         status = done[2] if optimize else torch.zeros_like(lengths)
         y = y.view(len(part), n, h, w, 3)
@@ -331,13 +437,33 @@ def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, wan
             images.append(y)
     table = torch.stack(rows).cpu().numpy()                            # (Q, 5, n): the one download
     _raise_on_opt_status(table[:, 4].astype(np.int64).reshape(-1))
-    size = _file_bytes(table[:, 3].astype(np.int64), effective)
+    size = _file_bytes(table[:, 3].astype(np.int64), effective, tables)
     with np.errstate(divide='ignore'):
         out = {'ssim': table[:, 0], 'psnr': table[:, 1], 'msssim': table[:, 2], 'msssim_db': -10.0 * np.log10(1.0 - table[:, 2]),
                'bytes': size, 'bpp': 8 * size / h / w}
     if want_images:
         return out, (images[0] if len(images) == 1 else torch.cat(images))
     return out
+
+
+def rate_distortion_tables(batch_x, tables, subsampling='4:4:4', effective=True, want_images=False, optimize=False):
+    """rate_distortion over K quantisation table sets in place of qualities: tables (K, T, 64) or (K, T, 8, 8), T = 2 or 3, every set
+    as check_qtables takes it - a quality ladder of learned tables, say.  Returns the dictionary of rate_distortion with (K, n)
+    arrays (the byte counts those of compress_batch(qtables=tables[k])), with want_images also the decoded (K,n,h,w,3) device tensor.
+    The batch is coded as K * n items, one table set per item, in one transform, one encode and one reconstruct call per group
+    within RD_WORKSPACE_BUDGET, and the numbers come back in one download."""
+    if np.ndim(tables) not in (3, 4) or len(tables) == 0:
+        raise ValueError('rate_distortion_tables: table sets (K, T, 64) or (K, T, 8, 8) needed, got shape {}'.format(np.shape(tables)))
+    sets = np.stack([check_qtables(t) for t in tables])
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    x = _device_batch(batch_x, keep_bytes=False)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError('rate_distortion_tables needs an (n,h,w,3) batch')
+    n = x.shape[0]
+    # set-major: item j = (sets[j // n], image j % n)
+    return _rate_distortion(x, len(sets), hs, vs,
+                            lambda k0, k1: _item_round(x, None, hs, vs, True, True, optimize, _device_tables(sets[k0:k1], n, x.device)),
+                            effective, want_images, optimize, sets[0])
 
 
 def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4', optimize=False):
@@ -621,6 +747,31 @@ def decode_coefficients(files, device_output=False, subseq_bits=0, device=None):
     _, _, coef, status, _, _ = groups[0]
     _raise_on_status(groups, [status.cpu().numpy()])
     return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
+
+
+def transcode_batch(files, optimize=True):
+    """Baseline files written again with their coefficients and their quantisation tables untouched - a list of bytes in input order.
+    The Huffman tables are the optimal ones of each image (what jpegtran -optimize does) or, with optimize=False, Annex K's.  Every
+    file parse_header accepts is read; the header written is the one of encode_batch - JFIF APP0, two DQT segments where the file's Cb
+    and Cr tables are equal, else three; APPn and COM segments are dropped.  Files go up in one copy, every group of equal (h, w,
+    sampling) is decoded (nimg_jpeg_decode) and coded again on the device without a pixel being computed.  Damaged data raises as in
+    decode_batch."""
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    files = [bytes(files)] if single else [bytes(f) for f in files]
+    headers, groups = _decode_groups(files, 0, None)
+    _raise_on_status(groups, np.split(torch.cat([g[3] for g in groups]).cpu().numpy(), np.cumsum([len(g[0]) for g in groups])[:-1]))
+    names = {v: k for k, v in ops.JPEG_SUBSAMPLING.items()}
+    result = [None] * len(files)
+    for idx, (h, w, hs, vs), coef, _, _, _ in groups:
+        if optimize:
+            segments, tables = _device_codec_optimised(coef, len(idx), h, w, hs, vs)
+        else:
+            segments, tables = _device_codec_plain(coef, len(idx), h, w, hs, vs), [None] * len(idx)
+        for i, s, t in zip(idx, segments, tables):
+            qt = headers[i].qtables
+            qt = qt[:2] if np.array_equal(qt[1], qt[2]) else qt
+            result[i] = jpeg_header(h, w, None, names[(hs, vs)], huffman=t, qtables=qt) + s + b'\xff\xd9'
+    return result
 
 
 class JPEGMarkerStats(object):

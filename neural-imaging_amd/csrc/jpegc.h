@@ -1,5 +1,6 @@
 // What the units of the JPEG family share (jpegc.hip: one quality per batch and the entropy coder; jpegc_items.hip: one quality per
-// image; jpegd.hip: the tables of each file; jpegc_opt.hip: the coder with the caller's Huffman tables): the workspace layout, the
+// image; jpegc_tables.hip: the caller's quantisation tables per item; jpegd.hip: the tables of each file; jpegc_opt.hip: the coder with
+// the caller's Huffman tables): the workspace layout, the
 // quantisation tables, the bit sink of the two coders, and the forward-transform and inverse-DCT kernels as templates over where their
 // quantisation table comes from - a unit instantiates them with its own table source, so each instantiation knows the address space it
 // reads.  Everything here has internal linkage - each unit compiles its own copy.
@@ -60,11 +61,14 @@ struct QTabs { uint16_t q[2][64]; };        // [luma | chroma], natural order
 // A table source is what the transform and the inverse-DCT kernel are templates over:
 //   table(g, t, item, comp)   the 64 divisors, natural order, of component `comp` of image `item`; t = the thread's block in the batch
 //   source(item)              the image whose pixels item `item` transforms
+//   divisor(q, nat)           entry `nat` of the table q that table() returned, as the transform divides by it: the entry itself where
+//                             the tables are the library's own, clamped to 1..255 where they are a caller's (jpegc_tables.hip)
 // This one passes the tables of one quality for the whole batch by value in the kernel arguments.
 struct BatchTables {
     QTabs qt;
     __device__ __forceinline__ const uint16_t* table(const JpegGeo&, long, int, int comp) const { return qt.q[comp ? 1 : 0]; }
     __device__ __forceinline__ int source(int item) const { return item; }
+    __device__ __forceinline__ int divisor(const uint16_t* q, int nat) const { return q[nat]; }
 };
 
 constexpr int Q_BASE[2][64] = {
@@ -247,7 +251,7 @@ __global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restr
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
         const int nat = c_nat_of_zz[k];
-        const int v = d[nat], qv = (int)q[nat] << 3;
+        const int v = d[nat], qv = tabs.divisor(q, nat) << 3;
         const int m = (int)(((unsigned)abs(v) + (unsigned)(qv >> 1)) / (unsigned)qv);
         const uint32_t c16 = (uint32_t)(v < 0 ? -m : m) & 0xffffu;
         if (k & 1) o[k >> 1] |= c16 << 16;

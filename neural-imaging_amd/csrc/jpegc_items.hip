@@ -30,6 +30,7 @@ struct ItemTables {
         return c_qbank.t[min(max(q, 1), 100) - 1].q[comp ? 1 : 0];
     }
     __device__ __forceinline__ int source(int item) const { return item % n_src; }
+    __device__ __forceinline__ int divisor(const uint16_t* q, int nat) const { return q[nat]; }
 };
 
 }  // namespace

@@ -9,6 +9,8 @@ Differences by design: Q tables are passed to the kernel per call, so the tempor
 (:235-243, not re-entrant in the reference) has no shared state here.  The 'libjpeg' codec (:227-233) - the reference's
 final-validation codec, a host round trip through imageio there - is the baseline codec of csrc/jpegc.hip here: libjpeg's
 files and decoded images bit for bit, on the device (compression/jpeg_helpers.py).  It has no gradient.
+New: JPEG.file_tables / JPEG.process_files run that real codec with the model's own tables - the learned ones, or those the
+differentiable codec divides by - so the two stand side by side at identical tables.
 """
 import numpy as np
 import torch
@@ -16,7 +18,7 @@ import torch
 from .. import ops
 from ..device import DeviceArray, default_device, to_device
 from ..helpers.utils import is_number
-from ..compression.jpeg_helpers import device_codec, jpeg_qf_estimation
+from ..compression.jpeg_helpers import compress_batch, device_codec, encode_batch, jpeg_qf_estimation, libjpeg_qtable
 from .tfmodel import ParamStore, TFModel
 
 _common_codec = None
@@ -155,6 +157,46 @@ class JPEG(TFModel):
         y, _ = self.forward(to_device(batch_x, self.device), quality)
         y = DeviceArray(y)
         return (y, np.nan) if return_entropy else y
+
+    # the real codec with the model's own tables ---------------------------------------------------
+    def file_tables(self):
+        """The model's own (luma, chroma) tables as a baseline file can carry them: (tables (2, 64) uint16 in natural order, clamped
+        (2, 64) bool).  The learned weights with trainable=True, else the tables of the constructor's quality as the differentiable
+        codec uses them (_model_tables), rounded to the nearest integer (ties to even) and clamped to 1..255 on the device
+        (ops.jpeg_tables_from_float); `clamped` marks the entries that rule had to move - below 1, above 255 or not finite.
+        codec='libjpeg': libjpeg's own tables of the numeric quality, nothing clamped."""
+        if self._codec_model is None:
+            if not is_number(self.quality):
+                raise ValueError('file_tables needs a numeric quality with codec="libjpeg", got {}'.format(self.quality))
+            q = self.resolve_quality(self.quality)
+            return np.stack([libjpeg_qtable(q, c).ravel() for c in (0, 1)]).astype(np.uint16), np.zeros((2, 64), bool)
+        if self.trainable:
+            t = self._codec_model.params.flat.detach().view(1, 2, 64)
+        else:
+            t = self._codec_model.qtables(self.quality, self.device)[:2].reshape(1, 2, 64)
+        t = t.contiguous()
+        qtabs, _ = ops.jpeg_tables_from_float(t)
+        both = torch.cat([qtabs[0, :2].reshape(-1).float(), t.reshape(-1)]).cpu().numpy()          # one download
+        tables, t = both[:128].reshape(2, 64).astype(np.uint16), both[128:].reshape(2, 64)
+        with np.errstate(invalid='ignore'):
+            return tables, ~np.isfinite(t) | (np.rint(t) < 1) | (np.rint(t) > 255)
+
+    def process_files(self, batch_x, subsampling='4:4:4', optimize=False, return_files=False):
+        """The real codec with exactly file_tables(): (float32 (n,h,w,3) batch libjpeg decodes, list of byte counts[, list of the
+        files]) - what the learned tables, or the soft / sin / harmonic codec's, cost in bytes and do to the image once a standard
+        encoder holds them.  Forward only: the real codec has no gradient (forward(training=True) of the libjpeg codec says the same)."""
+        x = to_device(batch_x, self.device)
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise NotImplementedError('the real codec has no gradient (the reference has none either): train on a differentiable '
+                                      'codec, measure on this one')
+        tables, _ = self.file_tables()
+        y, sizes = compress_batch(x, None, subsampling=subsampling, optimize=optimize, qtables=tables)
+        if y.ndim == 3:
+            raise ValueError('process_files needs an (n,h,w,3) batch')
+        if return_files:
+            # x is float32 here, so the files hold the bytes compress_batch coded: the reference's conversion, no uint8 short cut
+            return y, sizes, encode_batch(x, None, subsampling, optimize=optimize, qtables=tables)
+        return y, sizes
 
     def __repr__(self):
         if self._codec_model is not None:              # models/jpeg.py:253-257

@@ -2497,3 +2497,44 @@ def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None,
     _lib.call('nimg_jpeg_encode_tables', _p(coef), n, h, w, hs, vs, _p(tables), _p(out),
               out.numel() if capacity is None else int(capacity), _p(lengths), _p(status), _p(workspace), need, _stream())
     return out, lengths, status
+
+
+# any quantisation tables: a table set is (3, 64) uint16 [Y, Cb, Cr] in natural order, one set per item
+def _jpeg_qtabs(qtabs, name):
+    _chk(qtabs)
+    if qtabs.element_size() != 2 or qtabs.is_floating_point() or qtabs.dim() != 3 or tuple(qtabs.shape[1:]) != (3, 64) or qtabs.shape[0] < 1:
+        raise RuntimeError('{}: tables {} {}, (n_items, 3, 64) 16-bit integers needed'.format(name, qtabs.dtype, tuple(qtabs.shape)))
+    return qtabs
+
+
+def jpeg_transform_tables(x, qtabs, hs=1, vs=1, workspace=None, err=None):
+    """(n_src,h,w,3) float32 or uint8 and one table set per item, qtabs (n_items, 3, 64) uint16 (or int16 bit patterns) in natural order
+    on the device -> ((n_items, real blocks, 64) int16 coefficients laid out as jpeg_transform's, (1,) int32 error flag: non-zero = an
+    entry outside 1..255 was clamped).  Item j codes source image j % n_src with qtabs[j]."""
+    _chk(x)
+    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
+        raise RuntimeError('jpeg_transform_tables needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(x.dtype, tuple(x.shape)))
+    qtabs = _jpeg_qtabs(qtabs, 'jpeg_transform_tables')
+    n_src, h, w, _ = x.shape
+    n_items = qtabs.shape[0]
+    ws, need = _jpeg_workspace(n_items, h, w, hs, vs, x.device, workspace)
+    coef = torch.empty((n_items, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
+    err = torch.zeros((1,), dtype=torch.int32, device=x.device) if err is None else err
+    _lib.call('nimg_jpeg_transform_tables', _p(x), int(x.dtype == torch.uint8), n_src, h, w, hs, vs, _p(qtabs), n_items, _p(coef), _p(err),
+              _p(ws), need, _stream())
+    return coef, err
+
+
+def jpeg_tables_from_float(t):
+    """float32 tables (n_sets, n_tabs, 64) or (n_sets, n_tabs, 8, 8) on the device, natural order, n_tabs 2 or 3 -> (qtabs (n_sets, 3, 64)
+    int16 holding the uint16 entries - rint (ties to even) clamped to 1..255; with two tables Cr takes the chroma table - and status
+    (n_sets,) int32: bits 1 = an entry was raised to 1, 2 = lowered to 255, 4 = not finite)."""
+    _f32(t)
+    if t.dim() == 4 and tuple(t.shape[2:]) == (8, 8):
+        t = t.reshape(t.shape[0], t.shape[1], 64)
+    if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] not in (2, 3) or t.shape[2] != 64:
+        raise RuntimeError('jpeg_tables_from_float: float32 (n_sets, 2 or 3, 64) needed, got {}'.format(tuple(t.shape)))
+    qtabs = torch.empty((t.shape[0], 3, 64), dtype=torch.int16, device=t.device)
+    status = torch.empty(t.shape[0], dtype=torch.int32, device=t.device)
+    _lib.call('nimg_jpeg_tables_from_float', _p(t), t.shape[0], t.shape[1], _p(qtabs), _p(status), _stream())
+    return qtabs, status

@@ -15,8 +15,12 @@ image - the sequential decode the parallel one is measured against.  One JSON li
 --optimize times writing with optimised Huffman tables: nimg_jpeg_histogram, nimg_jpeg_optimal_tables and
 nimg_jpeg_encode_tables next to nimg_jpeg_encode on the same coefficients, encode_batch with and without optimize from host batch
 to files, and the segment and whole-file bytes either way.  One JSON line per sub-sampling.
+--qtables times the table form with libjpeg's tables of --quality, so that its numbers stand next to the
+default mode's: nimg_jpeg_transform_tables (the divisors read from device memory), nimg_jpeg_encode on its coefficients,
+nimg_jpeg_reconstruct_tables and compress_batch(qtables=); the coefficients are checked against the quality form's.  One JSON line
+per sub-sampling.
 
-    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode | --optimize]
+    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode | --optimize | --qtables]
 For the split of the calls into their kernels: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_time.py ...
 """
 import argparse
@@ -171,6 +175,28 @@ def measure_optimize(x_host, quality, subsampling, reps, dev):
             'ms': {k: round(v, 4) for k, v in ms.items()}, 'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
 
 
+def measure_qtables(x_host, quality, subsampling, reps, dev):
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    n, h, w, _ = x_host.shape
+    x = torch.from_numpy(x_host).to(dev)
+    pair = np.stack([jpeg_helpers.libjpeg_qtable(quality, c).ravel() for c in (0, 1)])
+    qt = jpeg_helpers._device_tables(jpeg_helpers.check_qtables(pair)[None], n, dev)
+    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
+    ms = {}
+    ms['transform'], (coef, err) = timed(lambda: ops.jpeg_transform_tables(x, qt, hs, vs, workspace=ws), reps)
+    assert int(err.item()) == 0 and torch.equal(coef, ops.jpeg_transform(x, quality, hs, vs))
+    ms['encode'], (data, lengths) = timed(lambda: ops.jpeg_encode(coef, h, w, hs, vs, out=out, workspace=ws), reps)
+    ln = lengths.cpu().numpy().astype(np.int64)
+    ms['reconstruct'], y = timed(lambda: ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, workspace=ws), reps)
+    ms['compress_batch_total'], (yb, sizes) = timed(
+        lambda: jpeg_helpers.compress_batch(x_host, None, subsampling=subsampling, qtables=pair), reps)
+    assert np.array_equal(yb, y.cpu().numpy()) and sizes == (ln + jpeg_helpers.JPEG_HEADER_BYTES + 2).tolist()
+    return {'mode': 'qtables', 'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality, 'bytes': int(ln.sum()),
+            'bpp': 8.0 * float(np.mean(sizes)) / h / w, 'ms': {k: round(v, 4) for k, v in ms.items()},
+            'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
+
+
 def pillow(x_host, quality, subsampling, reps):
     from PIL import Image
     u8 = np.clip(np.trunc(np.float32(255) * x_host), 0, 255).astype(np.uint8)
@@ -195,6 +221,7 @@ def main():
     ap.add_argument('--pillow', action='store_true', help='time Pillow on the host instead (no GPU needed)')
     ap.add_argument('--decode', action='store_true', help='time the decoder instead, per subseq_bits setting')
     ap.add_argument('--optimize', action='store_true', help='time writing with optimised Huffman tables next to nimg_jpeg_encode')
+    ap.add_argument('--qtables', action='store_true', help="time the table form with libjpeg's tables of --quality instead")
     args = ap.parse_args()
     x = natural_images(args.batch, args.size, args.size, seed=1)
     if args.pillow:
@@ -214,6 +241,11 @@ def main():
         for subsampling in SUBSAMPLINGS:
             measure_optimize(x[:4], args.quality, subsampling, 2, dev)                # warm-up
             print(json.dumps(dict(measure_optimize(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())), flush=True)
+        return
+    if args.qtables:
+        for subsampling in SUBSAMPLINGS:
+            measure_qtables(x, args.quality, subsampling, 3, dev)            # warm-up
+            print(json.dumps(dict(measure_qtables(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())), flush=True)
         return
     for subsampling in SUBSAMPLINGS:
         measure(x, args.quality, subsampling, 3, dev)                    # warm-up: code objects, allocator
