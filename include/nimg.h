@@ -355,7 +355,12 @@ int nimg_msssim(const float* a, const float* b, int n, int h, int w, int c, floa
  *  stats:  var / mean (b, attempts) of every candidate patch / 255 (np.var, np.mean over all three channels; :166-168).
  *  select: the discard policy over each image's candidates -> chosen_xy (b, 2); mode 0 none, 1 'flat' (uniforms (b,
  *          attempts) feed its coin flip, :177-178), 2 'flat-aggressive', 3 'dark-n-textured'; max_attempts = the panic
- *          counter (:156); attempts_used (b, may be NULL) = candidates consumed.
+ *          counter (:156); attempts_used (b, may be NULL) = candidates consumed.  Two deviations from the reference: if the
+ *          candidates run out before the policy settles the last one is taken; and since stats gives an exactly flat patch
+ *          the variance 0.0 (exact integer moments), 'dark-n-textured' rejects it by `0 < variance` - the reference's np.var of
+ *          a constant patch / 255 is a rounding residue of ~1e-34 at most byte levels, which it accepts when the mean is in
+ *          (0.35, 0.99).
+ *  stats and gather need even h and w (2-byte row loads), NIMG_ERR_ARG otherwise.
  *  gather: x_out (b, patch/2, patch/2, 4) = raw crop / 65535, y_out (b, patch, patch, 3) = rgb crop / 255 (either may be
  *          NULL), float32 of the float64 quotient like dataset.py:124-126. */
 int nimg_patch_stats(const uint8_t* rgb, int n_images, int h, int w, const int* image_idx, const int* cand_xy, int b,

@@ -55,6 +55,10 @@ __global__ __launch_bounds__(256) void patch_stats_kernel(const uint8_t* __restr
 // the discard policy of sample_patch over attempt k = 0, 1, ... of one image; mode 0 none, 1 flat, 2 flat-aggressive,
 // 3 dark-n-textured.  If the A candidates run out before the policy settles (only 'flat' can do that, by losing its coin
 // flip more than A - max_attempts times) the last candidate is taken.
+// A second deviation, 'dark-n-textured' on an exactly flat patch: patch_stats_kernel gives such a patch the variance 0.0 (exact
+// integer moments), so `0 < v` rejects it, as the reference's condition says.  The reference's own np.var(patch / 255) of a
+// constant patch is a rounding residue of about 1e-34 at most byte levels (it changes with level and patch size), which passes
+// `0 < variance`: there the reference accepts a flat patch whose mean lies in (0.35, 0.99).  Not reproduced.
 __global__ void patch_select_kernel(const int* __restrict__ cand_xy, const float* __restrict__ uniforms,
                                     const double* __restrict__ var, const double* __restrict__ mean, int B, int A,
                                     int max_attempts, int mode, int* __restrict__ chosen_xy,
@@ -142,6 +146,7 @@ int nimg_patch_stats(const uint8_t* rgb, int n_images, int h, int w, const int* 
     if (b < 0 || attempts <= 0) return NIMG_ERR_ARG;
     if (b == 0) return NIMG_OK;
     if (!rgb || !image_idx || !cand_xy || !var_out || !mean_out || n_images <= 0) return NIMG_ERR_ARG;
+    if ((h & 1) || (w & 1)) return NIMG_ERR_ARG;                   /* as nimg_patch_gather: the 2-byte row loads need an even w */
     if (patch <= 0 || (patch & 1) || patch > h || patch > w || patch > 1024) return NIMG_ERR_ARG;   /* n SS - S^2 stays below 2^64 */
     hipLaunchKernelGGL(patch_stats_kernel, dim3(b * attempts), dim3(256), 0, (hipStream_t)stream, rgb, h, w, image_idx,
                        cand_xy, attempts, patch, var_out, mean_out);

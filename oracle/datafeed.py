@@ -77,7 +77,10 @@ def sample_patch(rgb_image, rgb_patch_size=128, discard=None, max_attempts=25, r
 
 def select(rgb_image, cands, uniforms, rgb_patch_size, discard, max_attempts):
     """The same policy over a GIVEN candidate list (what the device kernels get): -> ((xx, yy), candidates consumed).  If the
-    list runs out the last candidate is taken (the documented deviation of nimg_patch_select)."""
+    list runs out the last candidate is taken (the documented deviation of nimg_patch_select).  A second documented deviation
+    is NOT restated here: patch_stats() above is np.var, which gives an exactly flat patch a rounding residue of about 1e-34 at
+    most byte levels, so 'dark-n-textured' accepts it here when its mean lies in (0.35, 0.99); the device computes exact
+    integer moments, gets 0.0 and rejects it by `0 < var`."""
     pol = Policy(discard, max_attempts)
     for k, (xx, yy) in enumerate(cands):
         var, mean = patch_stats(rgb_image, xx, yy, rgb_patch_size) if discard else (0.0, 0.0)

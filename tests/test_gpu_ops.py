@@ -1600,7 +1600,10 @@ def test_device_data_feed_kernels(dev, discard, patch, attempts, max_attempts):
     ref = np.array([[odf.patch_stats(rgb[image_idx[i]], cand[i, k, 0], cand[i, k, 1], patch) for k in range(attempts)]
                     for i in range(b)])
     assert np.abs(var.cpu().numpy() - ref[..., 0]).max() < 1e-13 and np.abs(mean.cpu().numpy() - ref[..., 1]).max() < 1e-13
-    assert (var.cpu().numpy()[-1] == 0).all()                 # flat image: exactly zero, like np.var
+    # flat image: exactly zero (exact integer moments).  np.var of a constant patch / 255 is a residue of ~1e-34 at most levels,
+    # within the 1e-13 above; at level 77 the mean 0.302 < 0.35 makes both sides reject the patch in 'dark-n-textured' anyway
+    # (levels where they differ: tests/test_gpu_operands_exact.py::test_flat_patches_in_dark_n_textured)
+    assert (var.cpu().numpy()[-1] == 0).all()
     xy, used = ops.patch_select(d_cand, d_uni, var if discard else None, mean if discard else None, discard, max_attempts)
     want = [odf.select(rgb[image_idx[i]], [tuple(c) for c in cand[i]], uni[i], patch, discard, max_attempts)
             for i in range(b)]
