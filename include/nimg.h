@@ -57,8 +57,8 @@ extern "C" {
  * per value; 6: the nimg_l3ic_* bitstream entry points; 7: the nimg_jpeg_* baseline codec entry points; 8: the per-item
  * nimg_jpeg_*_items forms and nimg_msssim; version 8 also carries the later, purely added nimg_jpeg_decode* and
  * nimg_jpeg_reconstruct_tables entry points, the nimg_jpeg_histogram / _optimal_tables / _encode_tables ones and
- * nimg_jpeg_transform_tables / nimg_jpeg_tables_from_float).  A binding compares nimg_abi_version() with the NIMG_ABI_VERSION it was
- * written against. */
+ * nimg_jpeg_transform_tables / nimg_jpeg_tables_from_float, and the nimg_jpeg_*_restart ones).  A binding compares nimg_abi_version()
+ * with the NIMG_ABI_VERSION it was written against. */
 #define NIMG_ABI_VERSION 8
 int nimg_abi_version(void);
 
@@ -800,6 +800,43 @@ int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, in
 int nimg_jpeg_transform_tables(const void* x, int is_u8, int n_src, int h, int w, int hs, int vs, const uint16_t* qtabs, int n_items,
                                int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream);
 int nimg_jpeg_tables_from_float(const float* t, int n_sets, int n_tabs, uint16_t* qtabs, uint32_t* status, void* stream);
+
+/* Writing files with restart intervals (libjpeg's restart_interval, Pillow's restart_marker_blocks): the
+ * writing entry points above with `restart_interval` = Ri MCUs in scan order, 0..65535 (anything else is NIMG_ERR_ARG).  Behind every
+ * Ri MCUs that another MCU follows the coder fills the current byte up with 1-bits, writes the marker FF D0 .. FF D7 (the k-th is
+ * D(k mod 8), never stuffed) and predicts the next DC value of every component from 0.  Ri = 0, and the entry points without the
+ * argument, write no marker: the same bytes as before.  Purely added: NIMG_ABI_VERSION stays.
+ *   encode_restart          nimg_jpeg_encode with the markers in `out` and counted in `lengths`; the DRI segment of the header is the
+ *                           caller's.  A segment is at most 4 bytes per marker longer than without.  The workspace is
+ *                           nimg_jpeg_encode_restart_workspace_bytes, which nimg_jpeg_transform and nimg_jpeg_reconstruct accept too.
+ *   histogram_restart       nimg_jpeg_histogram of the symbols nimg_jpeg_encode_restart emits: the DC differences at the start of an
+ *                           interval differ, as in libjpeg's statistics pass.
+ *   encode_tables_restart   nimg_jpeg_encode_tables with the markers; workspace nimg_jpeg_encode_tables_restart_workspace_bytes.  An
+ *                           image whose tables are refused (status bit 1) is its markers alone.
+ *   decode_restart          nimg_jpeg_decode of segments that carry the markers of `restart_interval` (the file's DRI value; all images
+ *                           of a call share it).  The markers are taken out while the stuffing is, and every interval is an entry
+ *                           point: its first subsequence starts from a known state, subsequences never straddle an interval, and
+ *                           `rounds` is at most the subsequences of the image's longest interval - 1 (0 where every interval fits one
+ *                           subsequence).  A run ends with its interval's blocks; what stands between them and the marker is skipped,
+ *                           as libjpeg skips it.  Status bit 512: restart markers missing, surplus or out of sequence (the k-th must
+ *                           be FF D(k mod 8), and there must be ceil(MCUs / Ri) - 1); the other bits as nimg_jpeg_decode's, "fewer
+ *                           blocks" (32) and "bits beyond the end" (16) per interval.  Workspace:
+ *                           nimg_jpeg_decode_restart_workspace_bytes.  restart_interval = 0 is nimg_jpeg_decode, where FF D0 .. D7
+ *                           are markers like any other (bit 1). */
+size_t nimg_jpeg_encode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval);
+int nimg_jpeg_encode_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint8_t* out,
+                             size_t out_capacity, uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream);
+int nimg_jpeg_histogram_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint32_t* hist,
+                                void* stream);
+size_t nimg_jpeg_encode_tables_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval);
+int nimg_jpeg_encode_tables_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, const uint8_t* tables,
+                                    uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+size_t nimg_jpeg_decode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, size_t ecd_bytes,
+                                                int subseq_bits);
+int nimg_jpeg_decode_restart(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                             int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

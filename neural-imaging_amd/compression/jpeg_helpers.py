@@ -18,6 +18,10 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
   compress_batch), check_qtables,                       ones, the differentiable codec's, a foreign file's (DESIGN.md section 4h);
   rate_distortion_tables, transcode_batch               K table sets over a batch in one item call; a file written again with its
                                                         coefficients and tables untouched and optimal (or Annex K) Huffman tables
+  restart_interval= (jpeg_header, device_codec,         new: files with restart intervals, libjpeg's byte for byte, and - asked for with
+  encode_batch, compress_batch), allow_restart=         allow_restart - read back with every interval as an entry point of the parallel
+  (parse_header, decode_batch, decode_coefficients,     decoder
+  transcode_batch)
   JPEGMarkerStats (:133-250)                            host parsing of a file's segments
 
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
@@ -32,6 +36,7 @@ from .. import ops
 from ..device import default_device, unwrap
 
 JPEG_HEADER_BYTES = 623           # SOI .. SOS of every file written here with two quantisation tables
+_DRI_BYTES = 6                    # a restart interval (restart_interval= above 0): one DRI segment between the last DHT and SOS
 _DHT_OFFSET = 177
 _DQT_BYTES = 69                   # a third quantisation table (qtables= with three): one more DQT segment in front of SOF0
 
@@ -131,20 +136,23 @@ def _quality_or_tables(quality, qtables, clamp=False):
     return q, None
 
 
-def _header_bytes(tables):
+def _header_bytes(tables, restart_interval=0):
     """(bytes from SOI to the end of SOS with the Annex K Huffman tables, offset of the first DHT segment) of a file with
-    `tables` = None or (2, 64): 623 and 177; (3, 64): one DQT segment more."""
+    `tables` = None or (2, 64): 623 and 177; (3, 64): one DQT segment more.  A restart interval adds its DRI segment's 6 bytes behind
+    the Huffman tables."""
     extra = _DQT_BYTES if tables is not None and len(tables) == 3 else 0
-    return JPEG_HEADER_BYTES + extra, _DHT_OFFSET + extra
+    return JPEG_HEADER_BYTES + extra + (_DRI_BYTES if restart_interval else 0), _DHT_OFFSET + extra
 
 
-def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None):
+def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None, *, restart_interval=0):
     """The bytes from SOI to the end of SOS as libjpeg writes them: 623 with default settings.  huffman: one image's four tables in
     DHT-id order 00 10 01 11 as (4, 272) bytes (16 counts, then the symbols in code order) - what libjpeg writes with optimize_coding:
     four DHT segments of 21 bytes + the table's symbols each.  The first DHT segment stays at offset 177.  qtables (with quality None,
     see check_qtables): these tables instead of a quality's, as libjpeg writes a caller's - zig-zag, one DQT segment each; a third
-    table goes to Cr (selector 2 in SOF0) and moves everything behind it by 69 bytes: 692 in all, the first DHT at 246."""
+    table goes to Cr (selector 2 in SOF0) and moves everything behind it by 69 bytes: 692 in all, the first DHT at 246.
+    restart_interval (MCUs, 0..65535): above 0 the DRI segment FFDD 0004 RRRR between the last DHT segment and SOS, 6 bytes more."""
     hs, vs = ops.jpeg_subsampling(subsampling)
+    ri = ops.jpeg_restart_interval(restart_interval)
     quality, qtables = _quality_or_tables(quality, qtables, clamp=True)
     if qtables is None:
         qtables = np.stack([libjpeg_qtable(quality, t).ravel() for t in (0, 1)])
@@ -161,6 +169,8 @@ def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None):
         tables = [bytes([ident]) + t[:16 + int(t[:16].sum(dtype=np.int64))].tobytes() for ident, t in zip((0x00, 0x10, 0x01, 0x11), huffman)]
     for t in tables:
         out += b'\xff\xc4' + struct.pack('>H', len(t) + 2) + t
+    if ri:
+        out += b'\xff\xdd\x00\x04' + struct.pack('>H', ri)
     return out + bytes.fromhex('ffda000c' '03' '0100' '0211' '0311' '00' '3f' '00')
 
 
@@ -180,11 +190,11 @@ JPEG_OPT_STATUS_BITS = OrderedDict([(1, 'Huffman table that is no prefix code'),
                                     (4, 'Huffman code size above 32'), (8, 'symbol histogram total of 2^32 or more')])
 
 
-def _optimised(coef, h, w, hs, vs, capacity):
+def _optimised(coef, h, w, hs, vs, capacity, restart_interval=0):
     """histogram -> optimal tables -> encode_tables on the device: (segments, lengths (n,) int32, tables (n,4,272) uint8, status (n,)
     int32: the bits of JPEG_OPT_STATUS_BITS).  Nothing is read back."""
-    tables, tstatus = ops.jpeg_optimal_tables(ops.jpeg_histogram(coef, h, w, hs, vs))
-    data, lengths, status = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=capacity)
+    tables, tstatus = ops.jpeg_optimal_tables(ops.jpeg_histogram(coef, h, w, hs, vs, restart_interval=restart_interval))
+    data, lengths, status = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=capacity, restart_interval=restart_interval)
     tstatus = tstatus[:, 0] | tstatus[:, 1] | tstatus[:, 2] | tstatus[:, 3]
     return data, lengths, tables, status | (tstatus << 2)
 
@@ -197,31 +207,31 @@ def _raise_on_opt_status(status):
                 i, s, ' | '.join(text for bit, text in JPEG_OPT_STATUS_BITS.items() if s & bit)) for i, s in bad)))
 
 
-def _device_codec_optimised(coef, n, h, w, hs, vs):
+def _device_codec_optimised(coef, n, h, w, hs, vs, restart_interval=0):
     """([segment bytes], tables (n,4,272) uint8 numpy) - lengths, status and tables in one download, then the segments."""
-    capacity = n * min(ops.jpeg_ecd_bound_tables(h, w, hs, vs), 192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024)
-    data, lengths, tables, status = _optimised(coef, h, w, hs, vs, capacity)
+    capacity = n * min(ops.jpeg_ecd_bound_tables(h, w, hs, vs, restart_interval), 192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024)
+    data, lengths, tables, status = _optimised(coef, h, w, hs, vs, capacity, restart_interval)
     flat = torch.cat([lengths.view(torch.uint8), status.view(torch.uint8), tables.reshape(-1)]).cpu().numpy()
     lengths, status = flat[:4 * n].view(np.int32).astype(np.int64), flat[4 * n:8 * n].view(np.int32)
     _raise_on_opt_status(status)
     if int(lengths.sum()) > capacity:
-        data = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=int(lengths.sum()))[0]
+        data = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=int(lengths.sum()), restart_interval=restart_interval)[0]
     tables = flat[8 * n:].reshape(n, 4, 272)
     blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
     ends = np.concatenate([[0], np.cumsum(lengths)])
     return [blob[ends[i]:ends[i + 1]] for i in range(n)], tables
 
 
-def _device_codec_plain(coef, n, h, w, hs, vs, ws=None):
+def _device_codec_plain(coef, n, h, w, hs, vs, ws=None, restart_interval=0):
     """[segment bytes] with the Annex K tables: one download for the lengths, one for the segments."""
     # room for 3 bytes per sample (random noise at quality 100 needs about 2); the bound is 6.5, and a batch that needs more
     # than it was given reports so through its lengths and is coded again with exactly what it needs
     scan = ops.jpeg_geometry(h, w, hs, vs)[1]
-    capacity = n * min(ops.jpeg_ecd_bound(h, w, hs, vs), 192 * scan + 1024)
-    data, lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=capacity)
+    capacity = n * min(ops.jpeg_ecd_bound(h, w, hs, vs, restart_interval), 192 * scan + 1024)
+    data, lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=capacity, restart_interval=restart_interval)
     lengths = lengths.cpu().numpy().astype(np.int64)
     if int(lengths.sum()) > capacity:
-        data, _ = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=int(lengths.sum()))
+        data, _ = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=int(lengths.sum()), restart_interval=restart_interval)
     blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
     ends = np.concatenate([[0], np.cumsum(lengths)])
     return [blob[ends[i]:ends[i + 1]] for i in range(n)]
@@ -235,17 +245,20 @@ def _device_tables(tables, items, device):
     return torch.from_numpy(np.repeat(t, items, axis=0).view(np.int16)).to(device)
 
 
-def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True, optimize=False, *, qtables=None):
+def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True, optimize=False, *, qtables=None, restart_interval=0):
     """One batch through the GPU codec: x (n,h,w,3) device tensor, float32 or uint8 -> (decoded (n,h,w,3) float32 device tensor or
     None, list of the entropy-coded segments as bytes or None).  One host synchronisation (for the lengths) when want_bytes.
     With `optimize` the segments are coded with per-image optimal Huffman tables (histogram -> optimal tables -> encode_tables, the
     tables and the lengths coming back together) and a third value is returned: the tables, (n, 4, 272) uint8, or None.
     qtables (with quality None, see check_qtables): the whole batch is quantised with these tables instead of a quality's
-    (ops.jpeg_transform_tables, ops.jpeg_reconstruct_tables)."""
+    (ops.jpeg_transform_tables, ops.jpeg_reconstruct_tables).  restart_interval (MCUs, 0..65535): the segments carry a restart marker
+    behind every so many MCUs; the image is the same."""
     hs, vs = ops.jpeg_subsampling(subsampling)
     quality, qtables = _quality_or_tables(quality, qtables)
+    ri = ops.jpeg_restart_interval(restart_interval)
     n, h, w, _ = x.shape
-    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
+    ws = torch.empty(int(ops._lib.load().nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, ri) if ri else
+                         ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
     if qtables is None:
         coef = ops.jpeg_transform(x, quality, hs, vs, workspace=ws)
     else:
@@ -253,9 +266,9 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
         coef = ops.jpeg_transform_tables(x, qt, hs, vs, workspace=ws)[0]          # (check_qtables has seen every entry: no flag to read)
     segments = tables = None
     if want_bytes and optimize:
-        segments, tables = _device_codec_optimised(coef, n, h, w, hs, vs)
+        segments, tables = _device_codec_optimised(coef, n, h, w, hs, vs, ri)
     elif want_bytes:
-        segments = _device_codec_plain(coef, n, h, w, hs, vs, ws)
+        segments = _device_codec_plain(coef, n, h, w, hs, vs, ws, ri)
     image = None
     if want_image:
         image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if qtables is None else \
@@ -263,21 +276,24 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
     return (image, segments, tables) if optimize else (image, segments)
 
 
-def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtables=None):
+def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0):
     """The JPEG files of a batch (n,h,w,3) or one image (h,w,3), a list of bytes.  uint8 input is coded as it is; float input goes
     through the reference's conversion (x / 255 first if its maximum exceeds 1, then (255 x) truncated).  `optimize`: every file with
     Huffman tables of its own, the files libjpeg writes with optimize_coding (Pillow: optimize=True).  qtables (with quality None, see
-    check_qtables): the files libjpeg writes with these quantisation tables (Pillow: qtables=[...])."""
+    check_qtables): the files libjpeg writes with these quantisation tables (Pillow: qtables=[...]).  restart_interval (MCUs in
+    scan order, 0..65535): the files libjpeg writes with that restart interval (Pillow: restart_marker_blocks=) - a DRI segment and a
+    marker FFD0..FFD7 behind every so many MCUs that another follows; a whole number of MCU rows is rows * MCUs per row."""
     quality, qtables = _quality_or_tables(quality, qtables)
+    ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=True)
     if x.dim() == 3:
         x = x[None]
     if optimize:
-        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, optimize=True, qtables=qtables)
-        return [jpeg_header(x.shape[1], x.shape[2], quality, subsampling, huffman=t, qtables=qtables) + s + b'\xff\xd9'
+        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, optimize=True, qtables=qtables, restart_interval=ri)
+        return [jpeg_header(x.shape[1], x.shape[2], quality, subsampling, huffman=t, qtables=qtables, restart_interval=ri) + s + b'\xff\xd9'
                 for s, t in zip(segments, tables)]
-    _, segments = device_codec(x, quality, subsampling, want_image=False, qtables=qtables)
-    head = jpeg_header(x.shape[1], x.shape[2], quality, subsampling, qtables=qtables)
+    _, segments = device_codec(x, quality, subsampling, want_image=False, qtables=qtables, restart_interval=ri)
+    head = jpeg_header(x.shape[1], x.shape[2], quality, subsampling, qtables=qtables, restart_interval=ri)
     return [head + s + b'\xff\xd9' for s in segments]
 
 
@@ -287,25 +303,29 @@ def _optimised_header_bytes(tables, base=JPEG_HEADER_BYTES):
     return base - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)
 
 
-def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False, *, qtables=None):
+def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0):
     """Compress an image or a batch with the standard JPEG codec (jpeg_helpers.py:82-114).  (h,w,3) -> (float64 image, bytes);
     (n,h,w,3) -> (float32 batch, list of bytes).  `effective` counts from the first Huffman table on instead of the whole file.
     Every input, uint8 included, goes through the reference's conversion: x / 255 in float32 if the maximum exceeds 1, then
     (255 x) truncated - a byte k can come out as k - 1.  Values that numpy's cast would wrap are clamped to 0..255.
     `optimize`: the sizes are those of the files with optimised Huffman tables (encode_batch(optimize=True)); the image is the same.
     qtables (with jpeg_quality None, see check_qtables): the codec with these quantisation tables instead of a quality's; the sizes
-    are those of encode_batch(qtables=) - a third table costs 69 bytes of header, none of the effective size."""
+    are those of encode_batch(qtables=) - a third table costs 69 bytes of header, none of the effective size.
+    restart_interval: the sizes are those of encode_batch(restart_interval=), the DRI segment and the markers counted (both lie
+    behind the first Huffman table, so `effective` counts them too); the image is the same."""
     jpeg_quality, qtables = _quality_or_tables(jpeg_quality, qtables)
+    ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=False)
     if x.dim() not in (3, 4):
         raise ValueError('compress_batch needs an (h,w,3) image or an (n,h,w,3) batch')
     single = x.dim() == 3
-    head, dht = _header_bytes(qtables)
+    head, dht = _header_bytes(qtables, ri)
     if optimize:
-        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=True, qtables=qtables)
+        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=True, qtables=qtables,
+                                               restart_interval=ri)
         heads = _optimised_header_bytes(tables, head).tolist()
     else:
-        image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling, qtables=qtables)
+        image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling, qtables=qtables, restart_interval=ri)
         heads = [head] * len(segments)
     sizes = [hd + len(s) + 2 - (dht if effective else 0) for hd, s in zip(heads, segments)]
     image = image.cpu().numpy()
@@ -518,11 +538,12 @@ def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4',
 
 
 # ---- reading files ---------------------------------------------------------------------------------
-JPEGHeader = namedtuple('JPEGHeader', 'h w hs vs qtables huffman ecd_offset ecd_end')
+JPEGHeader = namedtuple('JPEGHeader', 'h w hs vs qtables huffman ecd_offset ecd_end restart_interval', defaults=(0,))
 JPEG_STATUS_BITS = OrderedDict([(1, 'marker inside the entropy-coded segment'), (2, 'invalid Huffman code'), (4, 'zig-zag index past 63'),
                                 (8, 'coefficient category out of range'), (16, 'bits needed beyond the end of the stream'),
                                 (32, 'fewer blocks than the scan has'), (64, 'DC value outside int16'),
-                                (128, 'Huffman table that is no prefix code'), (256, 'bad segment offsets')])
+                                (128, 'Huffman table that is no prefix code'), (256, 'bad segment offsets'),
+                                (512, 'restart markers missing, surplus or out of sequence')])
 _MAX_SIDE = 4096
 _SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless', 0xc5: 'differential sequential',
               0xc6: 'differential progressive', 0xc7: 'differential lossless', 0xc9: 'arithmetic-coded sequential',
@@ -530,19 +551,23 @@ _SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless'
               0xce: 'arithmetic-coded differential progressive', 0xcf: 'arithmetic-coded differential lossless'}
 
 
-def parse_header(data):
+def parse_header(data, allow_restart=False):
     """The header of a baseline JPEG file, read on the host without decoding: JPEGHeader(h, w, hs, vs, qtables (3, 64) uint16 in
     natural order per component, huffman = six (16 counts, symbols) pairs of bytes in the order Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC
-    as the DHT bodies have them, ecd_offset, ecd_end = the offset of the final FFD9).  Accepted: SOF0 with 8-bit samples, three
-    components in one interleaved scan, luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma, any 8-bit quantisation and any Huffman tables
-    in any assignment, no restart interval; APPn and COM are skipped.  Every other file raises ValueError naming the reason."""
+    as the DHT bodies have them, ecd_offset, ecd_end = the offset of the final FFD9, restart_interval).  Accepted: SOF0 with 8-bit
+    samples, three components in one interleaved scan, luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma, any 8-bit quantisation and any
+    Huffman tables in any assignment, no restart interval; APPn and COM are skipped.  Every other file raises ValueError naming the
+    reason.  allow_restart: a file with a restart interval (a DRI segment with a value above 0) is accepted
+    too - restart_interval is that value in MCUs, and the markers FFD0 .. FFD7 in the entropy-coded segment are stepped over (their
+    number and sequence are the decoder's to check, status bit 512).  Still refused: a restart marker in a file whose interval is 0,
+    and several DRI segments with different values (libjpeg would let the last one hold)."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise ValueError('JPEG data: bytes needed, got {}'.format(type(data).__name__))
     data = bytes(data)
     if data[:2] != b'\xff\xd8':
         raise ValueError('not a JPEG file: no SOI marker')
     order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
-    qt, huff, frame, pos = {}, {}, None, 2
+    qt, huff, frame, pos, restart = {}, {}, None, 2, None
     while True:
         if pos + 4 > len(data):
             raise ValueError('truncated file: no SOS marker')
@@ -607,8 +632,13 @@ def parse_header(data):
         elif marker == 0xdd:
             if len(body) != 2:
                 raise ValueError('malformed DRI segment')
-            if struct.unpack('>H', body)[0] != 0:
-                raise ValueError('restart interval {} (DRI): files with restart markers are not read'.format(struct.unpack('>H', body)[0]))
+            value = struct.unpack('>H', body)[0]
+            if value != 0 and not allow_restart:
+                raise ValueError('restart interval {} (DRI): files with restart markers are not read'.format(value))
+            if restart is not None and restart != value:
+                raise ValueError('several DRI segments with different restart intervals ({} and {}; libjpeg lets the last one hold): '
+                                 'not read'.format(restart, value))
+            restart = value
         elif marker == 0xda:
             break
         elif not (0xe0 <= marker <= 0xef or marker == 0xfe or marker == 0xdc or 0xf0 <= marker <= 0xfd):
@@ -651,26 +681,31 @@ def parse_header(data):
         if nxt == 0xd9:
             break
         if 0xd0 <= nxt <= 0xd7:
-            raise ValueError('restart marker FF{:02X} in the entropy-coded segment: files with restart markers are not read'.format(nxt))
+            if not allow_restart:
+                raise ValueError('restart marker FF{:02X} in the entropy-coded segment: files with restart markers are not read'.format(nxt))
+            if not restart:
+                raise ValueError('restart marker FF{:02X} in the entropy-coded segment of a file whose restart interval is 0'.format(nxt))
+            k += 2
+            continue
         if nxt in (0xda, 0xc4, 0xdb, 0xdd):
             raise ValueError('several scans: marker FF{:02X} behind the first entropy-coded segment'.format(nxt))
         raise ValueError('unexpected marker FF{:02X} in the entropy-coded segment'.format(nxt))
-    return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, tuple(tables), ecd_offset, k)
+    return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, tuple(tables), ecd_offset, k, restart or 0)
 
 
 def _status_text(status):
     return ' | '.join(text for bit, text in JPEG_STATUS_BITS.items() if status & bit)
 
 
-def _decode_groups(files, subseq_bits, device):
-    """Headers parsed, one upload, one nimg_jpeg_decode per group of equal (h, w, hs, vs).  Returns (headers, groups) with groups =
-    [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back."""
-    headers = [parse_header(f) for f in files]
+def _decode_groups(files, subseq_bits, device, allow_restart=False):
+    """Headers parsed, one upload, one nimg_jpeg_decode[_restart] per group of equal (h, w, hs, vs, restart interval).  Returns
+    (headers, groups) with groups = [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back."""
+    headers = [parse_header(f, allow_restart) for f in files]
     if not headers:
         raise ValueError('no files to decode')
     keys = OrderedDict()
     for i, hd in enumerate(headers):
-        keys.setdefault((hd.h, hd.w, hd.hs, hd.vs), []).append(i)
+        keys.setdefault((hd.h, hd.w, hd.hs, hd.vs, hd.restart_interval), []).append(i)
     dev = device if device is not None else default_device()
     order = [i for idx in keys.values() for i in idx]                    # the segments back to back, group after group
     blob = b''.join(files[i][headers[i].ecd_offset:headers[i].ecd_end] for i in order)
@@ -683,11 +718,12 @@ def _decode_groups(files, subseq_bits, device):
     ecd = torch.from_numpy(np.frombuffer(blob if blob else b'\0', np.uint8).copy()).to(dev)
     huff, qt = torch.from_numpy(huff).to(dev), torch.from_numpy(qt).to(dev)
     groups, j0, b0 = [], 0, 0
-    for (h, w, hs, vs), idx in keys.items():
+    for (h, w, hs, vs, ri), idx in keys.items():
         lengths = [headers[i].ecd_end - headers[i].ecd_offset for i in idx]
         off = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
         part = ecd[b0:b0 + max(sum(lengths), 1)]
-        coef, status, rounds = ops.jpeg_decode(part, off, huff[j0:j0 + len(idx)], h, w, hs, vs, subseq_bits=subseq_bits)
+        coef, status, rounds = ops.jpeg_decode(part, off, huff[j0:j0 + len(idx)], h, w, hs, vs, subseq_bits=subseq_bits,
+                                               restart_interval=ri)
         groups.append((idx, (h, w, hs, vs), coef, status, rounds, qt[j0:j0 + len(idx)]))
         j0, b0 = j0 + len(idx), b0 + sum(lengths)
     return headers, groups
@@ -701,16 +737,17 @@ def _raise_on_status(groups, status):
             [i for i, _ in bad], '; '.join('{}: status {} ({})'.format(i, s, _status_text(s)) for i, s in bad)))
 
 
-def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None):
+def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False):
     """Decode baseline JPEG files on the GPU: a list of bytes (or one bytes) -> (n,h,w,3) uint8, the array imageio.imread returns for
     each (libjpeg's islow inverse DCT and fancy up-sampling, bit for bit), or float32(byte) / 255 with as_float.  Files of different
     geometry give a list of (h,w,3) arrays in input order.  Any 8-bit quantisation and Huffman tables are read from each file
     (parse_header names what is refused).  The segments go up in one copy, every group of equal (h, w, sampling) takes one decode and
     one reconstruct call, status and images come down once; device_output keeps the images on the device.  Damaged data raises
-    ValueError naming the indices and the status bits (JPEG_STATUS_BITS)."""
+    ValueError naming the indices and the status bits (JPEG_STATUS_BITS).  allow_restart: files with a restart interval are read
+    too (parse_header); a group is then the files of equal geometry and interval, and every interval is decoded from its own start."""
     single = isinstance(files, (bytes, bytearray, memoryview))
     files = [bytes(files)] if single else [bytes(f) for f in files]
-    headers, groups = _decode_groups(files, subseq_bits, device)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart)
     images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
               for _, (h, w, hs, vs), coef, _, _, qt in groups]
     words = [len(g[0]) for g in groups]
@@ -735,42 +772,46 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     return result
 
 
-def decode_coefficients(files, device_output=False, subseq_bits=0, device=None):
+def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, *, allow_restart=False):
     """The quantised coefficients of baseline files of ONE geometry, as stored in the files: ((n, real blocks, 64) int16 in the layout
     of DESIGN.md section 4c - [Y | Cb | Cr][block row][block col][zig-zag] - and the (n, 3, 64) uint16 quantisation tables per
-    component in natural order; jpeg_qf_estimation(tables[i, c].reshape(8, 8), c) names the quality they came from)."""
+    component in natural order; jpeg_qf_estimation(tables[i, c].reshape(8, 8), c) names the quality they came from).
+    allow_restart: as decode_batch's; the files must then share their restart interval too."""
     single = isinstance(files, (bytes, bytearray, memoryview))
     files = [bytes(files)] if single else [bytes(f) for f in files]
-    headers, groups = _decode_groups(files, subseq_bits, device)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart)
     if len(groups) != 1:
-        raise ValueError('decode_coefficients needs files of one geometry, got {}'.format([g[1] for g in groups]))
+        raise ValueError('decode_coefficients needs files of one geometry{}, got {}'.format(
+            ' and restart interval' if allow_restart else '', [g[1] for g in groups]))
     _, _, coef, status, _, _ = groups[0]
     _raise_on_status(groups, [status.cpu().numpy()])
     return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
 
 
-def transcode_batch(files, optimize=True):
+def transcode_batch(files, optimize=True, *, allow_restart=False):
     """Baseline files written again with their coefficients and their quantisation tables untouched - a list of bytes in input order.
     The Huffman tables are the optimal ones of each image (what jpegtran -optimize does) or, with optimize=False, Annex K's.  Every
     file parse_header accepts is read; the header written is the one of encode_batch - JFIF APP0, two DQT segments where the file's Cb
     and Cr tables are equal, else three; APPn and COM segments are dropped.  Files go up in one copy, every group of equal (h, w,
     sampling) is decoded (nimg_jpeg_decode) and coded again on the device without a pixel being computed.  Damaged data raises as in
-    decode_batch."""
+    decode_batch.  allow_restart: files with a restart interval are read too, and every file keeps its interval - DRI segment and
+    markers are written again."""
     single = isinstance(files, (bytes, bytearray, memoryview))
     files = [bytes(files)] if single else [bytes(f) for f in files]
-    headers, groups = _decode_groups(files, 0, None)
+    headers, groups = _decode_groups(files, 0, None, allow_restart)
     _raise_on_status(groups, np.split(torch.cat([g[3] for g in groups]).cpu().numpy(), np.cumsum([len(g[0]) for g in groups])[:-1]))
     names = {v: k for k, v in ops.JPEG_SUBSAMPLING.items()}
     result = [None] * len(files)
     for idx, (h, w, hs, vs), coef, _, _, _ in groups:
+        ri = headers[idx[0]].restart_interval                               # the group's: files are grouped by it
         if optimize:
-            segments, tables = _device_codec_optimised(coef, len(idx), h, w, hs, vs)
+            segments, tables = _device_codec_optimised(coef, len(idx), h, w, hs, vs, ri)
         else:
-            segments, tables = _device_codec_plain(coef, len(idx), h, w, hs, vs), [None] * len(idx)
+            segments, tables = _device_codec_plain(coef, len(idx), h, w, hs, vs, restart_interval=ri), [None] * len(idx)
         for i, s, t in zip(idx, segments, tables):
             qt = headers[i].qtables
             qt = qt[:2] if np.array_equal(qt[1], qt[2]) else qt
-            result[i] = jpeg_header(h, w, None, names[(hs, vs)], huffman=t, qtables=qt) + s + b'\xff\xd9'
+            result[i] = jpeg_header(h, w, None, names[(hs, vs)], huffman=t, qtables=qt, restart_interval=ri) + s + b'\xff\xd9'
     return result
 
 

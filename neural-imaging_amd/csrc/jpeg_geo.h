@@ -1,5 +1,6 @@
 // The geometry of one batch of baseline JPEG images, for every unit of the JPEG family (jpegc.h, jpegopt.h, jpegd.h) and for the host
-// programs that run their sequential cores (tests/jpegopt_host.cpp, tests/jpegd_host.cpp): plain C++, nothing of HIP.
+// programs that run their sequential cores (tests/jpegopt_host.cpp, tests/jpegd_host.cpp): plain C++, nothing of HIP
+// but the attributes that let a kernel call the two restart-interval predicates.
 #pragma once
 
 struct JpegGeo {
@@ -9,7 +10,32 @@ struct JpegGeo {
     int my, mx, per;                   // MCU grid; blocks per MCU = hs * vs + 2
     int nbY, nbC, NB;                  // real blocks per image: Y, one chroma component, all three
     int SB;                            // blocks per image in scan order, dummies included
+    int ri;                            // restart interval in MCUs; 0 = none, which make_geo sets
 };
+
+#if defined(__HIPCC__)
+#define JPEG_GEO_HD __host__ __device__
+#else
+#define JPEG_GEO_HD
+#endif
+
+// MCU m begins a restart interval: the DC predictors are 0 there (always true of MCU 0)
+JPEG_GEO_HD inline bool jpeg_interval_start(const JpegGeo& g, int m) { return m == 0 || (g.ri > 0 && m % g.ri == 0); }
+
+// scan block s is the last of a restart interval that a marker follows (never the last block of the image)
+JPEG_GEO_HD inline bool jpeg_marker_follows(const JpegGeo& g, int s) {
+    return g.ri > 0 && s + 1 < g.SB && (s + 1) % (g.ri * g.per) == 0;
+}
+
+// restart markers of one image: one behind every interval but the last
+JPEG_GEO_HD inline int jpeg_markers(const JpegGeo& g) { return g.ri > 0 ? (g.my * g.mx + g.ri - 1) / g.ri - 1 : 0; }
+
+// the restart interval of a call into the geometry; false = outside 0..65535
+inline bool set_restart(JpegGeo* g, int restart_interval) {
+    if (restart_interval < 0 || restart_interval > 65535) return false;
+    g->ri = restart_interval;
+    return true;
+}
 
 inline bool make_geo(JpegGeo* g, int n, int h, int w, int hs, int vs) {
     if (n < 1 || n > 65535 || h < 1 || w < 1 || h > 4096 || w > 4096) return false;
@@ -22,5 +48,6 @@ inline bool make_geo(JpegGeo* g, int n, int h, int w, int hs, int vs) {
     g->per = hs * vs + 2;
     g->nbY = g->bhY * g->bwY; g->nbC = g->bhC * g->bwC; g->NB = g->nbY + 2 * g->nbC;
     g->SB = g->my * g->mx * g->per;
+    g->ri = 0;
     return (long)n * g->SB < 0x7fffffffL;
 }

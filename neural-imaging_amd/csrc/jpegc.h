@@ -7,6 +7,7 @@
 #pragma once
 #include "common.h"
 #include "jpeg_geo.h"
+#include "jpegrst.h"
 
 namespace {
 
@@ -26,7 +27,8 @@ struct Workspace {
     uint32_t* total;                   // [n] bits of an image before the final padding
     unsigned long long* dst;           // [n] first byte of an image's segment in the output
     uint32_t* raw;                     // [n][raw_words] the un-stuffed bits, MSB first in every word
-    unsigned raw_words;                // capacity of one image's slot of `raw`: SB blocks of block_bits bits, a multiple of 4 words
+    unsigned raw_words;                // capacity of one image's slot of `raw`: SB blocks of block_bits bits and the restart markers' 23
+                                       // each, a multiple of 4 words
     uint8_t* planes;                   // reconstruct: [n][Y | Cb | Cr] sample planes over the real blocks
     size_t bytes;
 };
@@ -36,7 +38,8 @@ struct Workspace {
 inline Workspace carve(const JpegGeo& g, void* base, int block_bits = BLOCK_BITS_MAX, int code_words = 0) {
     Workspace ws{};
     uint8_t* p = (uint8_t*)base;
-    const unsigned long words = ((unsigned long)g.SB * block_bits + 31) / 32 + 1;
+    // a restart marker (section 4i) costs its interval up to 7 bits of padding and its own 16
+    const unsigned long words = ((unsigned long)g.SB * block_bits + 23ul * (unsigned long)jpeg_markers(g) + 31) / 32 + 1;
     ws.raw_words = (unsigned)((words + 3) & ~3ul);
     if (code_words) { ws.codes = (uint32_t*)p; p += align256((size_t)g.n * code_words * 4); }
     else { ws.flag = (uint32_t*)p; p += 256; }
@@ -92,12 +95,27 @@ constexpr QTabs make_qtabs(int quality) {
 }
 
 // ---- scans over a workgroup of SCAN_THREADS ------------------------------------------------------------------------------
+// What a scan combines is a + b = "a, then b": integers, and jpegrst.h's bit-offset functions of a scan with restart markers.
+__device__ __forceinline__ BitFn lane_up(const BitFn& v, int o) {
+    return BitFn{__shfl_up(v.a, o, 64), __shfl_up(v.b, o, 64), __shfl_up(v.round, o, 64)};
+}
+template <typename T>
+__device__ __forceinline__ T lane_up(T v, int o) { return __shfl_up(v, o, 64); }
+
+// the exclusive scan of a wave from its inclusive one: integers have an inverse, functions take their neighbour's
+template <typename T>
+__device__ __forceinline__ T wave_excl_of(T incl, T v, int) { return incl - v; }
+__device__ __forceinline__ BitFn wave_excl_of(const BitFn& incl, const BitFn&, int lane) {
+    const BitFn u = lane_up(incl, 1);
+    return lane ? u : BitFn{};
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_incl_scan(T v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-        const T u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
+        const T u = lane_up(v, o);
+        if (lane >= o) v = u + v;
     }
     return v;
 }
@@ -110,15 +128,15 @@ __device__ __forceinline__ T block_excl_scan(T v, T* wtot, T& total) {
     __syncthreads();                                   // the previous round's readers are done with wtot
     if (lane == 63) wtot[wv] = incl;
     __syncthreads();
-    T run = incl - v, tot = 0;
+    T before{}, tot{};
 #pragma unroll
     for (int k = 0; k < NT / 64; ++k) {
         const T s = wtot[k];
-        if (k < wv) run += s;
-        tot += s;
+        if (k < wv) before = before + s;
+        tot = tot + s;
     }
     total = tot;
-    return run;
+    return before + wave_excl_of(incl, v, lane);
 }
 
 // ---- transform --------------------------------------------------------------------------------------------------------
@@ -357,6 +375,14 @@ struct BitSink {
     }
 };
 
+// what an emitter adds behind scan block s, whose bits began at bit `begin`: behind the last block of the image, and of a restart
+// interval that a marker follows, the byte is filled up with 1-bits
+template <class Sink>
+__device__ __forceinline__ void pad_interval(Sink& sink, const JpegGeo& g, int s, uint32_t begin) {
+    const int pad = jpegrst_pad_bits(g, s, begin + sink.count);
+    if (pad) sink.put((1u << pad) - 1u, pad);
+}
+
 inline bool grid_ok(long items, int per_block) { return (items + per_block - 1) / per_block <= 0x7fffffffL; }
 
 }  // namespace
@@ -368,9 +394,12 @@ NIMG_HIDDEN int nimg_internal_jpeg_above_one(const float* x, long count, uint32_
 // the sample planes of g.n images (as the inverse DCT leaves them) -> y (n,h,w,3): float32 k / 255, or the bytes themselves if u8
 NIMG_HIDDEN int nimg_internal_jpeg_colour(uint8_t* planes, void* y, bool u8, const JpegGeo& g, hipStream_t stream);
 // the coder's passes around its bit-length and its emit pass (a raw buffer of raw_words words per image):
-// off[n][SB] bit lengths -> offsets in place, total[n]; the words of raw the bits will be OR-ed into zeroed
-NIMG_HIDDEN int nimg_internal_jpeg_offsets(uint32_t* off, uint32_t* total, uint32_t* raw, int n, int SB, unsigned raw_words,
+// off[n][SB] bit lengths -> offsets in place, total[n]; the words of raw the bits will be OR-ed into zeroed.  With g.ri the end of an
+// interval that a marker follows is rounded up to a byte and 16 bits are left free behind it.
+NIMG_HIDDEN int nimg_internal_jpeg_offsets(uint32_t* off, uint32_t* total, uint32_t* raw, const JpegGeo& g, unsigned raw_words,
                                            hipStream_t stream);
-// raw -> lengths[n], dst[n], and the stuffed bytes of all images back to back in out, none at or beyond capacity
-NIMG_HIDDEN int nimg_internal_jpeg_pack(const uint32_t* raw, const uint32_t* total, uint32_t* lengths, unsigned long long* dst, uint8_t* out,
-                                        size_t capacity, int n, unsigned raw_words, hipStream_t stream);
+// raw -> lengths[n], dst[n], and the stuffed bytes of all images back to back in out, none at or beyond capacity.  With g.ri the
+// 16 free bits in front of every interval but the first (found through off) go out as FF D0 .. FF D7, unstuffed.
+NIMG_HIDDEN int nimg_internal_jpeg_pack(const uint32_t* raw, const uint32_t* total, const uint32_t* off, uint32_t* lengths,
+                                        unsigned long long* dst, uint8_t* out, size_t capacity, const JpegGeo& g, unsigned raw_words,
+                                        hipStream_t stream);

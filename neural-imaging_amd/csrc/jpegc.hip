@@ -6,6 +6,9 @@
 //                  bit length of every block in scan order (dummy blocks included) | exclusive scan per image | zero the words
 //                  that will be OR-ed into | every block places its bits at its offset (last block: the 1-padding) |
 //                  count the FF bytes per image | scan the segment lengths | scatter the bytes with their 00 stuffing
+//                with a restart interval (nimg_jpeg_encode_restart, section 4i) the same passes: the predictors restart in the
+//                block walk, the scan rounds an interval's end up to a byte and leaves 16 bits free, the emitter of the interval's
+//                last block pads, and the scatter writes FF D0 .. D7 where those 16 bits stand
 //   reconstruct  coefficients -> float32 NHWC (dequantise, jidctint inverse DCT, fancy chroma up-sampling, colour, k / 255)
 // Nothing here loops over images or blocks on the host, and nothing is read back: the caller synchronises once for `lengths`.
 // The transform and inverse-DCT kernels and the bit sink are jpegc.h's, instantiated here for one quality per batch; the scan-order
@@ -82,20 +85,32 @@ __global__ void __launch_bounds__(256) jpeg_bitlen_kernel(const int16_t* __restr
     len[t] = sink.count;
 }
 
-// one workgroup per image: lengths -> offsets in place, total[image] = the bits before the padding
-__global__ void __launch_bounds__(SCAN_THREADS) jpeg_bitscan_kernel(uint32_t* __restrict__ off, uint32_t* __restrict__ total, int SB) {
-    __shared__ uint32_t wtot[SCAN_THREADS / 64];
+// one workgroup per image: lengths -> offsets in place, total[image] = the bits before the last padding.  T = uint32_t: a plain sum;
+// T = BitFn (g.ri > 0): a block that a restart marker follows also fills its byte up and leaves 16 bits free
+template <typename T>
+__device__ __forceinline__ T scan_item(uint32_t len, const JpegGeo& g, int s);
+template <>
+__device__ __forceinline__ uint32_t scan_item<uint32_t>(uint32_t len, const JpegGeo&, int) { return len; }
+template <>
+__device__ __forceinline__ BitFn scan_item<BitFn>(uint32_t len, const JpegGeo& g, int s) { return jpegrst_block_fn(len, g, s); }
+__device__ __forceinline__ uint32_t scan_value(uint32_t v) { return v; }
+__device__ __forceinline__ uint32_t scan_value(const BitFn& f) { return f.at(0u); }
+
+template <typename T>
+__global__ void __launch_bounds__(SCAN_THREADS) jpeg_bitscan_kernel(uint32_t* __restrict__ off, uint32_t* __restrict__ total, JpegGeo g) {
+    __shared__ T wtot[SCAN_THREADS / 64];
+    const int SB = g.SB;
     uint32_t* o = off + (long)blockIdx.x * SB;
-    uint32_t carry = 0;
+    T carry{};
     for (int b = 0; b < SB; b += SCAN_THREADS) {
         const int j = b + threadIdx.x;
-        const uint32_t v = j < SB ? o[j] : 0u;
-        uint32_t sum;
-        const uint32_t ex = block_excl_scan(v, wtot, sum);
-        if (j < SB) o[j] = carry + ex;
-        carry += sum;
+        const T v = j < SB ? scan_item<T>(o[j], g, j) : T{};
+        T sum;
+        const T ex = block_excl_scan(v, wtot, sum);
+        if (j < SB) o[j] = scan_value(carry + ex);
+        carry = carry + sum;
     }
-    if (threadIdx.x == 0) total[blockIdx.x] = carry;
+    if (threadIdx.x == 0) total[blockIdx.x] = scan_value(carry);
 }
 
 // zeroes the words the bits of an image will be OR-ed into (nothing beyond them, and never beyond the image's slot)
@@ -108,18 +123,14 @@ __global__ void __launch_bounds__(256) jpeg_zero_kernel(uint32_t* __restrict__ r
 }
 
 __global__ void __launch_bounds__(256) jpeg_emit_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ off,
-                                                        const uint32_t* __restrict__ total, uint32_t* __restrict__ raw, JpegGeo g,
-                                                        unsigned raw_words) {
+                                                        uint32_t* __restrict__ raw, JpegGeo g, unsigned raw_words) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)g.n * g.SB) return;
     const int img = (int)(t / g.SB), s = (int)(t - (long)img * g.SB);
     HuffSink<true> sink;
     sink.init(raw + (size_t)img * raw_words, raw_words, off[t]);
     jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
-    if (s == g.SB - 1) {                                 // the last byte is filled up with 1-bits
-        const int pad = (int)((0u - total[img]) & 7u);
-        if (pad) sink.put((1u << pad) - 1u, pad);
-    }
+    pad_interval(sink, g, s, off[t]);
     sink.finish();
 }
 
@@ -155,13 +166,17 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpeg_imgscan_kernel(const uint32
     }
 }
 
-// one workgroup per image: its bytes to dst[image] + position + FF bytes before it, every FF followed by 00
+// one workgroup per image: its bytes to dst[image] + position + FF bytes before it, every FF followed by 00.  RST: the bytes left
+// free for the restart markers are zero in raw - counted and placed like data, never stuffed - and go out as the markers
+template <bool RST>
 __global__ void __launch_bounds__(SCAN_THREADS) jpeg_stuff_kernel(const uint32_t* __restrict__ raw, const uint32_t* __restrict__ total,
+                                                                  const uint32_t* __restrict__ off,
                                                                   const unsigned long long* __restrict__ dst, uint8_t* __restrict__ out,
-                                                                  unsigned long long capacity, unsigned raw_words) {
+                                                                  unsigned long long capacity, JpegGeo g, unsigned raw_words) {
     __shared__ uint32_t wtot[SCAN_THREADS / 64];
     const unsigned img = blockIdx.x, nbytes = (total[img] + 7u) / 8u, nwords = min(raw_words, (nbytes + 3u) / 4u);
     const uint32_t* r = raw + (size_t)img * raw_words;
+    const uint32_t* o = off + (size_t)img * g.SB;
     const unsigned long long d0 = dst[img];
     uint32_t carry = 0;
     for (unsigned b = 0; b < nwords; b += SCAN_THREADS) {
@@ -171,13 +186,15 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpeg_stuff_kernel(const uint32_t
         uint32_t before = carry + block_excl_scan((uint32_t)ff_bytes(word), wtot, sum);
         carry += sum;
         if (j < nwords) {
+            const int k0 = RST ? jpegrst_first_marker(o, g, 4u * j) : 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const unsigned pos = 4u * j + (unsigned)q;
                 const uint32_t byte = (word >> (24 - 8 * q)) & 0xffu;
                 if (pos < nbytes) {
                     const unsigned long long at = d0 + pos + before;
-                    if (at < capacity) out[at] = (uint8_t)byte;
+                    const uint32_t mark = RST ? jpegrst_marker_byte(o, g, k0, pos) : 0u;
+                    if (at < capacity) out[at] = (uint8_t)(mark ? mark : byte);
                     if (byte == 0xffu) {
                         if (at + 1 < capacity) out[at + 1] = 0;
                         ++before;
@@ -244,10 +261,16 @@ int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, i
     return NIMG_OK;
 }
 
-int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, uint8_t* out, size_t out_capacity, uint32_t* lengths,
-                     void* workspace, size_t workspace_bytes, void* stream) {
+size_t nimg_jpeg_encode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval) {
     JpegGeo g;
-    if (!coef || !out || !lengths || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    if (!make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return 0;
+    return carve(g, nullptr).bytes;
+}
+
+int nimg_jpeg_encode_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint8_t* out,
+                             size_t out_capacity, uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream) {
+    JpegGeo g;
+    if (!coef || !out || !lengths || !workspace || !make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -255,12 +278,16 @@ int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, u
     const unsigned grid = (unsigned)((blocks + 255) / 256);
     hipLaunchKernelGGL(jpeg_bitlen_kernel, dim3(grid), dim3(256), 0, st, coef, ws.off, g);
     NIMG_CHECK_LAUNCH();
-    const int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, n, g.SB, ws.raw_words, st);
+    const int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, g, ws.raw_words, st);
     if (rc != NIMG_OK) return rc;
-    hipLaunchKernelGGL(jpeg_emit_kernel, dim3(grid), dim3(256), 0, st, coef, (const uint32_t*)ws.off, (const uint32_t*)ws.total, ws.raw,
-                       g, ws.raw_words);
+    hipLaunchKernelGGL(jpeg_emit_kernel, dim3(grid), dim3(256), 0, st, coef, (const uint32_t*)ws.off, ws.raw, g, ws.raw_words);
     NIMG_CHECK_LAUNCH();
-    return nimg_internal_jpeg_pack(ws.raw, ws.total, lengths, ws.dst, out, out_capacity, n, ws.raw_words, st);
+    return nimg_internal_jpeg_pack(ws.raw, ws.total, ws.off, lengths, ws.dst, out, out_capacity, g, ws.raw_words, st);
+}
+
+int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, uint8_t* out, size_t out_capacity, uint32_t* lengths,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    return nimg_jpeg_encode_restart(coef, n, h, w, hs, vs, 0, out, out_capacity, lengths, workspace, workspace_bytes, stream);
 }
 
 int nimg_jpeg_reconstruct(const int16_t* coef, int n, int h, int w, int hs, int vs, int quality, float* y, void* workspace,
@@ -298,23 +325,29 @@ int nimg_internal_jpeg_colour(uint8_t* planes, void* y, bool u8, const JpegGeo& 
     return NIMG_OK;
 }
 
-int nimg_internal_jpeg_offsets(uint32_t* off, uint32_t* total, uint32_t* raw, int n, int SB, unsigned raw_words, hipStream_t stream) {
-    hipLaunchKernelGGL(jpeg_bitscan_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, off, total, SB);
+int nimg_internal_jpeg_offsets(uint32_t* off, uint32_t* total, uint32_t* raw, const JpegGeo& g, unsigned raw_words, hipStream_t stream) {
+    if (g.ri) hipLaunchKernelGGL(jpeg_bitscan_kernel<BitFn>, dim3((unsigned)g.n), dim3(SCAN_THREADS), 0, stream, off, total, g);
+    else hipLaunchKernelGGL(jpeg_bitscan_kernel<uint32_t>, dim3((unsigned)g.n), dim3(SCAN_THREADS), 0, stream, off, total, g);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_zero_kernel, dim3((raw_words / 4 + 255) / 256, (unsigned)n), dim3(256), 0, stream, raw, (const uint32_t*)total,
+    hipLaunchKernelGGL(jpeg_zero_kernel, dim3((raw_words / 4 + 255) / 256, (unsigned)g.n), dim3(256), 0, stream, raw, (const uint32_t*)total,
                        raw_words);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 
-int nimg_internal_jpeg_pack(const uint32_t* raw, const uint32_t* total, uint32_t* lengths, unsigned long long* dst, uint8_t* out,
-                            size_t capacity, int n, unsigned raw_words, hipStream_t stream) {
+int nimg_internal_jpeg_pack(const uint32_t* raw, const uint32_t* total, const uint32_t* off, uint32_t* lengths, unsigned long long* dst,
+                            uint8_t* out, size_t capacity, const JpegGeo& g, unsigned raw_words, hipStream_t stream) {
+    const int n = g.n;
     hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, raw, total, lengths, raw_words);
     NIMG_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_imgscan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, (const uint32_t*)lengths, dst, n);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, raw, total, (const unsigned long long*)dst, out,
-                       (unsigned long long)capacity, raw_words);
+    if (g.ri)
+        hipLaunchKernelGGL(jpeg_stuff_kernel<true>, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, raw, total, off,
+                           (const unsigned long long*)dst, out, (unsigned long long)capacity, g, raw_words);
+    else
+        hipLaunchKernelGGL(jpeg_stuff_kernel<false>, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, raw, total, off,
+                           (const unsigned long long*)dst, out, (unsigned long long)capacity, g, raw_words);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }

@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(256) jpeg_bitlen_tables_kernel(const int16_t* 
 }
 
 __global__ void __launch_bounds__(256) jpeg_emit_tables_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ codes,
-                                                               const uint32_t* __restrict__ off, const uint32_t* __restrict__ total,
+                                                               const uint32_t* __restrict__ off,
                                                                const uint32_t* __restrict__ status, uint32_t* __restrict__ raw,
                                                                JpegGeo g, unsigned raw_words) {
     __shared__ uint32_t s_codes[JPEGOPT_CODE_WORDS];
@@ -203,10 +203,7 @@ __global__ void __launch_bounds__(256) jpeg_emit_tables_kernel(const int16_t* __
     sink.codes = s_codes;
     sink.init(raw + (size_t)img * raw_words, raw_words, off[(size_t)img * g.SB + s]);
     jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
-    if (s == g.SB - 1) {                                   // the last byte is filled up with 1-bits
-        const int pad = (int)((0u - total[img]) & 7u);
-        if (pad) sink.put((1u << pad) - 1u, pad);
-    }
+    pad_interval(sink, g, s, off[(size_t)img * g.SB + s]);
     sink.finish();
 }
 
@@ -214,14 +211,19 @@ __global__ void __launch_bounds__(256) jpeg_emit_tables_kernel(const int16_t* __
 
 extern "C" {
 
-int nimg_jpeg_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, uint32_t* hist, void* stream) {
+int nimg_jpeg_histogram_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint32_t* hist,
+                                void* stream) {
     JpegGeo g;
-    if (!coef || !hist || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    if (!coef || !hist || !make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return NIMG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(hist, 0, (size_t)n * 4 * JPEGOPT_HIST * 4, st) != hipSuccess) return NIMG_ERR_LAUNCH;
     hipLaunchKernelGGL(jpeg_histogram_kernel, dim3((unsigned)((g.SB + 255) / 256), (unsigned)n), dim3(256), 0, st, coef, hist, g);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
+}
+
+int nimg_jpeg_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, uint32_t* hist, void* stream) {
+    return nimg_jpeg_histogram_restart(coef, n, h, w, hs, vs, 0, hist, stream);
 }
 
 int nimg_jpeg_optimal_tables(const uint32_t* hist, int n_tables, uint8_t* tables, uint32_t* status, void* stream) {
@@ -232,17 +234,22 @@ int nimg_jpeg_optimal_tables(const uint32_t* hist, int n_tables, uint8_t* tables
     return NIMG_OK;
 }
 
-size_t nimg_jpeg_encode_tables_workspace_bytes(int n, int h, int w, int hs, int vs) {
+size_t nimg_jpeg_encode_tables_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval) {
     JpegGeo g;
-    if (!make_geo(&g, n, h, w, hs, vs)) return 0;
+    if (!make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return 0;
     return carve(g, nullptr, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS).bytes;
 }
 
-int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint8_t* tables, uint8_t* out,
-                            size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
-                            void* stream) {
+size_t nimg_jpeg_encode_tables_workspace_bytes(int n, int h, int w, int hs, int vs) {
+    return nimg_jpeg_encode_tables_restart_workspace_bytes(n, h, w, hs, vs, 0);
+}
+
+int nimg_jpeg_encode_tables_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, const uint8_t* tables,
+                                    uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
     JpegGeo g;
-    if (!coef || !tables || !out || !lengths || !status || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    if (!coef || !tables || !out || !lengths || !status || !workspace || !make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval))
+        return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -251,12 +258,19 @@ int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, in
     NIMG_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_bitlen_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, ws.off, status, g);
     NIMG_CHECK_LAUNCH();
-    int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, n, g.SB, ws.raw_words, st);
+    int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, g, ws.raw_words, st);
     if (rc != NIMG_OK) return rc;
     hipLaunchKernelGGL(jpeg_emit_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, (const uint32_t*)ws.off,
-                       (const uint32_t*)ws.total, (const uint32_t*)status, ws.raw, g, ws.raw_words);
+                       (const uint32_t*)status, ws.raw, g, ws.raw_words);
     NIMG_CHECK_LAUNCH();
-    return nimg_internal_jpeg_pack(ws.raw, ws.total, lengths, ws.dst, out, out_capacity, n, ws.raw_words, st);
+    return nimg_internal_jpeg_pack(ws.raw, ws.total, ws.off, lengths, ws.dst, out, out_capacity, g, ws.raw_words, st);
+}
+
+int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint8_t* tables, uint8_t* out,
+                            size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    return nimg_jpeg_encode_tables_restart(coef, n, h, w, hs, vs, 0, tables, out, out_capacity, lengths, status, workspace, workspace_bytes,
+                                           stream);
 }
 
 }  // extern "C"

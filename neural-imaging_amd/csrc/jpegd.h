@@ -24,6 +24,7 @@
 #define JPEGD_ST_DC 64u           // a DC value outside int16
 #define JPEGD_ST_TABLE 128u       // DHT counts that are no prefix code or name more than 256 symbols
 #define JPEGD_ST_OFFSETS 256u     // segment offsets that descend or exceed what the workspace was sized for
+#define JPEGD_ST_RESTART 512u     // restart markers missing, surplus or out of sequence (files with a restart interval, section 4i)
 
 #define JPEGD_INVALID 0xffffffffu        // JpegdState::p of a decoder that met an invalid symbol
 #define JPEGD_BLOCK_BITS_MAX 1728        // 64 x (16 + 11): no table makes a block longer
@@ -108,14 +109,16 @@ JPEGD_HD inline long jpegd_place(const JpegGeo& g, uint32_t b, int& comp) {
 
 // Decodes from state `s` until a symbol starts at or beyond `limit` (the caller passes min(next boundary, total_bits)) and leaves
 // the exit state in `s`, the number of blocks begun (DC symbols met) in `begun`.  An invalid code, a category out of range and a
-// symbol that runs beyond total_bits all end the run with s.p = JPEGD_INVALID.
+// symbol that runs beyond total_bits all end the run with s.p = JPEGD_INVALID.  The run belongs to one restart interval (the whole
+// scan where the file has none): total_bits is the interval's end in the stream, [block_begin, block_end) its scan-order blocks.
 // WRITE: `block` is the scan-order index of the first block begun here (the one in progress at entry is block - 1).  AC values go to
 // coef (the image's tensor; real blocks only), DC differences to dcdiff[scan-order block], errors to `status`; the run ends after
-// block SB - 1, and nothing at or beyond SB is stored.  Not WRITE: coef, dcdiff and status are not touched.
+// block block_end - 1 - what follows in the interval is skipped, as libjpeg skips it - and nothing outside the interval's blocks is
+// stored.  Not WRITE: coef, dcdiff and status are not touched.
 template <bool WRITE>
-JPEGD_HD inline void jpegd_run(const uint32_t* bits, uint32_t nwords, uint32_t total_bits, uint32_t limit, const JpegdTable* tabs,
-                               const JpegGeo& g, JpegdState& s, uint32_t& begun, uint32_t block, int16_t* coef, int32_t* dcdiff,
-                               uint32_t& status) {
+JPEGD_HD inline void jpegd_run_interval(const uint32_t* bits, uint32_t nwords, uint32_t total_bits, uint32_t limit, const JpegdTable* tabs,
+                                        const JpegGeo& g, JpegdState& s, uint32_t& begun, uint32_t block, uint32_t block_begin,
+                                        uint32_t block_end, int16_t* coef, int32_t* dcdiff, uint32_t& status) {
     begun = 0;
     uint32_t p = s.p;
     if (p == JPEGD_INVALID) return;
@@ -125,14 +128,14 @@ JPEGD_HD inline void jpegd_run(const uint32_t* bits, uint32_t nwords, uint32_t t
     uint32_t cur = block - (z ? 1u : 0u);              // WRITE: the block in progress, or the one the next DC code begins
     int16_t* dst = nullptr;                            // WRITE: the block in progress, if it is real
     if (WRITE && z) {
-        if (block == 0 || cur >= (uint32_t)g.SB) return;
+        if (block <= block_begin || cur >= block_end) return;
         int comp;
         const long at = jpegd_place(g, cur, comp);
         if (at >= 0) dst = coef + at * 64;
     }
     uint32_t fail = 0;
     while (p < limit) {
-        if (WRITE && z == 0 && cur >= (uint32_t)g.SB) break;
+        if (WRITE && z == 0 && cur >= block_end) break;
         const int c = m < ny ? 0 : m - ny + 1;
         const uint32_t window = jpegd_peek(bits, nwords, p);
         int len;
@@ -182,4 +185,62 @@ JPEGD_HD inline void jpegd_run(const uint32_t* bits, uint32_t nwords, uint32_t t
         return;
     }
     s.p = p; s.mz = (uint32_t)m << 8 | (uint32_t)z;
+}
+
+// the run of a file without restart markers: one interval, the whole scan
+template <bool WRITE>
+JPEGD_HD inline void jpegd_run(const uint32_t* bits, uint32_t nwords, uint32_t total_bits, uint32_t limit, const JpegdTable* tabs,
+                               const JpegGeo& g, JpegdState& s, uint32_t& begun, uint32_t block, int16_t* coef, int32_t* dcdiff,
+                               uint32_t& status) {
+    jpegd_run_interval<WRITE>(bits, nwords, total_bits, limit, tabs, g, s, begun, block, 0u, (uint32_t)g.SB, coef, dcdiff, status);
+}
+
+// ---- restart intervals -----------------------------------------------------------------------------
+// An image with g.ri > 0 has K = jpegd_intervals(g) intervals and K - 1 markers.  Its interval table ibit[K + 1] holds the bit at
+// which every interval begins in the un-stuffed stream, markers taken out; ibit[K] = the end of the stream.  Its subsequence table
+// sub0[K + 1] holds the index of every interval's first subsequence; sub0[K] = the number of subsequences.
+JPEGD_HD inline uint32_t jpegd_intervals(const JpegGeo& g) {
+    return g.ri > 0 ? (uint32_t)((g.my * g.mx + g.ri - 1) / g.ri) : 1u;
+}
+
+// the marker FF `second` met as the idx-th of the image (from 0) after `kept` bytes of un-stuffed data: the start of interval
+// idx + 1.  Returns JPEGD_ST_RESTART for a marker out of sequence or beyond the K - 1 the image has, else 0.
+JPEGD_HD inline uint32_t jpegd_marker(uint32_t idx, uint32_t second, uint32_t kept, uint32_t K, uint32_t* ibit) {
+    if (idx + 1u >= K) return JPEGD_ST_RESTART;
+    ibit[idx + 1u] = 8u * kept;
+    return (second & 7u) == (idx & 7u) ? 0u : JPEGD_ST_RESTART;
+}
+
+// subsequences of an interval of `len` bits: at least one, so that every interval has a first one
+JPEGD_HD inline uint32_t jpegd_interval_subs(uint32_t len, uint32_t sb) { return len == 0 ? 1u : (len + sb - 1u) / sb; }
+
+// the interval of subsequence i: the last k with sub0[k] <= i (i < sub0[K])
+JPEGD_HD inline uint32_t jpegd_interval_of(const uint32_t* sub0, uint32_t K, uint32_t i) {
+    uint32_t lo = 0, hi = K;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sub0[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// where subsequence i of an image with restart intervals stands
+struct JpegdSpan {
+    uint32_t k, j;                     // its interval, and its index inside it: 0 = its state at entry is known, (start, m 0, z 0)
+    uint32_t start, limit, end;        // its first bit, the bit its last symbol starts before, the interval's end
+    uint32_t block_begin, block_end;   // the interval's scan-order blocks
+};
+JPEGD_HD inline JpegdSpan jpegd_span(const JpegGeo& g, const uint32_t* ibit, const uint32_t* sub0, uint32_t K, uint32_t sb, uint32_t i) {
+    JpegdSpan sp;
+    sp.k = jpegd_interval_of(sub0, K, i);
+    sp.j = i - sub0[sp.k];
+    sp.end = ibit[sp.k + 1u];
+    const uint32_t first = ibit[sp.k], room = sp.end - first;
+    sp.start = sp.j < (room + sb - 1u) / sb ? first + sp.j * sb : sp.end;              // (never past the end, whatever the tables say)
+    sp.limit = sp.end - sp.start > sb ? sp.start + sb : sp.end;
+    const uint32_t per = g.ri > 0 ? (uint32_t)g.ri * (uint32_t)g.per : (uint32_t)g.SB;          // without an interval: the whole scan
+    sp.block_begin = sp.k * per;
+    sp.block_end = sp.block_begin + per < (uint32_t)g.SB ? sp.block_begin + per : (uint32_t)g.SB;
+    return sp;
 }

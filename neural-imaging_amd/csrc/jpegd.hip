@@ -14,6 +14,10 @@
 // of the round before (thread i reads i - 1 before any thread of this round has written it): the number of rounds is the same
 // for every chunking, on the host as on the device.
 // The sequential core - tables, block placement, the decode of one subsequence - is jpegd.h, shared with a host program.
+// Files with a restart interval (nimg_jpeg_decode_restart) go through the same kernels, instantiated with
+// RST: prepare also takes the markers FF D0 .. D7 out, checks their sequence and records where every interval begins; the
+// subsequences are cut per interval, the first of each starts from the known state (interval start, m 0, z 0) and is never decoded
+// again, a run ends with its interval's blocks, and the DC sums restart with every interval.
 #include "jpegc.h"
 #include "jpegd.h"
 
@@ -33,8 +37,15 @@ struct DLayout {
     uint32_t* raw;               // un-stuffed streams; image i from word (ecd_off[i] >> 2) + 2 i, (len + 3) / 4 + 1 words
     JpegdState* exit;            // exit states; image i from slot 8 ecd_off[i] / subseq_bits + i
     uint32_t* cnt;               // blocks begun, then (in place) the index of the first block begun; slots as `exit`
+    uint32_t* ibit;              // restart intervals only: [n][K + 1] the bit every interval begins at (jpegd.h)
+    uint32_t* sub0;              // restart intervals only: [n][K + 1] the first subsequence of every interval
+    uint32_t* maxsub;            // restart intervals only: [n] the subsequences of the image's longest interval
     size_t raw_words, slots, bytes;
 };
+
+// slots an image has beyond 8 * its bytes / subseq_bits: one for the partial subsequence at its end - with restart intervals one
+// per interval, and one more because an interval has at least one
+inline uint32_t slot_extra(const JpegGeo& g) { return g.ri ? jpegd_intervals(g) + 1u : 1u; }
 
 DLayout carve_d(const JpegGeo& g, uint64_t ecd_bytes, uint32_t sb, void* base) {
     DLayout d;
@@ -45,9 +56,16 @@ DLayout carve_d(const JpegGeo& g, uint64_t ecd_bytes, uint32_t sb, void* base) {
     d.dcdiff = (int32_t*)p; p += align256((size_t)g.n * g.SB * 4);
     d.raw_words = (size_t)(ecd_bytes / 4) + 2 * (size_t)g.n + 2;
     d.raw = (uint32_t*)p; p += align256(d.raw_words * 4);
-    d.slots = (size_t)(8 * ecd_bytes / sb) + (size_t)g.n + 1;
+    d.slots = (size_t)(8 * ecd_bytes / sb) + (size_t)g.n * slot_extra(g) + 1;
     d.exit = (JpegdState*)p; p += align256(d.slots * sizeof(JpegdState));
     d.cnt = (uint32_t*)p; p += align256(d.slots * 4);
+    d.ibit = d.sub0 = d.maxsub = nullptr;
+    if (g.ri) {
+        const size_t table = align256((size_t)g.n * (jpegd_intervals(g) + 1u) * 4);
+        d.ibit = (uint32_t*)p; p += table;
+        d.sub0 = (uint32_t*)p; p += table;
+        d.maxsub = (uint32_t*)p; p += align256((size_t)g.n * 4);
+    }
     d.bytes = (size_t)(p - (uint8_t*)base);
     return d;
 }
@@ -64,6 +82,8 @@ struct DArgs {
     const uint8_t* huffman;
     uint64_t ecd_cap;            // the segment bytes the workspace was sized for
     uint32_t sb;
+    uint32_t K;                  // restart intervals of an image (1 without a restart interval)
+    uint32_t extra;              // slot_extra
     JpegGeo g;
     int16_t* coef;
     uint32_t* status;
@@ -71,13 +91,24 @@ struct DArgs {
 };
 
 __device__ __forceinline__ size_t raw_start(uint64_t off, int img) { return (size_t)(off >> 2) + 2 * (size_t)img; }
-__device__ __forceinline__ size_t slot_start(uint64_t off, uint32_t sb, int img) { return (size_t)(8 * off / sb) + (size_t)img; }
+__device__ __forceinline__ size_t slot_start(const DArgs& a, uint64_t off, int img) {
+    return (size_t)(8 * off / a.sb) + (size_t)img * a.extra;
+}
 
 // ---- prepare ------------------------------------------------------------------------------------------------------------
+// what the un-stuffing scan sums: the bytes kept - with restart intervals also the markers met, in the upper half
+template <bool RST> struct PrepSum { typedef uint32_t type; };
+template <> struct PrepSum<true> { typedef unsigned long long type; };
+
+template <bool RST>
 __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DLayout d) {
-    __shared__ uint32_t wtot[SCAN_THREADS / 64];
+    typedef typename PrepSum<RST>::type Sum;
+    __shared__ Sum wtot[SCAN_THREADS / 64];
+    __shared__ uint32_t s_max;
     const int img = blockIdx.x, tid = threadIdx.x;
     const uint64_t o0 = a.off[img], o1 = a.off[img + 1];
+    uint32_t* ibit = RST ? d.ibit + (size_t)img * (a.K + 1u) : nullptr;
+    uint32_t* sub0 = RST ? d.sub0 + (size_t)img * (a.K + 1u) : nullptr;
     if (o1 < o0 || o1 > a.ecd_cap || o1 - o0 > ECD_MAX) {               // uniform
         if (tid == 0) {
             atomicOr(a.status + img, JPEGD_ST_OFFSETS);
@@ -90,8 +121,8 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DL
     const uint32_t len = (uint32_t)(o1 - o0), cap_bytes = ((len + 3u) / 4u + 1u) * 4u;
     const uint8_t* src = a.ecd + o0;
     uint8_t* out = (uint8_t*)(d.raw + raw_start(o0, img));
-    uint32_t carry = 0;
-    bool marker = false;
+    Sum carry = 0;
+    uint32_t flags = 0;
     for (uint32_t base = 0; base < len; base += 4u * SCAN_THREADS) {
         const uint32_t j = base + 4u * tid;
         uint8_t b[6];                                  // the byte before, four of this thread's, the byte after
@@ -100,28 +131,62 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DL
             const uint32_t k = j + (uint32_t)q - 1u;
             b[q] = (j + (uint32_t)q >= 1u && k < len) ? src[k] : (uint8_t)1;        // outside the segment: neither FF nor 00
         }
-        uint32_t keep = 0, kept = 0;
+        uint32_t keep = 0, kept = 0, mark = 0, marks = 0;
 #pragma unroll
         for (int q = 1; q <= 4; ++q) {
             if (j + (uint32_t)q - 1u >= len) break;
-            if (b[q] == 0xff && b[q + 1] != 0) marker = true;
+            if (RST && b[q] == 0xff && (b[q + 1] & 0xf8) == 0xd0) { mark |= 1u << q; ++marks; continue; }       // a restart marker:
+            if (RST && b[q - 1] == 0xff && (b[q] & 0xf8) == 0xd0) continue;                                      // both bytes go
+            if (b[q] == 0xff && b[q + 1] != 0) flags |= JPEGD_ST_MARKER;
             if (!(b[q] == 0 && b[q - 1] == 0xff)) { keep |= 1u << q; ++kept; }
         }
-        uint32_t sum;
-        uint32_t at = carry + block_excl_scan(kept, wtot, sum);
+        Sum sum;
+        const Sum before = carry + block_excl_scan((Sum)kept | (RST ? (Sum)((unsigned long long)marks << 32) : (Sum)0), wtot, sum);
         carry += sum;
+        uint32_t at = (uint32_t)before, idx = RST ? (uint32_t)((unsigned long long)before >> 32) : 0u;
 #pragma unroll
-        for (int q = 1; q <= 4; ++q)
+        for (int q = 1; q <= 4; ++q) {
             if (keep >> q & 1u) {
                 if (at < cap_bytes) out[(at & ~3u) + 3u - (at & 3u)] = b[q];       // byte k of the stream: bits 31 - 8 (k & 3) .. of word k / 4
                 ++at;
             }
+            if (RST && (mark >> q & 1u)) flags |= jpegd_marker(idx++, b[q + 1], at, a.K, ibit);
+        }
     }
-    if (marker) atomicOr(a.status + img, JPEGD_ST_MARKER);
+    const uint32_t total = 8u * (uint32_t)carry;
+    if (!RST) {
+        if (flags) atomicOr(a.status + img, flags);
+        if (tid == 0) {
+            d.total_bits[img] = total;
+            d.nsub[img] = total == 0 ? 1u : (total + a.sb - 1u) / a.sb;
+        }
+        return;
+    }
+    // the interval table: the markers met filled entries 1 .. their number; the intervals of missing markers are empty
+    const uint32_t met = (uint32_t)((unsigned long long)carry >> 32);
+    if (met + 1u != a.K) flags |= JPEGD_ST_RESTART;
+    if (flags) atomicOr(a.status + img, flags);
+    for (uint32_t k = min(met, a.K - 1u) + 1u + tid; k <= a.K; k += SCAN_THREADS) ibit[k] = total;
+    if (tid == 0) { ibit[0] = 0; s_max = 0; }
+    __syncthreads();
+    // the subsequences: every interval is cut on its own
+    uint32_t first = 0, longest = 0;
+    for (uint32_t base = 0; base < a.K; base += SCAN_THREADS) {
+        const uint32_t k = base + tid;
+        const uint32_t subs = k < a.K ? jpegd_interval_subs(ibit[k + 1u] - ibit[k], a.sb) : 0u;
+        uint32_t sum;
+        const uint32_t ex = first + block_excl_scan(subs, (uint32_t*)wtot, sum);
+        first += sum;
+        if (k < a.K) sub0[k] = ex;
+        longest = max(longest, subs);
+    }
+    atomicMax(&s_max, longest);
+    __syncthreads();
     if (tid == 0) {
-        const uint32_t total = 8u * carry;
+        sub0[a.K] = first;
         d.total_bits[img] = total;
-        d.nsub[img] = total == 0 ? 1u : (total + a.sb - 1u) / a.sb;
+        d.nsub[img] = first;
+        d.maxsub[img] = s_max;
     }
 }
 
@@ -134,7 +199,7 @@ __device__ __forceinline__ void load_tables(JpegdTable* dst, const JpegdTable* s
 }
 
 // ---- speculate / write: one thread per subsequence ------------------------------------------------------------------------
-template <bool WRITE>
+template <bool WRITE, bool RST>
 __global__ void __launch_bounds__(DEC_THREADS) jpegd_decode_kernel(DArgs a, DLayout d) {
     __shared__ JpegdTable tabs[6];
     const int img = blockIdx.y;
@@ -144,23 +209,37 @@ __global__ void __launch_bounds__(DEC_THREADS) jpegd_decode_kernel(DArgs a, DLay
     const uint64_t o0 = a.off[img];
     const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
     const uint32_t* bits = d.raw + raw_start(o0, img);
-    JpegdState* ex = d.exit + slot_start(o0, a.sb, img);
-    uint32_t* cnt = d.cnt + slot_start(o0, a.sb, img);
+    JpegdState* ex = d.exit + slot_start(a, o0, img);
+    uint32_t* cnt = d.cnt + slot_start(a, o0, img);
+    const uint32_t* ibit = RST ? d.ibit + (size_t)img * (a.K + 1u) : nullptr;
+    const uint32_t* sub0 = RST ? d.sub0 + (size_t)img * (a.K + 1u) : nullptr;
+    int16_t* coef = a.coef + (size_t)img * a.g.NB * 64;
+    int32_t* dcdiff = d.dcdiff + (size_t)img * a.g.SB;
     uint32_t status = 0;
     for (uint32_t i = blockIdx.x * DEC_THREADS + threadIdx.x; i < S; i += gridDim.x * DEC_THREADS) {
         JpegdState s;
-        if (WRITE && i) s = ex[i - 1];
-        else { s.p = i * a.sb; s.mz = 0; }
-        const uint32_t limit = min((i + 1u) * a.sb, total);
         uint32_t begun;
-        jpegd_run<WRITE>(bits, nwords, total, limit, tabs, a.g, s, begun, WRITE ? cnt[i] : 0u,
-                         a.coef + (size_t)img * a.g.NB * 64, d.dcdiff + (size_t)img * a.g.SB, status);
+        if (RST) {
+            const JpegdSpan sp = jpegd_span(a.g, ibit, sub0, a.K, a.sb, i);
+            if (WRITE && sp.j) s = ex[i - 1];
+            else { s.p = sp.start; s.mz = 0; }
+            // the first block begun here: the interval's first and the blocks begun in the interval before this subsequence
+            const uint32_t block = WRITE ? sp.block_begin + (cnt[i] - cnt[sub0[sp.k]]) : 0u;
+            jpegd_run_interval<WRITE>(bits, nwords, sp.end, sp.limit, tabs, a.g, s, begun, block, sp.block_begin, sp.block_end, coef,
+                                      dcdiff, status);
+        } else {
+            if (WRITE && i) s = ex[i - 1];
+            else { s.p = i * a.sb; s.mz = 0; }
+            const uint32_t limit = min((i + 1u) * a.sb, total);
+            jpegd_run<WRITE>(bits, nwords, total, limit, tabs, a.g, s, begun, WRITE ? cnt[i] : 0u, coef, dcdiff, status);
+        }
         if (!WRITE) { ex[i] = s; cnt[i] = begun; }
     }
     if (WRITE && status) atomicOr(a.status + img, status);
 }
 
 // ---- synchronise and place: one workgroup per image -------------------------------------------------------------------------
+template <bool RST>
 __global__ void __launch_bounds__(SYNC_THREADS) jpegd_sync_kernel(DArgs a, DLayout d) {
     __shared__ JpegdTable tabs[6];
     __shared__ uint32_t wtot[SYNC_THREADS / 64];
@@ -174,24 +253,35 @@ __global__ void __launch_bounds__(SYNC_THREADS) jpegd_sync_kernel(DArgs a, DLayo
     const uint64_t o0 = a.off[img];
     const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
     const uint32_t* bits = d.raw + raw_start(o0, img);
-    JpegdState* ex = d.exit + slot_start(o0, a.sb, img);
-    uint32_t* cnt = d.cnt + slot_start(o0, a.sb, img);
+    JpegdState* ex = d.exit + slot_start(a, o0, img);
+    uint32_t* cnt = d.cnt + slot_start(a, o0, img);
+    const uint32_t* ibit = RST ? d.ibit + (size_t)img * (a.K + 1u) : nullptr;
+    const uint32_t* sub0 = RST ? d.sub0 + (size_t)img * (a.K + 1u) : nullptr;
     const uint32_t chunks = (S + SYNC_THREADS - 1) / SYNC_THREADS;
+    const uint32_t longest = RST ? d.maxsub[img] : S;        // the subsequences of the longest interval
     uint32_t rounds = 0, unused = 0;
-    // after round r the subsequences 0 .. r are true: S - 1 rounds always suffice
-    while (rounds + 1 < S) {
+    // after round r the subsequences 0 .. r of every interval are true: the longest interval's - 1 rounds always suffice
+    while (rounds + 1 < longest) {
         ++rounds;
         int changed = 0;
         for (uint32_t c = chunks; c-- > 0;) {
             const uint32_t i = c * SYNC_THREADS + tid;
-            const bool active = i >= rounds && i < S;
+            JpegdSpan sp;
+            bool active = i >= rounds && i < S;
+            if (RST && active) {
+                sp = jpegd_span(a.g, ibit, sub0, a.K, a.sb, i);
+                active = sp.j >= rounds;
+            }
             JpegdState s;
             if (active) s = ex[i - 1];
             __syncthreads();                           // every state of this chunk's predecessors is read before one is written
             if (active) {
                 const JpegdState old = ex[i];
                 uint32_t begun;
-                jpegd_run<false>(bits, nwords, total, min((i + 1u) * a.sb, total), tabs, a.g, s, begun, 0u, nullptr, nullptr, unused);
+                if (RST)
+                    jpegd_run_interval<false>(bits, nwords, sp.end, sp.limit, tabs, a.g, s, begun, 0u, 0u, 0u, nullptr, nullptr, unused);
+                else
+                    jpegd_run<false>(bits, nwords, total, min((i + 1u) * a.sb, total), tabs, a.g, s, begun, 0u, nullptr, nullptr, unused);
                 if (s.p != old.p || s.mz != old.mz) changed = 1;
                 ex[i] = s; cnt[i] = begun;
             }
@@ -208,29 +298,58 @@ __global__ void __launch_bounds__(SYNC_THREADS) jpegd_sync_kernel(DArgs a, DLayo
         if (i < S) cnt[i] = carry + exq;
         carry += sum;
     }
-    if (tid == 0) {
-        if (carry < (uint32_t)a.g.SB) atomicOr(a.status + img, JPEGD_ST_BLOCKS);
-        if (a.rounds) a.rounds[img] = rounds;
+    bool few = !RST && tid == 0 && carry < (uint32_t)a.g.SB;
+    if (RST) {                                             // every interval must have begun its own blocks
+        __syncthreads();
+        const uint32_t per = (uint32_t)a.g.ri * (uint32_t)a.g.per;
+        for (uint32_t k = tid; k < a.K; k += SYNC_THREADS) {
+            const uint32_t begun = (k + 1u < a.K ? cnt[sub0[k + 1u]] : carry) - cnt[sub0[k]];
+            few |= begun < min(per, (uint32_t)a.g.SB - k * per);
+        }
     }
+    if (few) atomicOr(a.status + img, JPEGD_ST_BLOCKS);
+    if (tid == 0 && a.rounds) a.rounds[img] = rounds;
 }
 
 // ---- DC: one workgroup per (component, image) --------------------------------------------------------------------------------
+// a sum that starts again where `first` is set: (a, then b) = b if b.first, else their sum - the prediction of a restart interval
+struct DcSum {
+    int v, first;
+};
+__device__ __forceinline__ DcSum operator+(const DcSum& a, const DcSum& b) { return b.first ? b : DcSum{a.v + b.v, a.first}; }
+__device__ __forceinline__ DcSum lane_up(const DcSum& s, int o) { return DcSum{__shfl_up(s.v, o, 64), __shfl_up(s.first, o, 64)}; }
+__device__ __forceinline__ DcSum wave_excl_of(const DcSum& incl, const DcSum&, int lane) {
+    const DcSum u = lane_up(incl, 1);
+    return lane ? u : DcSum{};
+}
+__device__ __forceinline__ int dc_value(int s) { return s; }
+__device__ __forceinline__ int dc_value(const DcSum& s) { return s.v; }
+template <typename T>
+__device__ __forceinline__ T dc_item(int v, bool first);
+template <>
+__device__ __forceinline__ int dc_item<int>(int v, bool) { return v; }
+template <>
+__device__ __forceinline__ DcSum dc_item<DcSum>(int v, bool first) { return DcSum{v, first ? 1 : 0}; }
+
+// T = int: one sum over the component; T = DcSum (a.g.ri > 0): one per restart interval
+template <typename T>
 __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout d) {
-    __shared__ int wtot[SCAN_THREADS / 64];
+    __shared__ T wtot[SCAN_THREADS / 64];
     const int comp = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     if (d.nsub[img] == 0) return;
     const int ny = a.g.per - 2, mcus = a.g.SB / a.g.per, count = comp ? mcus : mcus * ny;
+    const int span = a.g.ri ? (comp ? a.g.ri : a.g.ri * ny) : count;        // the component's blocks in one interval
     const int32_t* diff = d.dcdiff + (size_t)img * a.g.SB;
     int16_t* coef = a.coef + (size_t)img * a.g.NB * 64;
-    int carry = 0;
+    T carry{};
     bool bad = false;
     for (int base = 0; base < count; base += SCAN_THREADS) {
         const int j = base + tid;
         const uint32_t b = comp ? (uint32_t)(j * a.g.per + ny + comp - 1) : (uint32_t)((j / ny) * a.g.per + j % ny);
-        const int v = j < count ? diff[b] : 0;
-        int sum;
-        const int dc = carry + block_excl_scan(v, wtot, sum) + v;
-        carry += sum;
+        const T v = dc_item<T>(j < count ? diff[b] : 0, j % span == 0);
+        T sum;
+        const int dc = dc_value(carry + block_excl_scan(v, wtot, sum) + v);
+        carry = carry + sum;
         if (j < count) {
             int c2;
             const long at = jpegd_place(a.g, b, c2);
@@ -252,19 +371,27 @@ struct FileTables {
 
 extern "C" {
 
-size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, size_t ecd_bytes, int subseq_bits) {
+size_t nimg_jpeg_decode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, size_t ecd_bytes,
+                                                int subseq_bits) {
     JpegGeo g;
     uint32_t sb;
-    if (!make_geo(&g, n, h, w, hs, vs) || !subseq_ok(subseq_bits, &sb) || ecd_bytes > (size_t)n * ECD_MAX) return 0;
+    if (!make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb) ||
+        ecd_bytes > (size_t)n * ECD_MAX)
+        return 0;
     return carve_d(g, ecd_bytes, sb, nullptr).bytes;
 }
 
-int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
-                     int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
-                     void* stream) {
+size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, size_t ecd_bytes, int subseq_bits) {
+    return nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, 0, ecd_bytes, subseq_bits);
+}
+
+int nimg_jpeg_decode_restart(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                             int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
+                             size_t workspace_bytes, void* stream) {
     JpegGeo g;
     uint32_t sb;
-    if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs) || !subseq_ok(subseq_bits, &sb))
+    if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs) ||
+        !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb))
         return NIMG_ERR_ARG;
     // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
     if (carve_d(g, 0, sb, workspace).bytes > workspace_bytes) return NIMG_ERR_WORKSPACE;
@@ -276,26 +403,40 @@ int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t*
     }
     const DLayout d = carve_d(g, lo, sb, workspace);
     DArgs a;
-    a.ecd = ecd; a.off = ecd_off; a.huffman = huffman; a.ecd_cap = lo; a.sb = sb; a.g = g;
+    a.ecd = ecd; a.off = ecd_off; a.huffman = huffman; a.ecd_cap = lo; a.sb = sb; a.K = jpegd_intervals(g); a.extra = slot_extra(g); a.g = g;
     a.coef = coef; a.status = status; a.rounds = rounds;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(status, 0, (size_t)n * 4, st) != hipSuccess || hipMemsetAsync(coef, 0, (size_t)n * g.NB * 128, st) != hipSuccess ||
         hipMemsetAsync(d.dcdiff, 0, (size_t)n * g.SB * 4, st) != hipSuccess || hipMemsetAsync(d.raw, 0, d.raw_words * 4, st) != hipSuccess)
         return NIMG_ERR_LAUNCH;
-    hipLaunchKernelGGL(jpegd_prepare_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    const bool rst = g.ri != 0;
+    if (rst) hipLaunchKernelGGL(jpegd_prepare_kernel<true>, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    else hipLaunchKernelGGL(jpegd_prepare_kernel<false>, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
     // no valid stream is longer than SB blocks of JPEGD_BLOCK_BITS_MAX bits; a longer (damaged) one is covered by the threads' stride
     const uint64_t bits_max = min((uint64_t)g.SB * JPEGD_BLOCK_BITS_MAX, 8 * min(lo, ECD_MAX));
-    const unsigned gx = (unsigned)min((uint64_t)4096, max((uint64_t)1, (bits_max / sb + DEC_THREADS) / DEC_THREADS));
-    hipLaunchKernelGGL(jpegd_decode_kernel<false>, dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
+    const uint64_t subs_max = bits_max / sb + (rst ? a.K : 0u);
+    const unsigned gx = (unsigned)min((uint64_t)4096, max((uint64_t)1, (subs_max + DEC_THREADS) / DEC_THREADS));
+    if (rst) hipLaunchKernelGGL((jpegd_decode_kernel<false, true>), dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
+    else hipLaunchKernelGGL((jpegd_decode_kernel<false, false>), dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpegd_sync_kernel, dim3((unsigned)n), dim3(SYNC_THREADS), 0, st, a, d);
+    if (rst) hipLaunchKernelGGL(jpegd_sync_kernel<true>, dim3((unsigned)n), dim3(SYNC_THREADS), 0, st, a, d);
+    else hipLaunchKernelGGL(jpegd_sync_kernel<false>, dim3((unsigned)n), dim3(SYNC_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpegd_decode_kernel<true>, dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
+    if (rst) hipLaunchKernelGGL((jpegd_decode_kernel<true, true>), dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
+    else hipLaunchKernelGGL((jpegd_decode_kernel<true, false>), dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpegd_dc_kernel, dim3(3, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    if (rst) hipLaunchKernelGGL(jpegd_dc_kernel<DcSum>, dim3(3, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    else hipLaunchKernelGGL(jpegd_dc_kernel<int>, dim3(3, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
+}
+
+int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                     int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    return nimg_jpeg_decode_restart(ecd, ecd_off, huffman, n, h, w, hs, vs, 0, subseq_bits, coef, status, rounds, workspace,
+                                    workspace_bytes, stream);
 }
 
 int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,

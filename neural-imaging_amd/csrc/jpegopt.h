@@ -45,7 +45,8 @@ JPEGOPT_HD inline int jpegopt_y_dc(const int16_t* cy, const JpegGeo& g, int mr, 
 
 // Scan block s of one image (ci: its coefficients, real blocks only) as the symbols nimg_jpeg_encode codes, with its clamps (DC
 // difference +-2047, AC +-1023): sink.symbol(table, symbol, value bits, their number) with table = 0 Y DC, 1 Y AC, 2 chroma DC,
-// 3 chroma AC - the DHT-id order 00 10 01 11.  A dummy block is its DC difference and one end-of-block.
+// 3 chroma AC - the DHT-id order 00 10 01 11.  A dummy block is its DC difference and one end-of-block.  The first block of a
+// component in a restart interval (g.ri MCUs, section 4i) is predicted from 0, like the first of the image.
 template <typename Sink>
 JPEGOPT_HD inline void jpegopt_walk_block(const int16_t* ci, const JpegGeo& g, int s, Sink& sink) {
     const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.per - 2;
@@ -57,14 +58,14 @@ JPEGOPT_HD inline void jpegopt_walk_block(const int16_t* ci, const JpegGeo& g, i
         bool other;
         dc = jpegopt_y_dc(ci, g, mr, mc, k, real);
         if (k > 0) pred = jpegopt_y_dc(ci, g, mr, mc, k - 1, other);
-        else if (m > 0) pred = jpegopt_y_dc(ci, g, (m - 1) / g.mx, (m - 1) % g.mx, ny - 1, other);
+        else if (!jpeg_interval_start(g, m)) pred = jpegopt_y_dc(ci, g, (m - 1) / g.mx, (m - 1) % g.mx, ny - 1, other);
         else pred = 0;
         blk = ci + ((long)(mr * g.vs + (k >> g.hsh)) * g.bwY + mc * g.hs + (k & (g.hs - 1))) * 64;     // not read unless real
     } else {                       // the chroma grid is the MCU grid: block m, never a dummy
         t = 2;
         blk = ci + ((long)g.nbY + (long)(k - ny) * g.nbC + m) * 64;
         dc = blk[0];
-        pred = m > 0 ? blk[-64] : 0;
+        pred = jpeg_interval_start(g, m) ? 0 : blk[-64];
     }
     int diff = dc - pred;
     diff = diff < -2047 ? -2047 : (diff > 2047 ? 2047 : diff);

@@ -2263,13 +2263,34 @@ def jpeg_geometry(h, w, hs, vs):
     return sum(r * c for r, c in comps), scan, comps
 
 
-def jpeg_ecd_bound(h, w, hs, vs):
-    """Upper bound of one image's entropy-coded segment in bytes (every block at its longest, every byte stuffed)."""
-    return 2 * -(-jpeg_geometry(h, w, hs, vs)[1] * JPEG_BLOCK_BITS_MAX // 8)
+def jpeg_restart_interval(restart_interval):
+    """A restart interval in MCUs as a file carries it: an integer 0..65535 (0 = no markers); everything else is a ValueError -
+    the DRI segment has 16 bits, and a larger value would quietly become another interval."""
+    try:
+        ri = int(restart_interval)
+        exact = not isinstance(restart_interval, bool) and ri == restart_interval
+    except (TypeError, ValueError):
+        exact = False
+    if not exact or not 0 <= ri <= 65535:
+        raise ValueError('restart_interval: an integer 0..65535 (MCUs) needed, got {!r}'.format(restart_interval))
+    return ri
 
 
-def _jpeg_workspace(n, h, w, hs, vs, device, workspace):
-    need = int(_lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs))
+def jpeg_restart_markers(h, w, hs, vs, restart_interval):
+    """How many restart markers one image carries: one behind every interval but the last."""
+    ri = jpeg_restart_interval(restart_interval)
+    return -(-(jpeg_geometry(h, w, hs, vs)[1] // (hs * vs + 2)) // ri) - 1 if ri else 0
+
+
+def jpeg_ecd_bound(h, w, hs, vs, restart_interval=0):
+    """Upper bound of one image's entropy-coded segment in bytes (every block at its longest, every byte stuffed; a restart marker
+    adds at most 4: a padded byte, its stuffing and the marker's two)."""
+    return 2 * -(-jpeg_geometry(h, w, hs, vs)[1] * JPEG_BLOCK_BITS_MAX // 8) + 4 * jpeg_restart_markers(h, w, hs, vs, restart_interval)
+
+
+def _jpeg_workspace(n, h, w, hs, vs, device, workspace, restart_interval=0):
+    need = int(_lib.load().nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, restart_interval) if restart_interval else
+               _lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs))
     if need == 0:
         raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
     if workspace is None:
@@ -2294,21 +2315,27 @@ def jpeg_transform(x, quality, hs=1, vs=1, workspace=None):
     return coef
 
 
-def jpeg_encode(coef, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None):
+def jpeg_encode(coef, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None, *, restart_interval=0):
     """Coefficients of jpeg_transform -> (entropy-coded segments back to back (uint8), lengths (n,) int32).  No byte is written at
-    or beyond `capacity` (default: the whole of `out`; without `out`: the upper bound, so that every segment fits)."""
+    or beyond `capacity` (default: the whole of `out`; without `out`: the upper bound, so that every segment fits).
+    restart_interval: MCUs between two restart markers (nimg_jpeg_encode_restart), 0 = none; the workspace is then
+    nimg_jpeg_encode_restart_workspace_bytes."""
     _chk(coef)
     n = coef.shape[0]
+    ri = jpeg_restart_interval(restart_interval)
     if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
         raise RuntimeError('jpeg_encode: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
-    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace, ri)
     if out is None:
-        out = torch.empty(n * jpeg_ecd_bound(h, w, hs, vs) if capacity is None else int(capacity), dtype=torch.uint8,
+        out = torch.empty(n * jpeg_ecd_bound(h, w, hs, vs, ri) if capacity is None else int(capacity), dtype=torch.uint8,
                           device=coef.device)
     _chk(out)
     lengths = torch.empty(n, dtype=torch.int32, device=coef.device)
-    _lib.call('nimg_jpeg_encode', _p(coef), n, h, w, hs, vs, _p(out), out.numel() if capacity is None else int(capacity),
-              _p(lengths), _p(ws), need, _stream())
+    capacity = out.numel() if capacity is None else int(capacity)
+    if ri:
+        _lib.call('nimg_jpeg_encode_restart', _p(coef), n, h, w, hs, vs, ri, _p(out), capacity, _p(lengths), _p(ws), need, _stream())
+    else:
+        _lib.call('nimg_jpeg_encode', _p(coef), n, h, w, hs, vs, _p(out), capacity, _p(lengths), _p(ws), need, _stream())
     return out, lengths
 
 
@@ -2379,12 +2406,14 @@ def jpeg_reconstruct_items(coef, h, w, quality, hs=1, vs=1, workspace=None, out=
 JPEG_SUBSEQ_BITS_MAX = 1 << 30
 
 
-def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspace=None):
+def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspace=None, *, restart_interval=0):
     """The entropy-coded segments of n baseline files of one geometry -> (coefficients (n, real blocks, 64) int16 as jpeg_transform
     leaves them, status (n,) int32 - 0 = decoded, the bits are include/nimg.h's - and rounds (n,) int32, the synchronisation rounds
     each image took).  ecd: uint8 device tensor, the segments back to back as they stand in the files; ecd_off: (n + 1,) int64
     offsets into it; huffman: (n, 6, 272) uint8, per image the tables Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC as 16 counts + 256
-    symbols.  subseq_bits: bits one thread decodes (a multiple of 32, 0 = the default; at least the stream = a sequential decode)."""
+    symbols.  subseq_bits: bits one thread decodes (a multiple of 32, 0 = the default; at least the stream = a sequential decode).
+    restart_interval: the DRI value the files share (nimg_jpeg_decode_restart) - their markers FF D0 .. D7 are taken out and checked
+    (status bit 512), and every interval is decoded from its own known start; 0 = files without markers."""
     _chk(ecd)
     _chk(ecd_off)
     _chk(huffman)
@@ -2395,7 +2424,9 @@ def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspac
     if huffman.dtype != torch.uint8 or tuple(huffman.shape) != (n, 6, 272):
         raise RuntimeError('jpeg_decode: Huffman tables {} {}, ({}, 6, 272) uint8 needed'.format(huffman.dtype, tuple(huffman.shape), n))
     subseq_bits = int(subseq_bits)
-    need = int(_lib.load().nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
+    ri = jpeg_restart_interval(restart_interval)
+    need = int(_lib.load().nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, ri, ecd.numel(), subseq_bits) if ri else
+               _lib.load().nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
     if need == 0:
         raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{} subseq_bits={}'.format(n, h, w, hs, vs, subseq_bits))
     if workspace is None:
@@ -2406,8 +2437,12 @@ def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspac
     coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
     status = torch.empty(n, dtype=torch.int32, device=ecd.device)
     rounds = torch.empty(n, dtype=torch.int32, device=ecd.device)
-    _lib.call('nimg_jpeg_decode', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, subseq_bits, _p(coef), _p(status), _p(rounds),
-              _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    if ri:
+        _lib.call('nimg_jpeg_decode_restart', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, ri, subseq_bits, _p(coef), _p(status),
+                  _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    else:
+        _lib.call('nimg_jpeg_decode', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, subseq_bits, _p(coef), _p(status), _p(rounds),
+                  _p(workspace), workspace.numel() * workspace.element_size(), _stream())
     return coef, status, rounds
 
 
@@ -2437,22 +2472,28 @@ JPEG_TABLE_BYTES = 272
 JPEG_BLOCK_BITS_MAX_TABLES = 1665       # a DC code may take 16 bits: 16 + 11 bits, 63 x (AC 16 + 10)
 
 
-def jpeg_ecd_bound_tables(h, w, hs, vs):
+def jpeg_ecd_bound_tables(h, w, hs, vs, restart_interval=0):
     """jpeg_ecd_bound for segments coded with caller-supplied tables."""
-    return 2 * -(-jpeg_geometry(h, w, hs, vs)[1] * JPEG_BLOCK_BITS_MAX_TABLES // 8)
+    return 2 * -(-jpeg_geometry(h, w, hs, vs)[1] * JPEG_BLOCK_BITS_MAX_TABLES // 8) + \
+        4 * jpeg_restart_markers(h, w, hs, vs, restart_interval)
 
 
-def jpeg_histogram(coef, h, w, hs=1, vs=1, out=None):
-    """Coefficients of jpeg_transform -> (n, 4, 257) int32: how often jpeg_encode emits each symbol of each table; entry 256 is 0."""
+def jpeg_histogram(coef, h, w, hs=1, vs=1, out=None, *, restart_interval=0):
+    """Coefficients of jpeg_transform -> (n, 4, 257) int32: how often jpeg_encode emits each symbol of each table; entry 256 is 0.
+    restart_interval: as jpeg_encode's - the DC differences at the start of an interval are taken from 0."""
     _chk(coef)
     n = coef.shape[0]
+    ri = jpeg_restart_interval(restart_interval)
     if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
         raise RuntimeError('jpeg_histogram: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
     hist = torch.empty((n, 4, 257), dtype=torch.int32, device=coef.device) if out is None else out
     _chk(hist)
     if hist.dtype != torch.int32 or tuple(hist.shape) != (n, 4, 257):
         raise RuntimeError('jpeg_histogram: output {} {}, int32 {} needed'.format(hist.dtype, tuple(hist.shape), (n, 4, 257)))
-    _lib.call('nimg_jpeg_histogram', _p(coef), n, h, w, hs, vs, _p(hist), _stream())
+    if ri:
+        _lib.call('nimg_jpeg_histogram_restart', _p(coef), n, h, w, hs, vs, ri, _p(hist), _stream())
+    else:
+        _lib.call('nimg_jpeg_histogram', _p(coef), n, h, w, hs, vs, _p(hist), _stream())
     return hist
 
 
@@ -2470,17 +2511,20 @@ def jpeg_optimal_tables(hist):
     return tables, status
 
 
-def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None):
+def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None, *, restart_interval=0):
     """jpeg_encode with the Huffman tables of each image given: tables (n, 4, 272) uint8 -> (segments back to back (uint8), lengths
-    (n,) int32, status (n,) int32: bits 1 = tables that are no prefix code (length 0), 2 = a symbol of the image has no code)."""
+    (n,) int32, status (n,) int32: bits 1 = tables that are no prefix code (length 0, or the restart markers alone), 2 = a symbol of
+    the image has no code).  restart_interval: as jpeg_encode's (nimg_jpeg_encode_tables_restart)."""
     _chk(coef)
     _chk(tables)
     n = coef.shape[0]
+    ri = jpeg_restart_interval(restart_interval)
     if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
         raise RuntimeError('jpeg_encode_tables: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
     if tables.dtype != torch.uint8 or tuple(tables.shape) != (n, 4, JPEG_TABLE_BYTES):
         raise RuntimeError('jpeg_encode_tables: tables {} {}, ({}, 4, 272) uint8 needed'.format(tables.dtype, tuple(tables.shape), n))
-    need = int(_lib.load().nimg_jpeg_encode_tables_workspace_bytes(n, h, w, hs, vs))
+    need = int(_lib.load().nimg_jpeg_encode_tables_restart_workspace_bytes(n, h, w, hs, vs, ri) if ri else
+               _lib.load().nimg_jpeg_encode_tables_workspace_bytes(n, h, w, hs, vs))
     if need == 0:
         raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
     if workspace is None:
@@ -2489,13 +2533,18 @@ def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None,
     if workspace.numel() * workspace.element_size() < need:
         raise RuntimeError('JPEG workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
     if out is None:
-        out = torch.empty(n * jpeg_ecd_bound_tables(h, w, hs, vs) if capacity is None else int(capacity), dtype=torch.uint8,
+        out = torch.empty(n * jpeg_ecd_bound_tables(h, w, hs, vs, ri) if capacity is None else int(capacity), dtype=torch.uint8,
                           device=coef.device)
     _chk(out)
     lengths = torch.empty(n, dtype=torch.int32, device=coef.device)
     status = torch.empty(n, dtype=torch.int32, device=coef.device)
-    _lib.call('nimg_jpeg_encode_tables', _p(coef), n, h, w, hs, vs, _p(tables), _p(out),
-              out.numel() if capacity is None else int(capacity), _p(lengths), _p(status), _p(workspace), need, _stream())
+    capacity = out.numel() if capacity is None else int(capacity)
+    if ri:
+        _lib.call('nimg_jpeg_encode_tables_restart', _p(coef), n, h, w, hs, vs, ri, _p(tables), _p(out), capacity, _p(lengths),
+                  _p(status), _p(workspace), need, _stream())
+    else:
+        _lib.call('nimg_jpeg_encode_tables', _p(coef), n, h, w, hs, vs, _p(tables), _p(out), capacity, _p(lengths), _p(status),
+                  _p(workspace), need, _stream())
     return out, lengths, status
 
 

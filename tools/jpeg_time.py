@@ -20,7 +20,12 @@ default mode's: nimg_jpeg_transform_tables (the divisors read from device memory
 nimg_jpeg_reconstruct_tables and compress_batch(qtables=); the coefficients are checked against the quality form's.  One JSON line
 per sub-sampling.
 
+--restart N / --restart-rows R give the files a restart interval of N MCUs / of R MCU rows at either
+sub-sampling: the default mode then times nimg_jpeg_encode_restart and compress_batch(restart_interval=), and --decode times
+nimg_jpeg_decode_restart and decode_batch(allow_restart=True) on those files.  Every line names its interval.
+
     python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode | --optimize | --qtables]
+                              [--restart N | --restart-rows R]
 For the split of the calls into their kernels: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_time.py ...
 """
 import argparse
@@ -59,31 +64,40 @@ def timed(fn, reps):
     return float(np.median(times)), out
 
 
-def measure(x_host, quality, subsampling, reps, dev):
+def interval_of(args, h, w, subsampling):
+    """the restart interval in MCUs the arguments ask for at this sub-sampling"""
+    hs, _ = ops.jpeg_subsampling(subsampling)
+    return args.restart_rows * -(-w // (8 * hs)) if args.restart_rows else args.restart
+
+
+def measure(x_host, quality, subsampling, reps, dev, ri=0):
     hs, vs = ops.jpeg_subsampling(subsampling)
     n, h, w, _ = x_host.shape
     x = torch.from_numpy(x_host).to(dev)
-    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    lib = ops._lib.load()
+    ws = torch.empty(int(lib.nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, ri) if ri else
+                         lib.nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
     out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
     ms = {}
     ms['transform'], coef = timed(lambda: ops.jpeg_transform(x, quality, hs, vs, workspace=ws), reps)
-    ms['encode'], (data, lengths) = timed(lambda: ops.jpeg_encode(coef, h, w, hs, vs, out=out, workspace=ws), reps)
+    ms['encode'], (data, lengths) = timed(lambda: ops.jpeg_encode(coef, h, w, hs, vs, out=out, workspace=ws, restart_interval=ri), reps)
 
     def copy_out():
         ln = lengths.cpu().numpy().astype(np.int64)
         return data[:int(ln.sum())].cpu().numpy(), ln
     ms['copy_d2h'], (blob, ln) = timed(copy_out, reps)
     ms['reconstruct'], y = timed(lambda: ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws), reps)
-    ms['compress_batch_total'], (yb, sizes) = timed(lambda: jpeg_helpers.compress_batch(x_host, quality, subsampling=subsampling), reps)
-    assert np.array_equal(yb, y.cpu().numpy()) and sizes == (ln + jpeg_helpers.JPEG_HEADER_BYTES + 2).tolist()
-    return {'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality, 'bytes': int(ln.sum()),
+    ms['compress_batch_total'], (yb, sizes) = timed(
+        lambda: jpeg_helpers.compress_batch(x_host, quality, subsampling=subsampling, restart_interval=ri), reps)
+    assert np.array_equal(yb, y.cpu().numpy()) and sizes == (ln + jpeg_helpers._header_bytes(None, ri)[0] + 2).tolist()
+    return {'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality, 'restart_interval': ri, 'bytes': int(ln.sum()),
             'bpp': 8.0 * float(np.mean(sizes)) / h / w, 'ms': {k: round(v, 4) for k, v in ms.items()},
             'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
 
 
 # stage -> what its kernel's name holds in the profiler's records, demangled or mangled
-DECODE_STAGES = (('prepare', ('jpegd_prepare_kernel',)), ('speculate', ('jpegd_decode_kernel<false>', 'jpegd_decode_kernelILb0E')),
-                 ('sync', ('jpegd_sync_kernel',)), ('write', ('jpegd_decode_kernel<true>', 'jpegd_decode_kernelILb1E')),
+DECODE_STAGES = (('prepare', ('jpegd_prepare_kernel',)), ('speculate', ('jpegd_decode_kernel<false', 'jpegd_decode_kernelILb0E')),
+                 ('sync', ('jpegd_sync_kernel',)), ('write', ('jpegd_decode_kernel<true', 'jpegd_decode_kernelILb1E')),
                  ('dc', ('jpegd_dc_kernel',)))
 
 
@@ -107,12 +121,12 @@ def kernel_ms(fn, reps):
     return out
 
 
-def measure_decode(x_host, quality, subsampling, reps, dev):
+def measure_decode(x_host, quality, subsampling, reps, dev, ri=0):
     """one dict per subseq_bits setting"""
     hs, vs = ops.jpeg_subsampling(subsampling)
     n, h, w, _ = x_host.shape
-    files = jpeg_helpers.encode_batch(x_host, quality, subsampling)
-    heads = [jpeg_helpers.parse_header(f) for f in files]
+    files = jpeg_helpers.encode_batch(x_host, quality, subsampling, restart_interval=ri)
+    heads = [jpeg_helpers.parse_header(f, allow_restart=True) for f in files]
     segments = [f[hd.ecd_offset:hd.ecd_end] for f, hd in zip(files, heads)]
     ecd = torch.from_numpy(np.frombuffer(b''.join(segments), np.uint8).copy()).to(dev)
     off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(s) for s in segments])]).astype(np.int64)).to(dev)
@@ -125,20 +139,23 @@ def measure_decode(x_host, quality, subsampling, reps, dev):
     whole = -(-8 * max(len(s) for s in segments) // 32) * 32
     rows = []
     for subseq_bits in (256, 512, 1024, 2048, whole):
-        size = int(ops._lib.load().nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
+        lib = ops._lib.load()
+        size = int(lib.nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, ri, ecd.numel(), subseq_bits) if ri else
+                   lib.nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
         ws = torch.empty(size, dtype=torch.uint8, device=dev)
 
         def decode():
-            return ops.jpeg_decode(ecd, off, huff, h, w, hs, vs, subseq_bits=subseq_bits, workspace=ws)
+            return ops.jpeg_decode(ecd, off, huff, h, w, hs, vs, subseq_bits=subseq_bits, workspace=ws, restart_interval=ri)
         ms = {}
         ms['decode'], (coef, status, rounds) = timed(decode, reps)
         assert int(status.abs().sum()) == 0 and torch.equal(coef, want)
         ms['reconstruct_tables'], y = timed(lambda: ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=True), reps)
-        ms['decode_batch_total'], yb = timed(lambda: jpeg_helpers.decode_batch(files, subseq_bits=subseq_bits), max(3, reps // 4))
+        ms['decode_batch_total'], yb = timed(lambda: jpeg_helpers.decode_batch(files, subseq_bits=subseq_bits, allow_restart=True),
+                                             max(3, reps // 4))
         assert np.array_equal(yb, y.cpu().numpy())
         r = rounds.cpu().numpy()
         rows.append({'mode': 'decode', 'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality,
-                     'subseq_bits': subseq_bits, 'sequential': subseq_bits == whole, 'segment_bytes': int(ecd.numel()),
+                     'restart_interval': ri, 'subseq_bits': subseq_bits, 'sequential': subseq_bits == whole, 'segment_bytes': int(ecd.numel()),
                      'subsequences_per_image': round(8.0 * ecd.numel() / n / subseq_bits, 1), 'workspace_bytes': size,
                      'rounds': {'min': int(r.min()), 'median': float(np.median(r)), 'max': int(r.max())},
                      'ms': {k: round(v, 4) for k, v in ms.items()}, 'kernel_ms': kernel_ms(decode, reps),
@@ -222,6 +239,8 @@ def main():
     ap.add_argument('--decode', action='store_true', help='time the decoder instead, per subseq_bits setting')
     ap.add_argument('--optimize', action='store_true', help='time writing with optimised Huffman tables next to nimg_jpeg_encode')
     ap.add_argument('--qtables', action='store_true', help="time the table form with libjpeg's tables of --quality instead")
+    ap.add_argument('--restart', type=int, default=0, help='restart interval in MCUs of the files written and read (default mode, --decode)')
+    ap.add_argument('--restart-rows', type=int, default=0, help='the same in MCU rows: the interval follows the sub-sampling')
     args = ap.parse_args()
     x = natural_images(args.batch, args.size, args.size, seed=1)
     if args.pillow:
@@ -233,8 +252,9 @@ def main():
     dev = torch.device('cuda', 0)
     if args.decode:
         for subsampling in SUBSAMPLINGS:
-            measure_decode(x[:4], args.quality, subsampling, 2, dev)                  # warm-up
-            for row in measure_decode(x, args.quality, subsampling, args.reps, dev):
+            ri = interval_of(args, args.size, args.size, subsampling)
+            measure_decode(x[:4], args.quality, subsampling, 2, dev, ri)              # warm-up
+            for row in measure_decode(x, args.quality, subsampling, args.reps, dev, ri):
                 print(json.dumps(dict(row, csrc_sha16=csrc_sha16())), flush=True)
         return
     if args.optimize:
@@ -248,8 +268,9 @@ def main():
             print(json.dumps(dict(measure_qtables(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())), flush=True)
         return
     for subsampling in SUBSAMPLINGS:
-        measure(x, args.quality, subsampling, 3, dev)                    # warm-up: code objects, allocator
-        print(json.dumps(dict(measure(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())))
+        ri = interval_of(args, args.size, args.size, subsampling)
+        measure(x, args.quality, subsampling, 3, dev, ri)                # warm-up: code objects, allocator
+        print(json.dumps(dict(measure(x, args.quality, subsampling, args.reps, dev, ri), csrc_sha16=csrc_sha16())))
 
 
 if __name__ == '__main__':
