@@ -838,6 +838,28 @@ int nimg_jpeg_decode_restart(const uint8_t* ecd, const uint64_t* ecd_off, const 
                              int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* Sign planes of the FAN's bf16-stored pooled activations: all that a layer's input gradient reads of the
+ * activation in front of it is LeakyReLU', one bit per value.  A plane is (n, h, w, c / 8) bytes next to a bf16 tensor (n, h, w, c),
+ * c % 8 == 0: bit e of byte c' / 8 is 1 iff the STORED bf16 value of channel c' + e is > 0 (-0, +0 and NaN give 0) - the predicate of
+ * the act_mask arguments, so results do not change by a bit.  Purely added: the entry points without the argument are the ones with
+ * a null plane, NIMG_ABI_VERSION stays.
+ *   conv1_pool_fwd_c4_sign     nimg_conv1_pool_fwd_c4 + pool_sign (n, h/2, wd/2, 4), optional; needs out_bf16.
+ *   conv2d_pool_fwd_bf16_sign  nimg_conv2d_pool_fwd_bf16_ex + pool_sign (n, h/2, wd/2, cout / 8), optional.  Only the 5x5 ring kernels
+ *                              write it: NIMG_ERR_ARG where nimg_conv2d_pool_sign_ok(the same arguments) is 0.
+ *   conv2d_fwd_bf16_unpool_sign  nimg_conv2d_fwd_bf16_unpool + act_sign, the plane of act_mask (optional; act_mask stays required and
+ *                              bf16, the output bf16, o1 % 8 == 0, else NIMG_ERR_ARG).  The ring kernels read the plane instead of
+ *                              the mask - a sixteenth of the bytes -, every other route reads the mask. */
+int nimg_conv1_pool_fwd_c4_sign(const void* c4, const float* w, const float* bias, void* pooled, unsigned char* pool_idx,
+                                unsigned char* pool_sign, int n, int h, int wd, float alpha, int out_bf16, void* stream);
+int nimg_conv2d_pool_sign_ok(int cin, int cout, int n, int h, int wd, int ks, int flags);
+int nimg_conv2d_pool_fwd_bf16_sign(const float* in, int cin, const float* w, const void* wb, const float* bias,
+                                   float* pool_out, unsigned char* pool_idx, unsigned char* pool_sign, int cout, int n, int h,
+                                   int wd, int ks, int act, float alpha, int flags, void* stream);
+int nimg_conv2d_fwd_bf16_unpool_sign(const void* in_pooled, const unsigned char* in_idx, int c1, const void* wb, const float* bias,
+                                     float* out1, int o1, const float* act_mask, const unsigned char* act_sign, int n, int h, int wd,
+                                     int ks, int pad_t, int pad_l, int hout, int wout, int act, float alpha, int flags,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,12 @@ PROTOTYPES = {
     'nimg_jpeg_decode_restart': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     'nimg_msssim_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'nimg_msssim': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]),
+    'nimg_conv1_pool_fwd_c4_sign': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P]),
+    'nimg_conv2d_pool_sign_ok': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'nimg_conv2d_pool_fwd_bf16_sign': (c_int, [P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                               c_int, P]),
+    'nimg_conv2d_fwd_bf16_unpool_sign': (c_int, [P, P, c_int, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, c_float, c_int, P]),
 }
 
 ERRORS = {-1: 'NIMG_ERR_ARG (invalid argument / unsupported configuration)',

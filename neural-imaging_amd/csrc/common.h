@@ -16,6 +16,25 @@ constexpr int WAVE = 64;
 
 __device__ __forceinline__ float lrelu(float v, float alpha) { return v > 0.0f ? v : alpha * v; }
 
+// Sign planes (include/nimg.h): the bit of a stored bf16 value is (value > 0) - not -0, +0, a negative or a NaN.  On the bit
+// patterns that is 1 <= bits <= 0x7F80 (+inf), per 16-bit half of a packed pair: one wrapping and one saturating packed
+// subtraction and a packed minimum -> 1 or 0 in each half (a compare + select + shift per VALUE is 1.6 x the instructions,
+// and the kernels that write planes are bound by VALU issue).
+typedef unsigned short nimg_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned bf16x2_positive(unsigned packed) {
+    const nimg_u16x2 one = {1, 1}, inf = {0x7F80, 0x7F80};
+    const nimg_u16x2 u = __builtin_bit_cast(nimg_u16x2, packed) - one;
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_elementwise_sub_sat(inf, u), one));
+}
+// x holds bits e = 0 .. 7 of channel pairs in each 16-bit half: channel 2 e in bit e, channel 2 e + 1 in bit 16 + e.  -> the 16
+// bits in channel order (bit c = channel c): both halves spread to the even positions at once, the upper one then moved up by one
+__device__ __forceinline__ unsigned sign_bits_interleave(unsigned x) {
+    x = (x | (x << 4)) & 0x0F0F0F0Fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return (x | (x >> 15)) & 0xFFFFu;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -33,6 +33,10 @@ struct ConvArgsB {
     float* out1b;                  // optional SECOND copy of out1 as bf16 (float32 out1 only): the running float32 sum of a residual
                                    // stream stays exact while its consumers - convolutions and weight gradients, which round to
                                    // bf16 anyway - read half the bytes through the bf16-input kernels
+    // Sign planes of bf16-stored pooled activations, (N, H, W, C / 8) bytes: bit e of byte c / 8 = (value of channel c + e > 0), the
+    // predicate of the LeakyReLU' mask (-0, +0 and NaN give 0).  Ring kernels only (conv_bf16_ring.h); null = not used.
+    unsigned char* pool_sign = nullptr;         // written next to pool_out (bf16-stored), from the values as stored
+    const unsigned char* act_sign = nullptr;    // read INSTEAD of act1 (which stays set: every other route masks with it)
 };
 
 namespace {
@@ -330,3 +334,5 @@ int conv_bf16_dispatch(const ConvArgsB& a, hipStream_t s);
 // launch_conv_b<KS, 1, 16, 16, 1, tn32 ? 32 : 64, INB>: the tile the fused conv + pool entry (conv_bf16_packed.hip) asks for
 template <int KS, bool INB>
 int conv_bf16_launch_16x16(const ConvArgsB& a, bool tn32, hipStream_t s);
+// the TN of the ring kernel conv_bf16_launch_16x16<5, true> hands this layer to, 0 if it goes elsewhere (who may ask for pool_sign)
+int conv_bf16_pool_ring_tn(const ConvArgsB& a, bool tn32);

@@ -122,7 +122,7 @@ static int conv2d_fwd_bf16_impl(const float* in1, int c1, const float* in2, int 
                          int ks, int stride, int pad_t, int pad_l, int pad_mode, int hout, int wout, int act,
                          float alpha, int flags, void* stream, const unsigned char* in_idx = nullptr,
                          const float* res = nullptr, void* out1b = nullptr, float* pool_out = nullptr,
-                         unsigned char* pool_idx = nullptr) {
+                         unsigned char* pool_idx = nullptr, const unsigned char* act_sign = nullptr) {
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!in1 || !wb || !out1 || c1 <= 0 || c2 < 0 || o1 <= 0 || o2 < 0 || n < 0 || h <= 0 || wd <= 0) return NIMG_ERR_ARG;
     if ((c2 > 0 && !in2) || (o2 > 0 && !out2) || hout <= 0 || wout <= 0 || pad_t < 0 || pad_l < 0) return NIMG_ERR_ARG;
@@ -142,6 +142,9 @@ static int conv2d_fwd_bf16_impl(const float* in1, int c1, const float* in2, int 
     if (in_idx && (!(flags & NIMG_BF16_IN) || stride != 1 || ks != 5 || (h & 1) || (wd & 1) || pad_mode != 0)) return NIMG_ERR_ARG;
     if ((flags & (NIMG_BF16_OUT | NIMG_BF16_MASK)) && ((o1 & 3) || (o2 & 3))) return NIMG_ERR_ARG;   // vector epilogue only
     if ((flags & NIMG_BF16_MASK) && o2 != 0) return NIMG_ERR_ARG;
+    // the sign plane stands for a bf16 mask of a bf16 output in 8-channel groups; the mask itself stays required
+    if (act_sign && (!act_mask || !(flags & NIMG_BF16_MASK) || !(flags & NIMG_BF16_OUT) || (o1 & 7) || o2 != 0)) return NIMG_ERR_ARG;
+    p.act_sign = act_sign;
     if ((flags & NIMG_D2S_OUT) && (ks != 3 || stride != 1 || o2 != 0 || (o1 & 15) || in_idx)) return NIMG_ERR_ARG;
     if ((flags & NIMG_S2D_OUT) && (ks != 3 || stride != 1 || o2 != 0 || (o1 & 3) || in_idx || (hout & 1) || (wout & 1) ||
                                    (flags & NIMG_D2S_OUT)))
@@ -233,9 +236,19 @@ int nimg_conv2d_fwd_bf16_res(const float* in1, int c1, const void* wb, const flo
 int nimg_conv2d_fwd_bf16_unpool(const void* in_pooled, const unsigned char* in_idx, int c1, const void* wb, const float* bias,
                                 float* out1, int o1, const float* act_mask, int n, int h, int wd, int ks, int pad_t, int pad_l,
                                 int hout, int wout, int act, float alpha, int flags, void* stream) {
+    return nimg_conv2d_fwd_bf16_unpool_sign(in_pooled, in_idx, c1, wb, bias, out1, o1, act_mask, nullptr, n, h, wd, ks, pad_t, pad_l,
+                                            hout, wout, act, alpha, flags, stream);
+}
+
+/* ... with the sign plane of act_mask next to it (see include/nimg.h): the ring kernels read the plane, every other route the mask */
+int nimg_conv2d_fwd_bf16_unpool_sign(const void* in_pooled, const unsigned char* in_idx, int c1, const void* wb, const float* bias,
+                                     float* out1, int o1, const float* act_mask, const unsigned char* act_sign, int n, int h, int wd,
+                                     int ks, int pad_t, int pad_l, int hout, int wout, int act, float alpha, int flags,
+                                     void* stream) {
     if (!in_idx) return NIMG_ERR_ARG;
     return conv2d_fwd_bf16_impl((const float*)in_pooled, c1, nullptr, 0, wb, bias, out1, o1, nullptr, 0, act_mask, n, h, wd, ks, 1,
-                                pad_t, pad_l, 0, hout, wout, act, alpha, flags | NIMG_BF16_IN, stream, in_idx);
+                                pad_t, pad_l, 0, hout, wout, act, alpha, flags | NIMG_BF16_IN, stream, in_idx, nullptr, nullptr,
+                                nullptr, nullptr, act_sign);
 }
 
 /* Conv2DTranspose(cout, 2x2, stride 2) forward (pipelines.py:205) on the matrix core: four 1x1 products, one per output

@@ -626,10 +626,40 @@ int nimg_conv2d_pool_fwd_bf16(const float* in, int cin, const float* w, const vo
 int nimg_conv2d_pool_fwd_bf16_ex(const float* in, int cin, const float* w, const void* wb, const float* bias,
                                  float* pool_out, unsigned char* pool_idx, int cout, int n, int h, int wd, int ks,
                                  int act, float alpha, int flags, void* stream) {
+    return nimg_conv2d_pool_fwd_bf16_sign(in, cin, w, wb, bias, pool_out, pool_idx, nullptr, cout, n, h, wd, ks, act, alpha, flags,
+                                          stream);
+}
+
+/* The ConvParamsB of the fused conv + pool layer over >= 8 input channels, and whether its tile is the 32-channel one */
+static bool pool_fwd_params(ConvParamsB& p, int cin, int cout, int n, int h, int wd, int ks, int act, float alpha, int flags) {
+    p.in2 = nullptr; p.out1 = nullptr; p.out2 = nullptr;
+    p.act1 = nullptr; p.pool_idx = nullptr; p.convt = 0; p.flags = flags; p.in_idx = nullptr; p.res = nullptr;
+    p.out1b = nullptr;
+    p.C1 = cin; p.C2 = 0; p.O1 = cout; p.O2 = 0; p.CinP = (cin + 15) / 16 * 16;
+    p.N = n; p.H = h; p.W = wd; p.Hout = h; p.Wout = wd; p.pad_t = p.pad_l = (ks - 1) / 2;
+    p.tiles_y = p.tiles_x = 0; p.act = act; p.pad_mode = 0; p.alpha = alpha;
+    return cout <= 32 || (long)cdiv(cout, 64) * cdiv(h, 16) * cdiv(wd, 16) * n < 384;
+}
+
+/* 1 if nimg_conv2d_pool_fwd_bf16_sign with these arguments can write the sign plane (the layer goes to a ring kernel), else 0 */
+int nimg_conv2d_pool_sign_ok(int cin, int cout, int n, int h, int wd, int ks, int flags) {
+    if (cin <= 0 || cout <= 0 || n <= 0 || h <= 0 || wd <= 0 || (h & 1) || (wd & 1) || ks != 5 || (cin % 8) || (cout & 7)) return 0;
+    if ((flags & (NIMG_BF16_IN | NIMG_BF16_OUT)) != (NIMG_BF16_IN | NIMG_BF16_OUT)) return 0;
+    ConvParamsB p;
+    p.in1 = nullptr; p.wb = nullptr; p.bias = nullptr; p.pool_out = nullptr;
+    const bool tn32 = pool_fwd_params(p, cin, cout, n, h, wd, ks, 1, 0.f, flags);
+    return conv_bf16_pool_ring_tn(p, tn32) != 0 ? 1 : 0;
+}
+
+/* ... and, optionally, the sign plane of the bf16-stored pooled activation (include/nimg.h) */
+int nimg_conv2d_pool_fwd_bf16_sign(const float* in, int cin, const float* w, const void* wb, const float* bias,
+                                   float* pool_out, unsigned char* pool_idx, unsigned char* pool_sign, int cout, int n, int h,
+                                   int wd, int ks, int act, float alpha, int flags, void* stream) {
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!in || !pool_out || cin <= 0 || cout <= 0 || (cout & 3) || n < 0 || h <= 0 || wd <= 0) return NIMG_ERR_ARG;
     if ((h & 1) || (wd & 1) || (ks != 3 && ks != 5) || act < 0 || act > 1) return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
+    if (pool_sign && !nimg_conv2d_pool_sign_ok(cin, cout, n, h, wd, ks, flags)) return NIMG_ERR_ARG;    /* no kernel would write it */
     hipStream_t s = (hipStream_t)stream;
     if (cin == 3 || cin == 4) {
         if (!w) return NIMG_ERR_ARG;
@@ -639,13 +669,8 @@ int nimg_conv2d_pool_fwd_bf16_ex(const float* in, int cin, const float* w, const
     }
     if (!wb || (cin % 8)) return NIMG_ERR_ARG;
     ConvParamsB p;
-    p.in1 = in; p.in2 = nullptr; p.wb = (const __bf16*)wb; p.bias = bias; p.out1 = nullptr; p.out2 = nullptr;
-    p.act1 = nullptr; p.pool_out = pool_out; p.pool_idx = pool_idx; p.convt = 0; p.flags = flags; p.in_idx = nullptr; p.res = nullptr;
-    p.out1b = nullptr;
-    p.C1 = cin; p.C2 = 0; p.O1 = cout; p.O2 = 0; p.CinP = (cin + 15) / 16 * 16;
-    p.N = n; p.H = h; p.W = wd; p.Hout = h; p.Wout = wd; p.pad_t = p.pad_l = (ks - 1) / 2;
-    p.tiles_y = p.tiles_x = 0; p.act = act; p.pad_mode = 0; p.alpha = alpha;
-    const bool tn32 = cout <= 32 || (long)cdiv(cout, 64) * cdiv(h, 16) * cdiv(wd, 16) * n < 384;
+    const bool tn32 = pool_fwd_params(p, cin, cout, n, h, wd, ks, act, alpha, flags);
+    p.in1 = in; p.wb = (const __bf16*)wb; p.bias = bias; p.pool_out = pool_out; p.pool_idx = pool_idx; p.pool_sign = pool_sign;
     if (flags & NIMG_BF16_IN)
         return ks == 3 ? conv_bf16_launch_16x16<3, true>(p, tn32, s) : conv_bf16_launch_16x16<5, true>(p, tn32, s);
     return ks == 3 ? conv_bf16_launch_16x16<3, false>(p, tn32, s) : conv_bf16_launch_16x16<5, false>(p, tn32, s);

@@ -324,8 +324,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : (TN == 32 ? 3 : 2)) void con
                         if (grp >= p.N || py >= Hp || px >= Wp) return;
                         const long o = (((long)grp * Hp + py) * Wp + px) * Cout + co0 + c;
                         const float f[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                        *reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(p.pool_out) + o) = pack8(f);
+                        const bf16x8 pk = pack8(f);
+                        *reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(p.pool_out) + o) = pk;
                         if (p.pool_idx) *reinterpret_cast<uint2*>(p.pool_idx + o) = k;
+                        if (p.pool_sign) {                 // one bit per value AS STORED: what the next layer's input gradient
+                            const uint4 pw = __builtin_bit_cast(uint4, pk);      // would have derived from the bf16 tensor
+                            const unsigned sb = bf16x2_positive(pw.x) | (bf16x2_positive(pw.y) << 1) | (bf16x2_positive(pw.z) << 2) |
+                                                (bf16x2_positive(pw.w) << 3);
+                            p.pool_sign[o >> 3] = (unsigned char)sign_bits_interleave(sb);
+                        }
                     });
             }
             return;
@@ -363,7 +370,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : (TN == 32 ? 3 : 2)) void con
 #pragma unroll
                     for (int e = 0; e < 8; ++e) f[e] = lrelu(f[e], p.alpha);
                 }
-                if (p.act1) {
+                if (p.act_sign) {                  // the mask's sign plane: one byte instead of the activation's 16
+                    const unsigned sb = p.act_sign[o >> 3];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) f[e] *= ((sb >> e) & 1u) ? 1.0f : p.alpha;
+                } else if (p.act1) {
                     const bf16x8 m = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const __bf16*>(p.act1) + o);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) f[e] *= (float)m[e] > 0.f ? 1.0f : p.alpha;

@@ -333,6 +333,29 @@ __global__ __launch_bounds__(256) void conv_fwd_bf16_kernel(const ConvParamsB p)
     }
 }
 
+// The ring kernel (its TN: 128 or 64; 0 = none) that launch_conv_b<5, 1, 16, 16, 1, 64, true> hands a layer to.  One function, so
+// that who has to know the route BEFORE the launch (the fused conv + pool entry, which lets only the ring epilogue write a sign
+// plane) asks exactly what the dispatch asks.
+inline int conv5_ring_tn(const ConvParamsB& p) {
+    static const bool no_buf = getenv("NIMG_NO_BUFFER_LOADS") != nullptr;
+    static const bool no_ring = getenv("NIMG_NO_CONV5_RING") != nullptr;
+    static const bool no_ring64 = getenv("NIMG_NO_CONV5_RING64") != nullptr;
+    static const bool tn64 = getenv("NIMG_RING_TN64") != nullptr;      // A/B: 512 pixels x 64 channels per workgroup
+    const int Cin = p.C1 + p.C2, Cout = p.O1 + p.O2;
+    const long in_bytes = ((long)p.N * p.H * p.W * p.C1 * 2) >> (p.in_idx ? 2 : 0);
+    const long w_bytes = (long)(p.CinP >> 4) * 25 * 16 * Cout * 2;
+    if (no_buf || p.C2 != 0 || Cin % 16 != 0 || Cout % 64 != 0 || p.convt || in_bytes >= (1l << 31) - 65536 ||
+        w_bytes >= (1l << 31) - 65536)
+        return 0;
+    // the ring kernels' epilogue knows bias / activation / mask / pooling only: a second bf16 copy (out1b), a
+    // residual or a layout flag stays with the generic kernel, whose epilogue writes them
+    const bool plain_epi = !p.res && !p.out1b && !(p.flags & (NIMG_D2S_OUT | NIMG_S2D_OUT | NIMG_COPY_LRELU));
+    if (no_ring || !plain_epi || p.O2 != 0 || p.pad_t != 2 || p.pad_l != 2 || p.Hout != p.H || p.Wout != p.W) return 0;
+    if (Cout % 128 == 0 && !(tn64 && p.Hout >= 32)) return 128;
+    if (!no_ring64 && p.Hout >= 32) return 64;
+    return 0;
+}
+
 template <int KS, int STRIDE, int TH, int TW, int NB, int TN, bool INB = false, bool BUF = false, int CKT = 16>
 int launch_conv_b(const ConvParamsB& p, hipStream_t stream) {
     if constexpr (KS == 1 && !BUF && CKT == 16) {          // 1x1: 64-channel K chunks when the channels allow
@@ -378,16 +401,9 @@ int launch_conv_b(const ConvParamsB& p, hipStream_t stream) {
                     return launch_conv5_ring<128, 4, 3>(p, stream);
             }
             if constexpr (KS == 5 && TH == 16 && TW == 16 && NB == 1 && TN == 64) {
-                static const bool no_ring = getenv("NIMG_NO_CONV5_RING") != nullptr;
-                static const bool no_ring64 = getenv("NIMG_NO_CONV5_RING64") != nullptr;
-                // the ring kernels' epilogue knows bias / activation / mask / pooling only: a second bf16 copy (out1b), a
-                // residual or a layout flag stays with the generic kernel, whose epilogue writes them
-                const bool plain_epi = !p.res && !p.out1b && !(p.flags & (NIMG_D2S_OUT | NIMG_S2D_OUT | NIMG_COPY_LRELU));
-                if (!no_ring && plain_epi && p.O2 == 0 && p.pad_t == 2 && p.pad_l == 2 && p.Hout == p.H && p.Wout == p.W) {
-                    static const bool tn64 = getenv("NIMG_RING_TN64") != nullptr;      // A/B: 512 pixels x 64 channels per workgroup
-                    if (Cout % 128 == 0 && !(tn64 && p.Hout >= 32)) return launch_conv5_ring<128>(p, stream);
-                    if (!no_ring64 && p.Hout >= 32) return launch_conv5_ring<64>(p, stream);
-                }
+                const int ring = conv5_ring_tn(p);
+                if (ring == 128) return launch_conv5_ring<128>(p, stream);
+                if (ring == 64) return launch_conv5_ring<64>(p, stream);
             }
             return launch_conv_b<KS, STRIDE, TH, TW, NB, TN, true, true>(p, stream);
         }

@@ -294,7 +294,8 @@ __device__ __forceinline__ void conv1_slot(int ks, int h, int j, int& ky, int& k
 template <int TWD, bool OUT_BF16>
 __global__ __launch_bounds__(256, CONV1_WGS) void conv1_pool_fwd_kernel(const void* __restrict__ c4, const float* __restrict__ w,
                                                              const float* __restrict__ bias, void* __restrict__ pooled,
-                                                             unsigned char* __restrict__ pidx, int N, int H, int W,
+                                                             unsigned char* __restrict__ pidx,
+                                                             unsigned char* __restrict__ psign, int N, int H, int W,
                                                              float alpha, int tiles_y, int tiles_x) {
     constexpr int TRD = 8, HR = TRD + 4, HC = TWD + 4, NPC = HC / 2;            // tile rows / halo rows / halo cols / pixel pairs
     constexpr int PT = NPC <= 64 ? 64 : 128, RG = 256 / PT, RPTS = (HR + RG - 1) / RG;
@@ -437,6 +438,12 @@ __global__ __launch_bounds__(256, CONV1_WGS) void conv1_pool_fwd_kernel(const vo
                     uint4* d = reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(pooled) + po);
                     d[0] = make_uint4(pb[0], pb[1], pb[2], pb[3]);
                     d[1] = make_uint4(pb[4], pb[5], pb[6], pb[7]);
+                    if (psign) {                  // sign plane: bit (c & 7) of byte c >> 3 = (value as stored > 0), this lane's 16 channels
+                        unsigned sb = 0;          // pair g = channels 2 g, 2 g + 1 -> bits g and 16 + g
+#pragma unroll
+                        for (int g = 7; g >= 0; --g) sb = (sb << 1) | nimg::bf16x2_positive(pb[g]);
+                        *reinterpret_cast<unsigned short*>(psign + (po >> 3)) = (unsigned short)nimg::sign_bits_interleave(sb);
+                    }
                 } else {
                     float4* d = reinterpret_cast<float4*>(reinterpret_cast<float*>(pooled) + po);
 #pragma unroll
@@ -844,18 +851,18 @@ __global__ __launch_bounds__(256) void conv1_dgrad_pooled_kernel(const void* __r
 constexpr int F1_WGS = 1024;             // persistent workgroups of the conv1 weight gradient (one slab each)
 
 template <int TWD>
-int launch_conv1_pool(const void* c4, const float* w, const float* bias, void* pooled, unsigned char* pidx, int n, int h,
-                      int wd, float alpha, int out_bf16, hipStream_t s) {
+int launch_conv1_pool(const void* c4, const float* w, const float* bias, void* pooled, unsigned char* pidx, unsigned char* psign,
+                      int n, int h, int wd, float alpha, int out_bf16, hipStream_t s) {
     const int tiles_y = cdiv(h, 8), tiles_x = cdiv(wd, TWD);
     const long total = (long)n * tiles_y * tiles_x;
     static const int capmul = getenv("NIMG_CONV1_CAP") ? atoi(getenv("NIMG_CONV1_CAP")) : 0;
     const long cap = 256L * (capmul > 0 ? capmul : CONV1_WGS);      // persistent: the resident workgroups (167 registers per lane)
     const dim3 grid((unsigned)(total < cap ? total : cap));
     if (out_bf16)
-        hipLaunchKernelGGL((conv1_pool_fwd_kernel<TWD, true>), grid, dim3(256), 0, s, c4, w, bias, pooled, pidx, n, h, wd, alpha,
-                           tiles_y, tiles_x);
+        hipLaunchKernelGGL((conv1_pool_fwd_kernel<TWD, true>), grid, dim3(256), 0, s, c4, w, bias, pooled, pidx, psign, n, h, wd,
+                           alpha, tiles_y, tiles_x);
     else
-        hipLaunchKernelGGL((conv1_pool_fwd_kernel<TWD, false>), grid, dim3(256), 0, s, c4, w, bias, pooled, pidx, n, h, wd,
+        hipLaunchKernelGGL((conv1_pool_fwd_kernel<TWD, false>), grid, dim3(256), 0, s, c4, w, bias, pooled, pidx, psign, n, h, wd,
                            alpha, tiles_y, tiles_x);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -965,9 +972,16 @@ extern "C" {
 
 int nimg_conv1_pool_fwd_c4(const void* c4, const float* w, const float* bias, void* pooled, unsigned char* pool_idx, int n,
                            int h, int wd, float alpha, int out_bf16, void* stream) {
+    return nimg_conv1_pool_fwd_c4_sign(c4, w, bias, pooled, pool_idx, nullptr, n, h, wd, alpha, out_bf16, stream);
+}
+
+/* ... and, optionally, the sign plane (n, h/2, wd/2, 4) of the bf16-stored pooled activation (include/nimg.h) */
+int nimg_conv1_pool_fwd_c4_sign(const void* c4, const float* w, const float* bias, void* pooled, unsigned char* pool_idx,
+                                unsigned char* pool_sign, int n, int h, int wd, float alpha, int out_bf16, void* stream) {
     if (n == 0) return NIMG_OK;
     if (!c4 || !w || !pooled || n < 0 || h < 2 || wd < 2 || (h & 1) || (wd & 1) || !(alpha > 0.f && alpha <= 1.f))
         return NIMG_ERR_ARG;
+    if (pool_sign && !out_bf16) return NIMG_ERR_ARG;            /* the bits are those of the bf16 values */
     const long per_image = (long)h * wd * 8;
     if (per_image > 0x7fffffffL) return NIMG_ERR_ARG;
     const int chunk = (int)(0x7fffffffL / per_image);           // buffer descriptors address < 2 GB
@@ -978,8 +992,9 @@ int nimg_conv1_pool_fwd_c4(const void* c4, const float* w, const float* bias, vo
         const void* src = (const char*)c4 + px0 * 8;
         void* dst = (char*)pooled + pp0 * esz;
         unsigned char* di = pool_idx ? pool_idx + (pp0 >> 2) : nullptr;       // 2 bits per value
-        const int rc = wd > 96 ? launch_conv1_pool<256>(src, w, bias, dst, di, nn, h, wd, alpha, out_bf16, (hipStream_t)stream)
-                               : launch_conv1_pool<64>(src, w, bias, dst, di, nn, h, wd, alpha, out_bf16, (hipStream_t)stream);
+        unsigned char* ds = pool_sign ? pool_sign + (pp0 >> 3) : nullptr;     // 1 bit per value
+        const int rc = wd > 96 ? launch_conv1_pool<256>(src, w, bias, dst, di, ds, nn, h, wd, alpha, out_bf16, (hipStream_t)stream)
+                               : launch_conv1_pool<64>(src, w, bias, dst, di, ds, nn, h, wd, alpha, out_bf16, (hipStream_t)stream);
         if (rc != NIMG_OK) return rc;
     }
     return NIMG_OK;

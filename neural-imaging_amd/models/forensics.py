@@ -124,19 +124,22 @@ class FAN(TFModel):
         net, nf = self._constrained.forward(P, x, c4_only=front)
         t['constrained'], t['nf'] = net, nf
         for i, c in enumerate(self._convs):
+            # the sign plane of this layer's pooled activation: all the NEXT convolution's input gradient reads of it (its
+            # LeakyReLU' mask) - kept where the kernel that takes the layer can write it (None otherwise: the mask is used)
+            want_sign = training and i + 1 < len(self._convs)
             if i == 0 and front:
                 nxt = self._convs[1] if len(self._convs) > 1 else self._conv1x1
                 as_bf16 = ops.STORE_BF16 and nxt.cout >= 8
-                net, idx = ops.conv1_pool_c4(net, P.p[c.name + '/kernel'], P.p[c.name + '/bias'], want_idx=training,
-                                             out_bf16=as_bf16)
-                t['idx1'], t['front'] = idx, True
+                net, idx, *sign = ops.conv1_pool_c4(net, P.p[c.name + '/kernel'], P.p[c.name + '/bias'], want_idx=training,
+                                                    out_bf16=as_bf16, want_sign=want_sign)
+                t['idx1'], t['front'], t['sign1'] = idx, True, sign[0] if sign else None
             elif c.can_pool(net):        # conv + LeakyReLU + pool in one pass; the full-resolution tensor is not stored
                 # throughput mode: pooled activations live in HBM as bf16 - every consumer (next convolution, its weight
                 # gradient, the LeakyReLU' sign test) rounds to bf16 / reads the sign anyway, so no result bit changes
                 nxt = self._convs[i + 1] if i + 1 < len(self._convs) else self._conv1x1
                 as_bf16 = ops.COMPUTE == 'bf16' and ops.STORE_BF16 and c.cout % 8 == 0 and nxt.cout >= 8
-                net, idx = c.forward_pool(P, net, want_idx=training, out_bf16=as_bf16)
-                t['idx{}'.format(i + 1)] = idx
+                net, idx, *sign = c.forward_pool(P, net, want_idx=training, out_bf16=as_bf16, want_sign=want_sign)
+                t['idx{}'.format(i + 1)], t['sign{}'.format(i + 1)] = idx, sign[0] if sign else None
             else:
                 a = c.forward(P, net)
                 t['conv{}'.format(i + 1)] = a
@@ -311,7 +314,8 @@ class FAN(TFModel):
                 params(lambda inp=inp, g=d_pool, i=i, conv=conv: ops.conv2d_wgrad_unpool(
                     inp, g, t['idx{}'.format(i)], conv.ks, dw=P.g[conv.name + '/kernel'], db=P.g[conv.name + '/bias'], side=True), i)
                 d_pool = ops.conv2d_dgrad_unpool(d_pool, t['idx{}'.format(i)], P.p[conv.name + '/kernel'], act_mask=prev_mask,
-                                                 out_bf16=g_bf16(i - 1))
+                                                 out_bf16=g_bf16(i - 1),
+                                                 act_sign=t.get('sign{}'.format(i - 1)) if prev_mask is not None else None)
                 continue
             if fused(i):
                 # throughput mode: the un-pooled gradient only feeds bf16 MFMA kernels - store it as bf16 (same bits)

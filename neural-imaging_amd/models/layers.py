@@ -65,10 +65,11 @@ class Conv2D(object):
         return self.stride == 1 and self.cin2 == 0 and self.ks in (3, 5) and self.cout % 4 == 0 and \
             x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0 and self.activation == 'leaky_relu'
 
-    def forward_pool(self, store, x, want_idx=True, out_bf16=False):
-        """conv -> activation -> MaxPool2D(2) in one pass; returns (pooled, argmax bytes)."""
+    def forward_pool(self, store, x, want_idx=True, out_bf16=False, want_sign=False):
+        """conv -> activation -> MaxPool2D(2) in one pass; returns (pooled, argmax bytes) - with want_sign a third value, the sign
+        plane of the pooled activation or None (ops.conv2d_pool)."""
         return ops.conv2d_pool(x, store.p[self.name + '/kernel'], store.p[self.name + '/bias'], act=self.activation,
-                               want_idx=want_idx, out_bf16=out_bf16)
+                               want_idx=want_idx, out_bf16=out_bf16, want_sign=want_sign)
 
     def forward_and_pool(self, store, x, out_bf16=False):
         """-> (activation, MaxPool2D(2) of it): one pass where the bf16 epilogue can write both (ops.conv2d_and_pool)."""

@@ -950,10 +950,25 @@ def maxpool2_bwd(dp, yact, add=None, apply_mask=True, out=None, alpha=None):
     return dz
 
 
-def conv2d_pool(x, w, bias=None, act='leaky_relu', want_idx=True, out_bf16=False):
+# Sign planes of the FAN's bf16-stored pooled activations: (N, H, W, C / 8) uint8, bit e of byte c / 8 = (channel c + e > 0).  The
+# input gradient of the layer behind reads the plane instead of the activation for its LeakyReLU' mask (a sixteenth of the bytes,
+# the same bits).  NIMG_NO_ACT_SIGN=1: no plane is written or read (A/B runs).
+ACT_SIGN = _os.environ.get('NIMG_NO_ACT_SIGN') is None
+
+
+def conv2d_pool_sign_ok(x, w, out_bf16=True):
+    """Can conv2d_pool(x, w, out_bf16=...) write the sign plane?  (Only the 5x5 ring kernels do; the library knows its routes.)"""
+    n, h, wd, cin = x.shape
+    return ACT_SIGN and COMPUTE == 'bf16' and _is_bf16(x) and out_bf16 and _lib.load().nimg_conv2d_pool_sign_ok(
+        cin, w.shape[3], n, h, wd, w.shape[0], BF16_IN | BF16_OUT) == 1
+
+
+def conv2d_pool(x, w, bias=None, act='leaky_relu', want_idx=True, out_bf16=False, want_sign=False):
     """Conv2D(SAME, stride 1) -> [LeakyReLU] -> MaxPool2D(2) in one pass (the FAN feature extractor): returns the pooled
     activation and the arg-max bytes; the full-resolution activation is never written.  Throughput mode: x may be stored as
-    bf16 and the pooled activation can be (out_bf16) - its consumers round it to bf16 anyway."""
+    bf16 and the pooled activation can be (out_bf16) - its consumers round it to bf16 anyway.
+    want_sign: returns (pooled, arg-max bytes, sign plane) - the plane is None where the kernel that takes this layer cannot write it
+    (conv2d_pool_sign_ok)."""
     _f32(w, bias)
     _fb(x)
     n, h, wd, cin = x.shape
@@ -969,12 +984,17 @@ def conv2d_pool(x, w, bias=None, act='leaky_relu', want_idx=True, out_bf16=False
     if bf16_path:
         wb = None if cin in (3, 4) else weights_bf16(w, 0)
         flags = (BF16_IN if _is_bf16(x) else 0) | (BF16_OUT if out_bf16 else 0)
+        if want_sign and conv2d_pool_sign_ok(x, w, out_bf16):
+            sign = torch.empty((n, h // 2, wd // 2, cout // 8), dtype=torch.uint8, device=x.device)
+            _lib.call('nimg_conv2d_pool_fwd_bf16_sign', _p(x), cin, _p(w), _p(wb), _p(bias), _p(pooled), _p(idx), _p(sign), cout, n,
+                      h, wd, ks, a, LRELU_ALPHA, flags, _stream())
+            return pooled, idx, sign
         _lib.call('nimg_conv2d_pool_fwd_bf16_ex', _p(x), cin, _p(w), _p(wb), _p(bias), _p(pooled), _p(idx), cout, n, h, wd,
                   ks, a, LRELU_ALPHA, flags, _stream())
     else:
         _lib.call('nimg_conv2d_pool_fwd', _p(x), cin, _p(w), _p(bias), _p(pooled), _p(idx), cout, n, h, wd, ks, a,
                   LRELU_ALPHA, _stream())
-    return pooled, idx
+    return (pooled, idx, None) if want_sign else (pooled, idx)
 
 
 # The UNet's encoder levels write the pooled tensor from the second convolution's epilogue (NIMG_NO_POOL_ALSO=1: a separate
@@ -1080,13 +1100,22 @@ def unpool_fold_ok(x, g, cin, cout, ks):
         _os.environ.get('NIMG_NO_BUFFER_LOADS') is None
 
 
-def conv2d_dgrad_unpool(g, idx, w, act_mask=None, out_bf16=False):
-    """Input gradient of a fused 5x5 conv + pool layer from the pooled gradient g (N,H/2,W/2,Cout) bf16 + arg-max bytes."""
+def conv2d_dgrad_unpool(g, idx, w, act_mask=None, out_bf16=False, act_sign=None):
+    """Input gradient of a fused 5x5 conv + pool layer from the pooled gradient g (N,H/2,W/2,Cout) bf16 + arg-max bytes.
+    act_sign: the sign plane of act_mask (conv2d_pool / conv1_pool_c4 with want_sign), next to it: the kernels that can read the
+    plane instead of the mask do, the others (and every call that does not fit it) use the mask - the same bits either way."""
     _f32(w)
     _fb(g, act_mask)
     _chk(idx)
     n, hp, wp, cz = g.shape
     ks, ci = w.shape[0], w.shape[2]
+    if act_sign is not None:
+        _chk(act_sign)
+        if act_mask is None or act_sign.dtype != torch.uint8 or ci % 8 or tuple(act_sign.shape) != (n, 2 * hp, 2 * wp, ci // 8) or \
+                tuple(act_mask.shape) != (n, 2 * hp, 2 * wp, ci):
+            raise ValueError('conv2d_dgrad_unpool: act_sign is the (N,H,W,Cin/8) uint8 sign plane of the act_mask given with it')
+        if not (ACT_SIGN and out_bf16 and _is_bf16(act_mask)) or SPARSE_DGRAD:
+            act_sign = None
     out = torch.empty((n, 2 * hp, 2 * wp, ci), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=g.device)
     flags = (BF16_OUT if out_bf16 else 0) | (BF16_MASK if _is_bf16(act_mask) else 0)
     if SPARSE_DGRAD and ks == 5 and ci % 32 == 0 and cz % 8 == 0 and _is_bf16(g) and g.numel() * 2 < (1 << 31) - 65536:
@@ -1097,6 +1126,10 @@ def conv2d_dgrad_unpool(g, idx, w, act_mask=None, out_bf16=False):
                   flags, _stream())
         return out
     wb = weights_bf16(w, 1)
+    if act_sign is not None:
+        _lib.call('nimg_conv2d_fwd_bf16_unpool_sign', _p(g), _p(idx), cz, _p(wb), None, _p(out), ci, _p(act_mask), _p(act_sign), n,
+                  2 * hp, 2 * wp, ks, ks - 1 - (ks - 1) // 2, ks - 1 - (ks - 1) // 2, 2 * hp, 2 * wp, 0, LRELU_ALPHA, flags, _stream())
+        return out
     _lib.call('nimg_conv2d_fwd_bf16_unpool', _p(g), _p(idx), cz, _p(wb), None, _p(out), ci, _p(act_mask), n, 2 * hp, 2 * wp, ks,
               ks - 1 - (ks - 1) // 2, ks - 1 - (ks - 1) // 2, 2 * hp, 2 * wp, 0, LRELU_ALPHA, flags, _stream())
     return out
@@ -1500,10 +1533,12 @@ def front_end_ok(cin, cout, ks, h, w, n=None):
         h >= 4 and w >= 4 and small
 
 
-def conv1_pool_c4(c4, w, bias, act='leaky_relu', want_idx=True, out_bf16=True):
+def conv1_pool_c4(c4, w, bias, act='leaky_relu', want_idx=True, out_bf16=True, want_sign=False):
     """Conv2D(32, 5x5, SAME) + bias + activation + MaxPool2D(2) over the bf16 {c0,c1,c2,1} pixels written by cconv3 (the FAN's
     first convolution, throughput mode).  Returns (pooled (N,H/2,W/2,32), arg-max codes (N,H/2,W/2,8) uint8 | None): 2 bits per
-    channel, channel c in byte c >> 2 at bits 2 (c & 3) (include/nimg.h nimg_conv1_pool_fwd_c4)."""
+    channel, channel c in byte c >> 2 at bits 2 (c & 3) (include/nimg.h nimg_conv1_pool_fwd_c4).
+    want_sign: a third value, the sign plane (N,H/2,W/2,4) uint8 of the bf16 pooled activation (None without out_bf16 or with
+    NIMG_NO_ACT_SIGN)."""
     _f32(w, bias)
     _chk(c4)
     n, h, wd, c = c4.shape
@@ -1511,9 +1546,14 @@ def conv1_pool_c4(c4, w, bias, act='leaky_relu', want_idx=True, out_bf16=True):
         raise ValueError('conv1_pool_c4: (N,H,W,4) bf16 pixels, a (5,5,3,32) kernel and even sizes expected')
     pooled = torch.empty((n, h // 2, wd // 2, 32), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=c4.device)
     idx = torch.empty((n, h // 2, wd // 2, 8), dtype=torch.uint8, device=c4.device) if want_idx else None
+    if want_sign and ACT_SIGN and out_bf16:
+        sign = torch.empty((n, h // 2, wd // 2, 4), dtype=torch.uint8, device=c4.device)
+        _lib.call('nimg_conv1_pool_fwd_c4_sign', _p(c4), _p(w), _p(bias), _p(pooled), _p(idx), _p(sign), n, h, wd,
+                  LRELU_ALPHA if act == 'leaky_relu' else 1.0, 1, _stream())
+        return pooled, idx, sign
     _lib.call('nimg_conv1_pool_fwd_c4', _p(c4), _p(w), _p(bias), _p(pooled), _p(idx), n, h, wd,
               LRELU_ALPHA if act == 'leaky_relu' else 1.0, 1 if out_bf16 else 0, _stream())
-    return pooled, idx
+    return (pooled, idx, None) if want_sign else (pooled, idx)
 
 
 def conv1_wgrad_c4(c4, g, idx, dw=None, db=None, accumulate=False, side=False):

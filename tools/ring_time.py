@@ -44,11 +44,14 @@ def child(reps, zeros, n):
         x = mk(n, h, h, cin).to(torch.bfloat16)
         w = torch.randn((5, 5, cin, cout), device=dev) * 0.05
         b = torch.zeros((cout,), device=dev)
-        res[name + '_fwd'] = timed(lambda: ops.conv2d_pool(x, w, b, out_bf16=True))
+        # sign planes as the FAN keeps them (ops.ACT_SIGN; NIMG_NO_ACT_SIGN=1 times the masks alone): conv2 and conv3 write the plane
+        # of their pooled activation (conv4's feeds the head, which has its own), every input gradient reads the plane of its mask
+        res[name + '_fwd'] = timed(lambda: ops.conv2d_pool(x, w, b, out_bf16=True, want_sign=name != 'conv4'))
         g = mk(n, h // 2, h // 2, cout).to(torch.bfloat16)
         idx = torch.randint(0, 4, (n, h // 2, h // 2, cout), device=dev, dtype=torch.uint8)
         mask = torch.randn((n, h, h, cin), device=dev).to(torch.bfloat16)
-        res[name + '_dgrad'] = timed(lambda: ops.conv2d_dgrad_unpool(g, idx, w, act_mask=mask, out_bf16=True))
+        sign = torch.randint(0, 256, (n, h, h, cin // 8), device=dev, dtype=torch.uint8)
+        res[name + '_dgrad'] = timed(lambda: ops.conv2d_dgrad_unpool(g, idx, w, act_mask=mask, out_bf16=True, act_sign=sign))
     print('RING_TIME ' + json.dumps(res), flush=True)
 
 
