@@ -89,6 +89,28 @@ size_t nimg_djpeg_dq_workspace_bytes(int n, int h, int w);
 int nimg_djpeg_bwd_dq(const float* x, const float* gy, const uint8_t* mask, const float* qtab, float* gx, float* dq,
                       int n, int h, int w, int rounding, int accumulate, void* workspace, size_t workspace_bytes,
                       void* stream);
+/* Differentiable JPEG with chroma sub-sampling (csrc/djpeg_sub.hip): (hs, vs) = (2, 1) is 4:2:2, (2, 2) is 4:2:0;
+ * h % (8 vs) == 0 and w % (8 hs) == 0 (whole MCUs).  Any other factors - (1, 1) included: 4:4:4 stays with the entry points above -
+ * or a ragged image are NIMG_ERR_ARG.  The operator: colour as above; Cb / Cr = the mean of each hs x vs group (libjpeg's h2v1 /
+ * h2v2 without the bias); the 8x8 block path of nimg_djpeg_fwd on Y at (h, w) and on Cb / Cr at (h / vs, w / hs); chroma up-sampled
+ * by libjpeg's triangle filter in float (out[2i] = 3/4 in[i] + 1/4 in[i-1], out[2i+1] = 3/4 in[i] + 1/4 in[i+1], the edge sample
+ * beyond the component, down the columns then along the rows at 4:2:0); + 127, inverse colour, / 255, clip.
+ * x, y, qtab, mask (optional): as nimg_djpeg_fwd.  idx (optional, int16) / xdq (optional, float32): ONE buffer each, per image
+ * [Y blocks (h/8, w/8) | Cb blocks | Cr blocks (h/(8 vs), w/(8 hs))], every block [8][8] in natural order.
+ * workspace: nimg_djpeg_sub_workspace_bytes(n, h, w, hs, vs, with_dq) device bytes, 16-byte aligned (0 for an empty or refused
+ * shape) - the reduced chroma planes (forward: reconstructed, backward: gradients) and, with_dq, the per-wave table-gradient sums;
+ * with_dq = 0 serves the forward and a backward with dq == NULL.  A shorter one is NIMG_ERR_WORKSPACE.  Two launches per direction
+ * on `stream` (plus the reduction with dq), asynchronous, capturable, no allocation.  n == 0 is a no-op. */
+size_t nimg_djpeg_sub_workspace_bytes(int n, int h, int w, int hs, int vs, int with_dq);
+int nimg_djpeg_sub_fwd(const float* x, float* y, const float* qtab, uint8_t* mask, int16_t* idx, float* xdq,
+                       int n, int h, int w, int hs, int vs, int rounding, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* gx = d loss / d x of nimg_djpeg_sub_fwd given gy and the forward's mask; recomputes the forward DCTs from x.  dq (may be NULL):
+ * (2,8,8) float32 = [d loss / d Q_luma, d loss / d Q_chroma (Cb + Cr)], (+)= when accumulate - deterministic, the contract of
+ * nimg_djpeg_bwd_dq (per-wave partial sums in the workspace, fixed-order reduction; always the IEEE division). */
+int nimg_djpeg_sub_bwd(const float* x, const float* gy, const uint8_t* mask, const float* qtab, float* gx,
+                       float* dq /* may be NULL */, int n, int h, int w, int hs, int vs, int rounding, int accumulate,
+                       void* workspace, size_t workspace_bytes, void* stream);
 /* IJG quality scaling - replaces jpeg_qtable, compression/jpeg_helpers.py:264-305.  HOST function: out64 is a host
  * pointer to 64 floats (row-major 8x8).  channel 0 = luma, >0 = chroma. */
 int nimg_jpeg_qtable(int quality, int channel, float* out64);

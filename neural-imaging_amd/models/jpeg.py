@@ -11,6 +11,8 @@ final-validation codec, a host round trip through imageio there - is the baselin
 files and decoded images bit for bit, on the device (compression/jpeg_helpers.py).  It has no gradient.
 New: JPEG.file_tables / JPEG.process_files run that real codec with the model's own tables - the learned ones, or those the
 differentiable codec divides by - so the two stand side by side at identical tables.
+New: subsampling='4:2:2' / '4:2:0' - the differentiable codec with the real codec's chroma sub-sampling (box down-sampling,
+libjpeg's triangle up-sampling; csrc/djpeg_sub.hip).  '4:4:4' (the default) is the reference's model.
 """
 import numpy as np
 import torch
@@ -43,7 +45,9 @@ class DifferentiableJPEG(object):
     """Holds the codec settings; __call__ returns (y, X_dequantised) like the Keras model's call()."""
 
     def __init__(self, quality=None, rounding_approximation='sin', rounding_approximation_steps=5, trainable=False,
-                 device=None):
+                 device=None, subsampling='4:4:4'):
+        self.subsampling = subsampling
+        self.factors = ops.jpeg_subsampling(subsampling)          # ValueError for anything but 4:4:4, 4:2:2, 4:2:0
         if quality is not None and not is_valid_quality(quality):
             raise ValueError('Invalid JPEG quality: requires int in [1,100] or an iterable with least 2 such numbers')
         if rounding_approximation is not None and rounding_approximation not in ['sin', 'harmonic', 'soft']:
@@ -78,18 +82,23 @@ class DifferentiableJPEG(object):
     def __call__(self, x, quality=None):
         q = self.trainable_tables() if (self.trainable and (quality is None or quality == self.quality)) else \
             self.qtables(self.quality if quality is None else quality, x.device)
+        if self.factors != (1, 1):         # xdq: (X_luma (n,h/8,w/8,8,8), X_chroma (n,2,h/(8 vs),w/(8 hs),8,8))
+            y, _, _, xdq = ops.djpeg_sub_fwd(x, q, self.rounding_approximation, *self.factors, want_mask=False, want_xdq=True)
+            return y, xdq
         y, _, _, xdq = ops.djpeg_fwd(x, q, self.rounding_approximation, want_mask=False, want_xdq=True)
         return y, xdq
 
 
 class JPEG(TFModel):
 
-    def __init__(self, quality=None, codec='soft', trainable=False, device=None):
+    def __init__(self, quality=None, codec='soft', trainable=False, device=None, subsampling='4:4:4'):
         super().__init__(device=device)
         if codec is not None and codec not in ['libjpeg', 'soft', 'sin', 'harmonic']:
             raise ValueError('Unsupported codec version: {}'.format(codec))
+        self.subsampling = subsampling
+        self._factors = ops.jpeg_subsampling(subsampling)         # ValueError for anything but 4:4:4, 4:2:2, 4:2:0
         self._codec_model = None if codec == 'libjpeg' else DifferentiableJPEG(quality, codec, trainable=trainable,
-                                                                               device=self.device)
+                                                                               device=self.device, subsampling=subsampling)
         # no trainable parameters unless trainable=True: then the two quantisation tables (models/jpeg.py:57-62)
         self._model = self._codec_model.params if (trainable and self._codec_model is not None) else ParamStore([], self.device)
         self.trainable = bool(trainable)
@@ -125,8 +134,9 @@ class JPEG(TFModel):
             if training:
                 raise NotImplementedError('the libjpeg codec has no gradient (the reference has none either): train on a '
                                           'differentiable codec, validate on this one')
-            # models/jpeg.py:227-233: compress_batch(batch_x, quality)[0] at 4:4:4; the byte counts are not asked for here
-            y, _ = device_codec(x, self.resolve_quality(self.quality if quality is None else quality), want_bytes=False)
+            # models/jpeg.py:227-233: compress_batch(batch_x, quality)[0], at the model's sub-sampling (4:4:4 there); the byte counts are not asked for here
+            y, _ = device_codec(x, self.resolve_quality(self.quality if quality is None else quality), self.subsampling,
+                                want_bytes=False)
             if out is not None:
                 out.copy_(y)
                 y = out
@@ -140,13 +150,21 @@ class JPEG(TFModel):
             q = self._codec_model.trainable_tables()
         else:
             q = self._codec_model.qtables(resolved, x.device)
-        y, mask, _, _ = ops.djpeg_fwd(x, q, self.codec, want_mask=training, out=out)
+        if self._factors != (1, 1):
+            y, mask, _, _ = ops.djpeg_sub_fwd(x, q, self.codec, *self._factors, want_mask=training, out=out)
+        else:
+            y, mask, _, _ = ops.djpeg_fwd(x, q, self.codec, want_mask=training, out=out)
         return y, ({'x': x, 'mask': mask, 'q': q, 'learned': learned} if training else None)
 
     def backward(self, ctx, dy, accumulate=False):
         """d loss / d x; with trainable tables also fills (accumulate: adds to) their gradients in the model's gradient buffer."""
         if self._codec_model is None:
             raise NotImplementedError('the libjpeg codec has no gradient')
+        if self._factors != (1, 1):
+            if ctx.get('learned'):
+                return ops.djpeg_sub_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec, *self._factors,
+                                         dq=self._model.flat_grad, accumulate=accumulate)
+            return ops.djpeg_sub_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec, *self._factors)
         if ctx.get('learned'):
             return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec, dq=self._model.flat_grad, accumulate=accumulate)
         return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec)
@@ -181,8 +199,9 @@ class JPEG(TFModel):
         with np.errstate(invalid='ignore'):
             return tables, ~np.isfinite(t) | (np.rint(t) < 1) | (np.rint(t) > 255)
 
-    def process_files(self, batch_x, subsampling='4:4:4', optimize=False, return_files=False):
-        """The real codec with exactly file_tables(): (float32 (n,h,w,3) batch libjpeg decodes, list of byte counts[, list of the
+    def process_files(self, batch_x, subsampling=None, optimize=False, return_files=False):
+        """The real codec with exactly file_tables(), at `subsampling` or (None) the model's own: (float32 (n,h,w,3) batch libjpeg
+        decodes, list of byte counts[, list of the
         files]) - what the learned tables, or the soft / sin / harmonic codec's, cost in bytes and do to the image once a standard
         encoder holds them.  Forward only: the real codec has no gradient (forward(training=True) of the libjpeg codec says the same)."""
         x = to_device(batch_x, self.device)
@@ -190,6 +209,8 @@ class JPEG(TFModel):
             raise NotImplementedError('the real codec has no gradient (the reference has none either): train on a differentiable '
                                       'codec, measure on this one')
         tables, _ = self.file_tables()
+        if subsampling is None:
+            subsampling = self.subsampling
         y, sizes = compress_batch(x, None, subsampling=subsampling, optimize=optimize, qtables=tables)
         if y.ndim == 3:
             raise ValueError('process_files needs an (n,h,w,3) batch')
@@ -199,15 +220,19 @@ class JPEG(TFModel):
         return y, sizes
 
     def __repr__(self):
+        sub = '' if self._factors == (1, 1) else ',subsampling="{}"'.format(self.subsampling)
         if self._codec_model is not None:              # models/jpeg.py:253-257
-            return 'JPEG(quality={},codec="{}",trainable={})'.format(self.quality, self.codec, bool(self.trainable))
-        return 'JPEG(quality={},codec="{}")'.format(self.quality, self.codec)
+            return 'JPEG(quality={},codec="{}",trainable={}{})'.format(self.quality, self.codec, bool(self.trainable), sub)
+        return 'JPEG(quality={},codec="{}"{})'.format(self.quality, self.codec, sub)
+
+    def _sub_suffix(self):
+        return '' if self._factors == (1, 1) else ' ' + self.subsampling
 
     def summary(self, quality=None):
-        return 'JPEG ({}) {}'.format(self.codec, self._quality_mode(quality))
+        return 'JPEG ({}) {}{}'.format(self.codec, self._quality_mode(quality), self._sub_suffix())
 
     def summary_compact(self, quality=None):
-        return 'JPEG ({}) {}'.format(self.codec, self._quality_mode(quality))
+        return 'JPEG ({}) {}{}'.format(self.codec, self._quality_mode(quality), self._sub_suffix())
 
     def _model_tables(self):
         """The codec model's own (luma, chroma) tables on the host: the learned weights with trainable=True, else the IJG tables of

@@ -552,6 +552,59 @@ def djpeg_bwd(x, gy, mask, qtab, rounding='soft', out=None, dq=None, accumulate=
     return gx
 
 
+def _djpeg_sub_shape(x, hs, vs):
+    """(n, h, w) of an NHW3 batch of whole MCUs at the sampling factors (2,1) = 4:2:2 or (2,2) = 4:2:0; a ValueError otherwise."""
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError('dJPEG expects NHW3 images')
+    if (hs, vs) not in ((2, 1), (2, 2)):
+        raise ValueError('sub-sampled dJPEG: sampling factors (2,1) or (2,2) expected, got ({},{}) - 4:4:4 is djpeg_fwd / '
+                         'djpeg_bwd'.format(hs, vs))
+    n, h, w, _ = x.shape
+    if h <= 0 or w <= 0 or h % (8 * vs) or w % (8 * hs):
+        raise ValueError('sub-sampled dJPEG needs whole MCUs: h % {} == 0 and w % {} == 0, got {} x {}'.format(8 * vs, 8 * hs, h, w))
+    return n, h, w
+
+
+def _djpeg_sub_views(buf, n, h, w, hs, vs):
+    """The (n,h/8,w/8,8,8) luma view and the (n,2,h/(8 vs),w/(8 hs),8,8) chroma view of an idx / xdq buffer."""
+    hb, wb, hcb, wcb = h // 8, w // 8, h // (8 * vs), w // (8 * hs)
+    return buf[:, :hb * wb * 64].view(n, hb, wb, 8, 8), buf[:, hb * wb * 64:].view(n, 2, hcb, wcb, 8, 8)
+
+
+def djpeg_sub_fwd(x, qtab, rounding='soft', hs=2, vs=2, want_mask=True, want_idx=False, want_xdq=False, out=None):
+    """Differentiable JPEG with chroma sub-sampling (include/nimg.h nimg_djpeg_sub_fwd): (y, mask, idx, xdq); idx and xdq are
+    (luma view, chroma view) pairs of one buffer each, laid out per image as [Y blocks | Cb blocks | Cr blocks]."""
+    _f32(x, qtab, out)
+    n, h, w = _djpeg_sub_shape(x, hs, vs)
+    y = torch.empty_like(x) if out is None else out
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if want_mask else None
+    per_image = (h // 8 * (w // 8) + 2 * (h // (8 * vs)) * (w // (8 * hs))) * 64
+    idx = torch.empty((n, per_image), dtype=torch.int16, device=x.device) if want_idx else None
+    xdq = torch.empty((n, per_image), dtype=torch.float32, device=x.device) if want_xdq else None
+    need = _lib.load().nimg_djpeg_sub_workspace_bytes(n, h, w, hs, vs, 0)
+    ws = _ws_current(x.device).get(need, x.device)
+    _lib.call('nimg_djpeg_sub_fwd', _p(x), _p(y), _p(qtab), _p(mask), _p(idx), _p(xdq), n, h, w, hs, vs, ROUNDING[rounding],
+              _p(ws), need, _stream())
+    return (y, mask, _djpeg_sub_views(idx, n, h, w, hs, vs) if want_idx else None,
+            _djpeg_sub_views(xdq, n, h, w, hs, vs) if want_xdq else None)
+
+
+def djpeg_sub_bwd(x, gy, mask, qtab, rounding='soft', hs=2, vs=2, out=None, dq=None, accumulate=False):
+    """gx = d loss / d x of djpeg_sub_fwd; with dq (a (2,8,8) or 128-element float32 buffer) also the gradient of trainable
+    quantisation tables, [luma, chroma (Cb + Cr)], (+)= when accumulate."""
+    _f32(x, gy, qtab, dq)
+    _chk(mask)
+    n, h, w = _djpeg_sub_shape(x, hs, vs)
+    gx = torch.empty_like(x) if out is None else out
+    if dq is not None and (dq.numel() != 128 or not dq.is_contiguous()):
+        raise ValueError('dq: 128 contiguous float32 values (2 x 8 x 8) expected')
+    need = _lib.load().nimg_djpeg_sub_workspace_bytes(n, h, w, hs, vs, 0 if dq is None else 1)
+    ws = _ws_current(x.device).get(need, x.device)
+    _lib.call('nimg_djpeg_sub_bwd', _p(x), _p(gy), _p(mask), _p(qtab), _p(gx), _p(dq), n, h, w, hs, vs, ROUNDING[rounding],
+              1 if accumulate else 0, _p(ws), need, _stream())
+    return gx
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # convolutions
 def conv2d(x, w, bias=None, x2=None, stride=1, padding='SAME', act=None, pad_mode=0, out=None, out2=None,

@@ -7,6 +7,8 @@ with autograd formulas:
 
     import neural_imaging_amd.torch_ops                     # registers the ops
     y = torch.ops.nimg.djpeg(x, qtab, 'soft')               # models/jpeg.py:91-159, DIFFERENTIABLE (nimg_djpeg_fwd / _bwd)
+    y = torch.ops.nimg.djpeg_sub(x, qtab, 'soft', 2, 2)     # the same with chroma sub-sampling, (hs, vs) = (2,1) 4:2:2 | (2,2) 4:2:0,
+                                                            #   DIFFERENTIABLE (nimg_djpeg_sub_fwd / _bwd)
     z = torch.ops.nimg.conv2d(x, w, b, 1, 'leaky_relu')      # Conv2D SAME (+bias, LeakyReLU 0.2), DIFFERENTIABLE at stride 1:
                                                             #   nimg_conv2d_* forward / input gradient / weight gradient
     c = torch.ops.nimg.cconv3(x, nf, 1)                     # ConstrainedConv2D core (models/layers.py:56-57), forward only
@@ -42,6 +44,9 @@ def _define():
     lib.define('djpeg(Tensor x, Tensor qtab, str rounding) -> Tensor')
     lib.define('djpeg_fwd(Tensor x, Tensor qtab, str rounding) -> (Tensor, Tensor)')
     lib.define('djpeg_bwd(Tensor x, Tensor gy, Tensor mask, Tensor qtab, str rounding) -> Tensor')
+    lib.define('djpeg_sub(Tensor x, Tensor qtab, str rounding, int hs, int vs) -> Tensor')
+    lib.define('djpeg_sub_fwd(Tensor x, Tensor qtab, str rounding, int hs, int vs) -> (Tensor, Tensor)')
+    lib.define('djpeg_sub_bwd(Tensor x, Tensor gy, Tensor mask, Tensor qtab, str rounding, int hs, int vs) -> Tensor')
     lib.define('conv2d(Tensor x, Tensor w, Tensor? bias, int stride, str act) -> Tensor')
     lib.define('conv2d_fwd(Tensor x, Tensor w, Tensor? bias, int stride, str act) -> Tensor')
     lib.define('conv2d_dgrad(Tensor dz, Tensor w, int h, int w_) -> Tensor')
@@ -81,6 +86,31 @@ class _DJpeg(torch.autograd.Function):
     def backward(ctx, gy):
         x, mask, qtab = ctx.saved_tensors
         return torch.ops.nimg.djpeg_bwd(x, gy, mask, qtab, ctx.rounding), None, None
+
+
+def _djpeg_sub_fwd(x, qtab, rounding, hs, vs):
+    _cuda_only(x, qtab)
+    y, mask, _, _ = ops.djpeg_sub_fwd(x.contiguous(), qtab.contiguous(), rounding, hs, vs, want_mask=True)
+    return y, mask
+
+
+def _djpeg_sub_bwd(x, gy, mask, qtab, rounding, hs, vs):
+    _cuda_only(x, gy)
+    return ops.djpeg_sub_bwd(x.contiguous(), gy.contiguous(), mask, qtab.contiguous(), rounding, hs, vs)
+
+
+class _DJpegSub(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, qtab, rounding, hs, vs):
+        y, mask = torch.ops.nimg.djpeg_sub_fwd(x, qtab, rounding, hs, vs)
+        ctx.save_for_backward(x, mask, qtab)
+        ctx.rounding, ctx.factors = rounding, (hs, vs)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mask, qtab = ctx.saved_tensors
+        return torch.ops.nimg.djpeg_sub_bwd(x, gy, mask, qtab, ctx.rounding, *ctx.factors), None, None, None, None
 
 
 def _conv2d(x, w, bias, stride, act):
@@ -142,6 +172,8 @@ def _register():
     impl = torch.library.Library(_LIB, 'IMPL', 'CUDA')
     impl.impl('djpeg_fwd', _djpeg_fwd)
     impl.impl('djpeg_bwd', _djpeg_bwd)
+    impl.impl('djpeg_sub_fwd', _djpeg_sub_fwd)
+    impl.impl('djpeg_sub_bwd', _djpeg_sub_bwd)
     impl.impl('conv2d', _conv2d)
     impl.impl('conv2d_fwd', _conv2d)
     impl.impl('conv2d_dgrad', _conv2d_dgrad)
@@ -153,6 +185,8 @@ def _register():
     auto = torch.library.Library(_LIB, 'IMPL', 'Autograd')
     auto.impl('djpeg', lambda x, qtab, rounding: _DJpeg.apply(x, qtab, rounding))
     impl.impl('djpeg', lambda x, qtab, rounding: _djpeg_fwd(x, qtab, rounding)[0])
+    auto.impl('djpeg_sub', lambda x, qtab, rounding, hs, vs: _DJpegSub.apply(x, qtab, rounding, hs, vs))
+    impl.impl('djpeg_sub', lambda x, qtab, rounding, hs, vs: _djpeg_sub_fwd(x, qtab, rounding, hs, vs)[0])
     auto.impl('conv2d', lambda x, w, bias, stride, act: _Conv2D.apply(x, w, bias, stride, act))
 
     def forward_only(name):
@@ -381,3 +415,11 @@ def conv2d(x, w, bias=None, stride=1, act=''):
 def djpeg(x, qtab, rounding='soft'):
     """Differentiable JPEG (models/jpeg.py:91-159) as a dispatcher op: torch.ops.nimg.djpeg."""
     return torch.ops.nimg.djpeg(x, qtab, rounding)
+
+
+def djpeg_sub(x, qtab, rounding='soft', subsampling='4:2:0'):
+    """Differentiable JPEG with chroma sub-sampling as a dispatcher op: torch.ops.nimg.djpeg_sub ('4:4:4' is djpeg)."""
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    if (hs, vs) == (1, 1):
+        return torch.ops.nimg.djpeg(x, qtab, rounding)
+    return torch.ops.nimg.djpeg_sub(x, qtab, rounding, hs, vs)

@@ -1,5 +1,7 @@
 """Stand-alone timing of the FAN front-end kernels at the bench shapes (320 images of 256x256), HIP events on the launch stream.
-   python tools/front_time.py [reps]      -> one line per kernel: ms per launch, GB/s against its algorithmic bytes"""
+   python tools/front_time.py [reps]      -> one line per kernel: ms per launch, GB/s against its algorithmic bytes
+   python tools/front_time.py reps rounds -> then the dJPEG rows again, `rounds` times round-robin (4:4:4 and the sub-sampled kernels
+                                             alternate): min / median / max ms per launch and the ratio of the medians to 4:4:4"""
 import importlib
 import os
 import sys
@@ -49,14 +51,43 @@ q = ops.qtables_device(80, dev)
 yj, mj, _, _ = ops.djpeg_fwd(xj, q, 'soft', want_mask=True)
 cases.append(('dJPEG fwd', lambda: ops.djpeg_fwd(xj, q, 'soft', want_mask=True), 25 * N * H * W))
 cases.append(('dJPEG bwd', lambda: ops.djpeg_bwd(xj, dc, mj, q, 'soft'), 37 * N * H * W))
-for name, fn, nbytes in cases:
-    fn()
-    torch.cuda.synchronize()
+# sub-sampled dJPEG (csrc/djpeg_sub.hip), two launches per direction; bytes per pixel: forward x 12 + reduced planes
+# written and read 2 * 8 / (hs vs) + x 12 + y 12 + mask 1; backward gy 12 + mask 1 + x 12 + planes written and read + x 12 + gy 12 +
+# mask 1 + gx 12 (the one-pixel ring of the gather is re-read from the caches)
+n_djpeg = 2
+for sub, (hs, vs) in (('4:2:2', (2, 1)), ('4:2:0', (2, 2))):
+    _, ms_, _, _ = ops.djpeg_sub_fwd(xj, q, 'soft', hs, vs, want_mask=True)
+    planes = 16 // (hs * vs)
+    cases.append(('dJPEG {} fwd'.format(sub), lambda hs=hs, vs=vs: ops.djpeg_sub_fwd(xj, q, 'soft', hs, vs, want_mask=True),
+                  (37 + planes) * N * H * W))
+    cases.append(('dJPEG {} bwd'.format(sub), lambda hs=hs, vs=vs, ms_=ms_: ops.djpeg_sub_bwd(xj, dc, ms_, q, 'soft', hs, vs),
+                  (62 + planes) * N * H * W))
+    n_djpeg += 2
+
+
+def time_once(fn):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(reps):
         fn()
     e1.record()
     torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / reps
+    return e0.elapsed_time(e1) / reps
+
+
+for name, fn, nbytes in cases:
+    fn()
+    torch.cuda.synchronize()
+    ms = time_once(fn)
     print('{:40s} {:8.3f} ms   {:7.0f} GB/s (algorithmic {:.0f} MB)'.format(name, ms, nbytes / ms / 1e6, nbytes / MB))
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+if rounds > 0:
+    times = {name: [] for name, _, _ in cases[-n_djpeg:]}
+    for _ in range(rounds):
+        for name, fn, _ in cases[-n_djpeg:]:
+            times[name].append(time_once(fn))
+    med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+    for name, _, nbytes in cases[-n_djpeg:]:
+        base = med['dJPEG fwd' if name.endswith('fwd') else 'dJPEG bwd']
+        print('{:40s} min {:7.3f}  median {:7.3f}  max {:7.3f} ms   {:6.1f} B/px  {:7.0f} GB/s   {:.2f} x 4:4:4'.format(
+            name, min(times[name]), med[name], max(times[name]), nbytes / (N * H * W), nbytes / med[name] / 1e6, med[name] / base))
