@@ -111,6 +111,30 @@ int nimg_djpeg_sub_fwd(const float* x, float* y, const float* qtab, uint8_t* mas
 int nimg_djpeg_sub_bwd(const float* x, const float* gy, const uint8_t* mask, const float* qtab, float* gx,
                        float* dq /* may be NULL */, int n, int h, int w, int hs, int vs, int rounding, int accumulate,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* Rate term of the 4:4:4 differentiable JPEG (csrc/djpeg_entropy.hip): the soft entropy the DCN trains against
+ * (helpers/tf_helpers.py:290-333), of the quantiser's OUTPUT e = quantise<rounding>(z), z = X / Q exactly as nimg_djpeg_fwd forms it
+ * (same float32 order, same division: with the modes that round, its idx output is e).  Code book: the 512 integers -255 .. 256
+ * (Quantization(latent_bpf=9), models/jpeg.py:89), v = 50, gamma = 25, eps = 1e-72; one pooled histogram of the N = 3 n h w values;
+ * weights, histogram, 1e-9 clip, re-normalisation and / 0.6931 in float64.  entropy: ONE float32 on the device (bits per value).
+ * The transform is recomputed from x; nothing of size N x 512 exists.  Values inside [-255.5, 256.5] see the five centres around
+ * the nearest one (every other centre weighs < 2e-33 of it), values outside all 512.
+ * workspace: nimg_djpeg_entropy_workspace_bytes(n, h, w) device bytes, 16-byte aligned (0 for an empty or refused shape); a shorter
+ * one is NIMG_ERR_WORKSPACE.  _fwd leaves dH / d mean_k there for _bwd: the workspace must stay untouched between the two (several
+ * _bwd calls may follow one _fwd).  h % 8, w % 8, a null pointer, a rounding mode out of range: NIMG_ERR_ARG.  The workgroups'
+ * partial histograms are summed in a fixed order; inside a workgroup the float64 LDS atomics arrive in any order, so two runs agree
+ * to the last bits of float64, not bit for bit.  Asynchronous on `stream`, capturable, no allocation, no synchronisation; n == 0 is
+ * a no-op. */
+size_t nimg_djpeg_entropy_workspace_bytes(int n, int h, int w);
+int nimg_djpeg_entropy_fwd(const float* x, const float* qtab, int n, int h, int w, int rounding, float* entropy,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* gx (+)= coef * d entropy / d x, plain autograd of the expression above: d H / d e from the estimator in float64, d e / d z the
+ * mode's backward surrogate as nimg_djpeg_bwd applies it (1 - cos(2 pi z) for SOFT and SIN, none for ROUND), d z / d X = 1 / Q, back
+ * through the DCT, the colour matrix and the 255.  dq (may be NULL): (2,8,8) float32 (+)= coef * [d H / d Q_luma, d H / d Q_chroma
+ * (Cb + Cr)] through d z / d Q = -z / Q - the layout and the fixed-order reduction of nimg_djpeg_bwd_dq; with dq the IEEE division.
+ * With SOFT the estimator is evaluated at integers, where its derivative vanishes: gx is ~1e-29. */
+int nimg_djpeg_entropy_bwd(const float* x, const float* qtab, int n, int h, int w, int rounding, float coef, float* gx,
+                           int accumulate_gx, float* dq /* 128 floats or NULL */, int accumulate_dq, void* workspace,
+                           size_t workspace_bytes, void* stream);
 /* IJG quality scaling - replaces jpeg_qtable, compression/jpeg_helpers.py:264-305.  HOST function: out64 is a host
  * pointer to 64 floats (row-major 8x8).  channel 0 = luma, >0 = chroma. */
 int nimg_jpeg_qtable(int quality, int channel, float* out64);

@@ -23,6 +23,9 @@ PROTOTYPES = {
     'nimg_djpeg_sub_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'nimg_djpeg_sub_fwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'nimg_djpeg_sub_bwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    'nimg_djpeg_entropy_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'nimg_djpeg_entropy_fwd': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'nimg_djpeg_entropy_bwd': (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_int, P, c_size_t, P]),
     'nimg_jpeg_qtable': (c_int, [c_int, c_int, P]),
     'nimg_conv2d_fwd': (c_int, [P, c_int, P, c_int, P, P, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),

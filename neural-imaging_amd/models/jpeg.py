@@ -13,6 +13,9 @@ New: JPEG.file_tables / JPEG.process_files run that real codec with the model's 
 differentiable codec divides by - so the two stand side by side at identical tables.
 New: subsampling='4:2:2' / '4:2:0' - the differentiable codec with the real codec's chroma sub-sampling (box down-sampling,
 libjpeg's triangle up-sampling; csrc/djpeg_sub.hip).  '4:4:4' (the default) is the reference's model.
+New: entropy_weight=w - the rate term the reference left commented out (:245-249, "takes too much memory"): the soft entropy of the
+quantised DCT coefficients (csrc/djpeg_entropy.hip), reported by process(return_entropy=True) and added to the
+gradients by backward(entropy_coef=).  None (the default) is the reference's model: the entropy is NaN and nothing else changes.
 """
 import numpy as np
 import torch
@@ -91,10 +94,20 @@ class DifferentiableJPEG(object):
 
 class JPEG(TFModel):
 
-    def __init__(self, quality=None, codec='soft', trainable=False, device=None, subsampling='4:4:4'):
+    def __init__(self, quality=None, codec='soft', trainable=False, device=None, subsampling='4:4:4', entropy_weight=None):
         super().__init__(device=device)
         if codec is not None and codec not in ['libjpeg', 'soft', 'sin', 'harmonic']:
             raise ValueError('Unsupported codec version: {}'.format(codec))
+        if entropy_weight is not None:
+            if isinstance(entropy_weight, bool) or not is_number(entropy_weight) or not entropy_weight >= 0:
+                raise ValueError('entropy_weight: None or a number >= 0 expected, got {!r}'.format(entropy_weight))
+            if codec == 'libjpeg':
+                raise ValueError('entropy_weight needs a differentiable codec: the libjpeg codec has no gradient, and its rate is '
+                                 'real bytes (compression/jpeg_helpers.py)')
+            if ops.jpeg_subsampling(subsampling) != (1, 1):
+                raise ValueError('entropy_weight: the rate term covers the 4:4:4 codec only, got subsampling="{}"'.format(subsampling))
+        self.entropy_weight = None if entropy_weight is None else float(entropy_weight)
+        self._entropy_ws = {}                    # (shape, device) -> workspace: allocated once, re-used by every step
         self.subsampling = subsampling
         self._factors = ops.jpeg_subsampling(subsampling)         # ValueError for anything but 4:4:4, 4:2:2, 4:2:0
         self._codec_model = None if codec == 'libjpeg' else DifferentiableJPEG(quality, codec, trainable=trainable,
@@ -154,10 +167,35 @@ class JPEG(TFModel):
             y, mask, _, _ = ops.djpeg_sub_fwd(x, q, self.codec, *self._factors, want_mask=training, out=out)
         else:
             y, mask, _, _ = ops.djpeg_fwd(x, q, self.codec, want_mask=training, out=out)
-        return y, ({'x': x, 'mask': mask, 'q': q, 'learned': learned} if training else None)
+        if not training:
+            return y, None
+        ctx = {'x': x, 'mask': mask, 'q': q, 'learned': learned}
+        if self.entropy_weight is not None:
+            ctx['entropy'], ctx['entropy_ws'] = self._entropy(x, q)
+        return y, ctx
 
-    def backward(self, ctx, dy, accumulate=False):
-        """d loss / d x; with trainable tables also fills (accumulate: adds to) their gradients in the model's gradient buffer."""
+    def _entropy(self, x, q):
+        """(entropy (1,) on the device, workspace) of the batch x at the tables q.  The workspace belongs to the model and serves
+        every call on the same shape (no per-step allocation: a captured step replays); it holds what backward() needs until the
+        next forward pass on that shape."""
+        key = (tuple(x.shape), str(x.device))
+        if key not in self._entropy_ws:
+            self._entropy_ws[key] = ops.djpeg_entropy_workspace(x)
+        return ops.djpeg_entropy_fwd(x, q, self.codec, ws=self._entropy_ws[key])
+
+    def backward(self, ctx, dy, accumulate=False, entropy_coef=0.0):
+        """d loss / d x; with trainable tables also fills (accumulate: adds to) their gradients in the model's gradient buffer.
+        entropy_coef (a model with entropy_weight): adds entropy_coef * d H / d x to the returned gradient and, with learned tables,
+        entropy_coef * d H / d Q to theirs."""
+        gx = self._backward_distortion(ctx, dy, accumulate)
+        if entropy_coef:
+            if ctx.get('entropy_ws') is None:
+                raise ValueError('entropy_coef needs a model with entropy_weight and the ctx of forward(training=True)')
+            ops.djpeg_entropy_bwd(ctx['x'], ctx['q'], ctx['entropy_ws'], entropy_coef, self.codec, out=gx, accumulate=True,
+                                  dq=self._model.flat_grad if ctx.get('learned') else None, accumulate_dq=True)
+        return gx
+
+    def _backward_distortion(self, ctx, dy, accumulate):
         if self._codec_model is None:
             raise NotImplementedError('the libjpeg codec has no gradient')
         if self._factors != (1, 1):
@@ -171,10 +209,15 @@ class JPEG(TFModel):
 
     def process(self, batch_x, quality=None, return_entropy=False):
         """Compress a batch (NHW3 rgb): number -> that quality; 2 numbers -> random integer in [lo, hi);
-        more -> random choice (models/jpeg.py:202-251).  Entropy is NaN, as in the reference (:245-249)."""
-        y, _ = self.forward(to_device(batch_x, self.device), quality)
-        y = DeviceArray(y)
-        return (y, np.nan) if return_entropy else y
+        more -> random choice (models/jpeg.py:202-251).  Entropy is NaN, as in the reference (:245-249) - unless the model has an
+        entropy_weight: then the soft entropy of the quantised DCT coefficients at the tables this call used."""
+        x = to_device(batch_x, self.device)
+        if self.entropy_weight is None or not return_entropy:
+            y, _ = self.forward(x, quality)
+            y = DeviceArray(y)
+            return (y, np.nan) if return_entropy else y
+        y, ctx = self.forward(x, quality, training=True)          # the ctx carries the tables the (possibly random) quality chose
+        return DeviceArray(y), float(ctx['entropy'][0])
 
     # the real codec with the model's own tables (DESIGN.md section 4h) ---------------------------------------------------
     def file_tables(self):
@@ -222,11 +265,13 @@ class JPEG(TFModel):
     def __repr__(self):
         sub = '' if self._factors == (1, 1) else ',subsampling="{}"'.format(self.subsampling)
         if self._codec_model is not None:              # models/jpeg.py:253-257
-            return 'JPEG(quality={},codec="{}",trainable={}{})'.format(self.quality, self.codec, bool(self.trainable), sub)
+            ew = '' if self.entropy_weight is None else ',entropy_weight={}'.format(self.entropy_weight)
+            return 'JPEG(quality={},codec="{}",trainable={}{}{})'.format(self.quality, self.codec, bool(self.trainable), sub, ew)
         return 'JPEG(quality={},codec="{}"{})'.format(self.quality, self.codec, sub)
 
     def _sub_suffix(self):
-        return '' if self._factors == (1, 1) else ' ' + self.subsampling
+        sub = '' if self._factors == (1, 1) else ' ' + self.subsampling
+        return sub if self.entropy_weight is None else '{} H+{}'.format(sub, self.entropy_weight)
 
     def summary(self, quality=None):
         return 'JPEG ({}) {}{}'.format(self.codec, self._quality_mode(quality), self._sub_suffix())

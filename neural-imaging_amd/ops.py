@@ -552,6 +552,45 @@ def djpeg_bwd(x, gy, mask, qtab, rounding='soft', out=None, dq=None, accumulate=
     return gx
 
 
+def djpeg_entropy_workspace(x):
+    """A workspace of its own for djpeg_entropy_fwd / _bwd on the batch x: it carries dH / d mean_k from the forward to the backward
+    pass, so it is NOT the per-stream scratch buffer every other op may overwrite."""
+    n, h, w, _ = x.shape
+    return torch.empty(max(int(_lib.load().nimg_djpeg_entropy_workspace_bytes(n, h, w)), 256), dtype=torch.uint8, device=x.device)
+
+
+def djpeg_entropy_fwd(x, qtab, rounding='soft', ws=None, out=None):
+    """Soft entropy (bits per value) of the quantised DCT coefficients of the 4:4:4 differentiable JPEG (include/nimg.h
+    nimg_djpeg_entropy_fwd): (entropy (1,) float32 on the device, ws).  ws: the workspace of an earlier call on the
+    same shape (None: a new one); it has to stay untouched until the last djpeg_entropy_bwd of this forward pass."""
+    _f32(x, qtab, out)
+    _chk(ws)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError('dJPEG expects NHW3 images')
+    n, h, w, _ = x.shape
+    if ws is None:
+        ws = djpeg_entropy_workspace(x)
+    ent = torch.empty(1, dtype=torch.float32, device=x.device) if out is None else out
+    _lib.call('nimg_djpeg_entropy_fwd', _p(x), _p(qtab), n, h, w, ROUNDING[rounding], _p(ent), _p(ws), ws.numel(), _stream())
+    return ent, ws
+
+
+def djpeg_entropy_bwd(x, qtab, ws, coef, rounding='soft', out=None, accumulate=False, dq=None, accumulate_dq=False):
+    """gx = coef * d entropy / d x (added to `out` when accumulate) after djpeg_entropy_fwd(x, qtab, rounding, ws); with dq (a (2,8,8)
+    or 128-element float32 buffer) also coef * the gradient of trainable tables, [luma, chroma (Cb + Cr)], (+)= when accumulate_dq."""
+    _f32(x, qtab, out, dq)
+    _chk(ws)
+    n, h, w, _ = x.shape
+    if accumulate and out is None:
+        raise ValueError('accumulate=True needs the gradient to add to (out=)')
+    gx = torch.empty_like(x) if out is None else out
+    if dq is not None and (dq.numel() != 128 or not dq.is_contiguous()):
+        raise ValueError('dq: 128 contiguous float32 values (2 x 8 x 8) expected')
+    _lib.call('nimg_djpeg_entropy_bwd', _p(x), _p(qtab), n, h, w, ROUNDING[rounding], float(coef), _p(gx), 1 if accumulate else 0,
+              _p(dq), 1 if accumulate_dq else 0, _p(ws), ws.numel(), _stream())
+    return gx
+
+
 def _djpeg_sub_shape(x, hs, vs):
     """(n, h, w) of an NHW3 batch of whole MCUs at the sampling factors (2,1) = 4:2:2 or (2,2) = 4:2:0; a ValueError otherwise."""
     if x.dim() != 4 or x.shape[3] != 3:

@@ -9,6 +9,8 @@ with autograd formulas:
     y = torch.ops.nimg.djpeg(x, qtab, 'soft')               # models/jpeg.py:91-159, DIFFERENTIABLE (nimg_djpeg_fwd / _bwd)
     y = torch.ops.nimg.djpeg_sub(x, qtab, 'soft', 2, 2)     # the same with chroma sub-sampling, (hs, vs) = (2,1) 4:2:2 | (2,2) 4:2:0,
                                                             #   DIFFERENTIABLE (nimg_djpeg_sub_fwd / _bwd)
+    H = torch.ops.nimg.djpeg_entropy(x, qtab, 'sin')        # soft entropy of the quantised DCT coefficients, DIFFERENTIABLE in x
+                                                            #   (nimg_djpeg_entropy_fwd / _bwd)
     z = torch.ops.nimg.conv2d(x, w, b, 1, 'leaky_relu')      # Conv2D SAME (+bias, LeakyReLU 0.2), DIFFERENTIABLE at stride 1:
                                                             #   nimg_conv2d_* forward / input gradient / weight gradient
     c = torch.ops.nimg.cconv3(x, nf, 1)                     # ConstrainedConv2D core (models/layers.py:56-57), forward only
@@ -47,6 +49,9 @@ def _define():
     lib.define('djpeg_sub(Tensor x, Tensor qtab, str rounding, int hs, int vs) -> Tensor')
     lib.define('djpeg_sub_fwd(Tensor x, Tensor qtab, str rounding, int hs, int vs) -> (Tensor, Tensor)')
     lib.define('djpeg_sub_bwd(Tensor x, Tensor gy, Tensor mask, Tensor qtab, str rounding, int hs, int vs) -> Tensor')
+    lib.define('djpeg_entropy(Tensor x, Tensor qtab, str rounding) -> Tensor')
+    lib.define('djpeg_entropy_fwd(Tensor x, Tensor qtab, str rounding) -> (Tensor, Tensor)')
+    lib.define('djpeg_entropy_bwd(Tensor x, Tensor qtab, Tensor ws, str rounding) -> Tensor')
     lib.define('conv2d(Tensor x, Tensor w, Tensor? bias, int stride, str act) -> Tensor')
     lib.define('conv2d_fwd(Tensor x, Tensor w, Tensor? bias, int stride, str act) -> Tensor')
     lib.define('conv2d_dgrad(Tensor dz, Tensor w, int h, int w_) -> Tensor')
@@ -113,6 +118,34 @@ class _DJpegSub(torch.autograd.Function):
         return torch.ops.nimg.djpeg_sub_bwd(x, gy, mask, qtab, ctx.rounding, *ctx.factors), None, None, None, None
 
 
+def _djpeg_entropy_fwd(x, qtab, rounding):
+    _cuda_only(x, qtab)
+    ent, ws = ops.djpeg_entropy_fwd(x.contiguous(), qtab.contiguous(), rounding)
+    return ent.reshape(()), ws
+
+
+def _djpeg_entropy_bwd(x, qtab, ws, rounding):
+    _cuda_only(x, qtab, ws)
+    return ops.djpeg_entropy_bwd(x.contiguous(), qtab.contiguous(), ws, 1.0, rounding)
+
+
+class _DJpegEntropy(torch.autograd.Function):
+    """Soft entropy of the quantised DCT coefficients; gradient to x, none to qtab - as djpeg."""
+
+    @staticmethod
+    def forward(ctx, x, qtab, rounding):
+        ent, ws = torch.ops.nimg.djpeg_entropy_fwd(x, qtab, rounding)
+        ctx.save_for_backward(x, qtab, ws)
+        ctx.rounding = rounding
+        return ent
+
+    @staticmethod
+    def backward(ctx, gh):
+        x, qtab, ws = ctx.saved_tensors
+        # the incoming gradient stays on the device: d H / d x at coef = 1, scaled by it (no host read of gh)
+        return torch.ops.nimg.djpeg_entropy_bwd(x, qtab, ws, ctx.rounding) * gh, None, None
+
+
 def _conv2d(x, w, bias, stride, act):
     _cuda_only(x, w, bias)
     return ops.conv2d(x.contiguous(), w.contiguous(), None if bias is None else bias.contiguous(), stride=stride,
@@ -174,6 +207,8 @@ def _register():
     impl.impl('djpeg_bwd', _djpeg_bwd)
     impl.impl('djpeg_sub_fwd', _djpeg_sub_fwd)
     impl.impl('djpeg_sub_bwd', _djpeg_sub_bwd)
+    impl.impl('djpeg_entropy_fwd', _djpeg_entropy_fwd)
+    impl.impl('djpeg_entropy_bwd', _djpeg_entropy_bwd)
     impl.impl('conv2d', _conv2d)
     impl.impl('conv2d_fwd', _conv2d)
     impl.impl('conv2d_dgrad', _conv2d_dgrad)
@@ -187,6 +222,8 @@ def _register():
     impl.impl('djpeg', lambda x, qtab, rounding: _djpeg_fwd(x, qtab, rounding)[0])
     auto.impl('djpeg_sub', lambda x, qtab, rounding, hs, vs: _DJpegSub.apply(x, qtab, rounding, hs, vs))
     impl.impl('djpeg_sub', lambda x, qtab, rounding, hs, vs: _djpeg_sub_fwd(x, qtab, rounding, hs, vs)[0])
+    auto.impl('djpeg_entropy', lambda x, qtab, rounding: _DJpegEntropy.apply(x, qtab, rounding))
+    impl.impl('djpeg_entropy', lambda x, qtab, rounding: _djpeg_entropy_fwd(x, qtab, rounding)[0])
     auto.impl('conv2d', lambda x, w, bias, stride, act: _Conv2D.apply(x, w, bias, stride, act))
 
     def forward_only(name):
@@ -415,6 +452,12 @@ def conv2d(x, w, bias=None, stride=1, act=''):
 def djpeg(x, qtab, rounding='soft'):
     """Differentiable JPEG (models/jpeg.py:91-159) as a dispatcher op: torch.ops.nimg.djpeg."""
     return torch.ops.nimg.djpeg(x, qtab, rounding)
+
+
+def djpeg_entropy(x, qtab, rounding='sin'):
+    """Soft entropy of the quantised DCT coefficients of the 4:4:4 codec as a dispatcher op, differentiable in x:
+    torch.ops.nimg.djpeg_entropy.  With 'soft' the gradient vanishes (the estimator is evaluated at integers)."""
+    return torch.ops.nimg.djpeg_entropy(x, qtab, rounding)
 
 
 def djpeg_sub(x, qtab, rounding='soft', subsampling='4:2:0'):

@@ -97,7 +97,8 @@ def validate_dcn(dcn, data, out_directory=None, savefig=False, epoch=0, show_ref
 
 def validate_jpeg(jpeg, data, batch_size=1):
     """Mean SSIM / PSNR of the differentiable JPEG codec over the validation images, `batch_size` at a time (the tail dropped);
-    the entropy is NaN, as JPEG.process reports it (models/jpeg.py:245-249)."""
+    the entropy is what JPEG.process reports: NaN as in the reference (models/jpeg.py:245-249), or - for a model built with an
+    entropy_weight - the mean over the batches of the soft entropy of the quantised DCT coefficients (bits per value)."""
     from ..models.jpeg import JPEG
     if not isinstance(jpeg, JPEG):
         raise ValueError('Codec needs to be as instance of {} but is {}'.format(JPEG, getattr(jpeg, 'class_name', type(jpeg))))

@@ -264,11 +264,15 @@ class ManipulationClassification(object):
 
     # -- training ------------------------------------------------------------------------------------------------
     def _codec_forward(self, c, training=False):
-        """-> (C, entropy or None, ctx); the learned codec returns its entropy, JPEG has none (jpeg.py:245-249)."""
+        """-> (C, entropy or None, ctx); the learned codec returns its entropy, JPEG has none (jpeg.py:245-249) unless it was built
+        with an entropy_weight (models/jpeg.py): then the soft entropy of its quantised DCT coefficients."""
         if self.codec is None:
             return c, None, None
         if self._is_dcn:
             return self.codec.forward(c, training=training)
+        if getattr(self.codec, 'entropy_weight', None) is not None:
+            C, ctx = self.codec.forward(c, training=True)          # the entropy travels in the training ctx
+            return C, ctx['entropy'], (ctx if training else None)
         C, ctx = self.codec.forward(c, training=training)
         return C, None, ctx
 
@@ -355,7 +359,13 @@ class ManipulationClassification(object):
                         dc_direct = torch.empty_like(c)
                         ops.mse255(c, C, grad_scale=lam, grad_out=dc_direct, accumulate=False)       # d/dc
                     loss_dcn = (mse, None)
-                dc = self.codec.backward(cctx, dC)           # fills the table gradients when the tables are trainable
+                rate_w = getattr(self.codec, 'entropy_weight', None) if train_dcn else None
+                if rate_w is not None:
+                    # codec term lambda_dcn * (MSE(c, C) + w H): H is a MEAN over this rank's batch, averaged over ranks like the MSE
+                    loss_dcn = (mse, entropy)
+                    dc = self.codec.backward(cctx, dC, entropy_coef=float(lambda_dcn) * rate_w)
+                else:
+                    dc = self.codec.backward(cctx, dC)       # fills the table gradients when the tables are trainable
                 if dc_direct is not None:
                     ops.add(dc, dc_direct, out=dc)
                 if train_dcn:
@@ -422,6 +432,8 @@ class ManipulationClassification(object):
         dcn_value = np.nan
         if loss_dcn is not None and loss_dcn[1] is None:       # JPEG with trainable tables: MeanSquaredError on [0,1] images
             dcn_value = _LazySum(torch.zeros_like(loss_dcn[0]), loss_dcn[0], 1.0 / (255.0 * 255.0))
+        elif loss_dcn is not None and not self._is_dcn:        # ... with a rate term: MSE / 255^2 + w H
+            dcn_value = _LazySum(loss_dcn[0], loss_dcn[1], self.codec.entropy_weight, 1.0 / (255.0 * 255.0))
         elif loss_dcn is not None:         # codec.loss = l2 + w H, read from the device only when somebody looks at it
             dcn_value = _LazySum(loss_dcn[0], loss_dcn[1], self.codec._h.entropy_weight)
         loss = _LazyLoss(loss_ce, loss_nip, float(lambda_nip) if 'nip' in self._trainable else 0.0,
@@ -513,15 +525,16 @@ class _JpegManipulation(object):
 
 
 class _LazySum(DeviceArray):
-    """a + w * b of two device scalars, evaluated on the host only when somebody reads it."""
-    __slots__ = ('a', 'b', 'w')
+    """wa * a + w * b of two device scalars, evaluated on the host only when somebody reads it."""
+    __slots__ = ('a', 'b', 'w', 'wa')
 
-    def __init__(self, a, b, w):
+    def __init__(self, a, b, w, wa=1.0):
         self.t = a
-        self.a, self.b, self.w = a, b, float(w)
+        self.a, self.b, self.w, self.wa = a, b, float(w), float(wa)
 
     def numpy(self):
-        return np.asarray(float(self.a.detach().cpu().reshape(())) + self.w * float(self.b.detach().cpu().reshape(())))
+        a = float(self.a.detach().cpu().reshape(()))
+        return np.asarray((a if self.wa == 1.0 else self.wa * a) + self.w * float(self.b.detach().cpu().reshape(())))
 
     def __float__(self):
         return float(self.numpy())
