@@ -273,6 +273,21 @@ int nimg_adam_step(float* params, const float* grads, float* m, float* v, long c
  * captured hipGraph replays - the host refreshes *lr_t before every replay, the launch itself never changes. */
 int nimg_adam_step_dev(float* params, const float* grads, float* m, float* v, long count, const float* lr_t, float beta1,
                        float beta2, float eps, float grad_scale, const int* skip_flag, void* stream);
+/* The same update (lr_t != NULL: the rate from device memory, lr and step unused; else from lr and step on the host) which, in
+ * the same launch, writes both bf16 images of every 4-D weight from the updated values: image_table is the table of
+ * nimg_conv_weights_bf16_batch with its entries in pairs - 2j = the mode-0, 2j + 1 = the mode-1 image of weight j - and the
+ * weights inside [params, params + count), ascending and apart (the caller's duty: the table is device memory).  params, m, v and
+ * the images get the bytes that nimg_adam_step[_dev] followed by nimg_conv_weights_bf16_batch give; a set skip_flag writes
+ * nothing at all.
+ * cc_kernel (optional): one of the table's weights, a ConstrainedConv2D kernel (cc_ks, cc_ks, cc_channels, cc_channels) of at
+ * most 4096 values.  The workgroup that updates it also writes cc_nf = nimg_constrained_kernel_fwd(updated kernel, cc_strength)
+ * and, where cc_nft is given, cc_nft = nimg_conv_flip_weights(cc_nf), both byte for byte.  A kernel that is not in the table
+ * with these dimensions is updated like any other value and neither is written.
+ * Purely added: NIMG_ABI_VERSION stays. */
+int nimg_adam_step_images(float* params, const float* grads, float* m, float* v, long count, float lr, const float* lr_t,
+                          float beta1, float beta2, float eps, int step, float grad_scale, const int* skip_flag,
+                          const void* image_table, int n_entries, const float* cc_kernel, float* cc_nf, float* cc_nft,
+                          int cc_ks, int cc_channels, float cc_strength, void* stream);
 /* flag[0] |= 1 if any gradient is NaN (device-side version of workflows/manipulation_classification.py:281-282) */
 int nimg_nan_flag(const float* g, long count, int* flag, void* stream);
 /* flag / scalar bookkeeping of a training step on the library's own kernels: mode 0 dst[0 .. n) = value, mode 1 dst[i] =
@@ -515,6 +530,9 @@ int nimg_conv5c3_bf16(const float* in, const float* w, float* out, int n, int h,
 int nimg_cconv3(const float* in, const float* w, float* out_f32, void* out_c4, int n, int h, int w_, int pad_mode,
                 void* stream);
 int nimg_cconv3_dgrad_border(const float* dc, const float* nf, float* dx, int n, int h, int w_, void* stream);
+/* The same terms added to dx in the same order, so bit for bit the same result, with the strips of dc that a stretch of the
+ * border needs staged in LDS (one workgroup per 64 border positions) instead of one dependent L2 read per tap. */
+int nimg_cconv3_dgrad_border_strips(const float* dc, const float* nf, float* dx, int n, int h, int w_, void* stream);
 /* First FAN convolution in throughput mode, models/forensics.py:69-70: Conv2D(32, 5x5, SAME) + bias + LeakyReLU(alpha) +
  * MaxPool2D(2) in one pass over the bf16 {c0,c1,c2,1} pixels of nimg_cconv3 (bf16 MFMA operands, float32 accumulation).
  * c4 (n,h,w,4) bf16; w (5,5,3,32) float32 HWIO; bias (32) or NULL; pooled (n,h/2,w/2,32) bf16 (out_bf16 = 1) or float32;

@@ -59,6 +59,8 @@ PROTOTYPES = {
     'nimg_fan_head_bwd': (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P]),
     'nimg_adam_step': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_int, c_float, P, P]),
     'nimg_adam_step_dev': (c_int, [P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, P, P]),
+    'nimg_adam_step_images': (c_int, [P, P, P, P, c_long, c_float, P, c_float, c_float, c_float, c_int, c_float, P, P, c_int, P, P, P,
+                                    c_int, c_int, c_float, P]),
     'nimg_conv3_rows_bf16': (c_int, [P, c_int, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
     'nimg_conv3_rows_d2s_bf16': (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P]),
     'nimg_conv2d_wgrad_bf16_deferred': (c_int, [P, c_int, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -149,6 +151,7 @@ PROTOTYPES = {
     'nimg_cconv3': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     'nimg_conv5c3_bf16': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'nimg_cconv3_dgrad_border': (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    'nimg_cconv3_dgrad_border_strips': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'nimg_conv1_pool_fwd_c4': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P]),
     'nimg_conv1_wgrad_c4_workspace_bytes': (c_size_t, []),
     'nimg_conv1_wgrad_c4': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),

@@ -3,31 +3,16 @@
 // with M the centre mask on the (i,i) diagonal (helpers/kernels.py:117-123).  Layout (kh,kw,Cin,Cout), 5x5x3x3 = 225
 // elements; a single workgroup.  The convolution itself (SYMMETRIC pad 2 + VALID conv, layers.py:56-57) runs on the
 // generic conv kernels with pad_mode = SYMMETRIC.
-#include "common.h"
+#include "constrained.h"
 
 namespace {
 
-__device__ __forceinline__ bool centre_mask(int e, int ks, int c) {
-    // e indexes (kh,kw,ci,co) flattened
-    const int co = e % c, ci = (e / c) % c, kw = (e / (c * c)) % ks, kh = e / (c * c * ks);
-    return kh == ks / 2 && kw == ks / 2 && ci == co;
-}
+using nimg::centre_mask;
 
 __global__ __launch_bounds__(256) void constrained_fwd_kernel(const float* __restrict__ k, float* __restrict__ nf,
                                                               int ks, int c, float strength) {
     __shared__ float df[16];
-    const int total = ks * ks * c * c, tid = threadIdx.x;
-    if (tid < c) {
-        float s = 0.f;
-        for (int e = tid; e < total; e += c)            // all elements with co == tid
-            if (!centre_mask(e, ks, c)) s += k[e];
-        df[tid] = s;
-    }
-    __syncthreads();
-    for (int e = tid; e < total; e += blockDim.x) {
-        const bool m = centre_mask(e, ks, c);
-        nf[e] = m ? -strength : strength * k[e] / df[e % c];
-    }
+    nimg::constrained_normalise(k, nf, nullptr, df, ks, c, strength);
 }
 
 __global__ __launch_bounds__(256) void constrained_bwd_kernel(const float* __restrict__ k,

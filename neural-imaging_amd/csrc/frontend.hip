@@ -246,6 +246,100 @@ __global__ void cdgrad_border_kernel(const float* __restrict__ dc, const float* 
     }
 }
 
+// The same terms in the same order (iu, iv, ky, kx, o: one fmaf chain per output value, so not a bit changes), read from LDS.
+// Every pixel of dc that a mirror term reads lies in the 2-pixel ring itself or, at a corner, within 4 pixels of it - so a unit
+// of 64 positions along one side x 2 pixels deep needs a strip of 4 x 68 (top / bottom) or 68 x 2 (left / right) pixels, which
+// the workgroup stages with coalesced loads next to the 225 filter values.  In cdgrad_border_kernel each of the ~30 taps of a
+// corner pixel was a dependent round trip to L2 (29 us for 320 images of 256 x 256 with 650 k threads that had little to do).
+// Unit index = image * (2 xchunks + 2 ychunks) + {top chunks, bottom chunks, left chunks, right chunks}; rows 0, 1, H-2, H-1
+// belong to the top / bottom units in full, the columns 0, 1, W-2, W-1 of the rows between them to the left / right units.
+constexpr int BSTRIP = 64;                                 // border positions per unit
+constexpr int BTILE = 4 * (BSTRIP + 4);                    // pixels per staged strip, either orientation
+__global__ __launch_bounds__(2 * BSTRIP) void cdgrad_border_strip_kernel(const float* __restrict__ dc, const float* __restrict__ nf,
+                                                                         float* __restrict__ dx, int N, int H, int W,
+                                                                         int xchunks, int ychunks) {
+    __shared__ float tile[BTILE * 3];
+    __shared__ float wl[225];
+    constexpr int NT = 2 * BSTRIP, SLOTS = (BTILE * 3 + NT - 1) / NT;
+    const int tid = threadIdx.x;
+    // every global load of the workgroup - filter and strip - is issued before the first one is waited for: clamped addresses
+    // and no condition on the load (hipcc turns a select behind a load into a branch around it and waits for each on its own:
+    // seven serial round trips to HBM, 25 us for the launch)
+    const float w0 = nf[tid], w1 = nf[tid + NT < 225 ? tid + NT : 224];
+    bool first = true;
+    const int per = 2 * xchunks + 2 * ychunks;
+    const long units = (long)N * per;
+    for (long unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const int n = (int)(unit / per);
+        int k = (int)(unit % per);
+        const bool horiz = k < 2 * xchunks;
+        int ry0, cx0, C, cnt, y, x;                        // cnt: floats of the strip
+        bool live;
+        if (horiz) {
+            const int far = k / xchunks, x0 = (k % xchunks) * BSTRIP;
+            ry0 = far ? H - 4 : 0; cx0 = x0 - 2; C = BSTRIP + 4; cnt = 4 * (BSTRIP + 4) * 3;
+            x = x0 + (tid & (BSTRIP - 1));
+            y = (far ? H - 2 : 0) + tid / BSTRIP;
+            live = x < W;
+        } else {
+            k -= 2 * xchunks;
+            const int far = k / ychunks, y0 = 2 + (k % ychunks) * BSTRIP;
+            ry0 = y0 - 2; cx0 = far ? W - 2 : 0; C = 2; cnt = (BSTRIP + 4) * 2 * 3;
+            y = y0 + (tid >> 1);
+            x = (far ? W - 2 : 0) + (tid & 1);
+            live = y < H - 2;
+        }
+        float sv[SLOTS];
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const int i = tid + NT * s < cnt ? tid + NT * s : cnt - 1;
+            const int r = horiz ? i / ((BSTRIP + 4) * 3) : i / 6, j = horiz ? i % ((BSTRIP + 4) * 3) : i % 6;
+            const int gy = ry0 + r, gx = cx0 + j / 3;
+            const int cy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), cx = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+            sv[s] = dc[(((long)n * H + cy) * W + cx) * 3 + j % 3];       // outside the image: a copy of the edge, never read
+        }
+        __syncthreads();                                   // the previous unit's readers
+        if (first) {
+            wl[tid] = w0;
+            if (tid + NT < 225) wl[tid + NT] = w1;
+            first = false;
+        }
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+            if (tid + NT * s < cnt) tile[tid + NT * s] = sv[s];
+        __syncthreads();
+        if (!live) continue;
+        int us[3], vs[3], nu = 0, nv = 0;
+        us[nu++] = y + 2;
+        if (y < 2) us[nu++] = 1 - y;
+        if (y >= H - 2) us[nu++] = 2 * H + 1 - y;
+        vs[nv++] = x + 2;
+        if (x < 2) vs[nv++] = 1 - x;
+        if (x >= W - 2) vs[nv++] = 2 * W + 1 - x;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        for (int iu = 0; iu < nu; ++iu)
+            for (int iv = 0; iv < nv; ++iv) {
+                if (iu == 0 && iv == 0) continue;               // the direct term belongs to the main kernel
+                const int u = us[iu], v = vs[iv];
+                const int ky0 = u - (H - 1) > 0 ? u - (H - 1) : 0, ky1 = u < 4 ? u : 4;        // 0 <= u - ky < H
+                const int kx0 = v - (W - 1) > 0 ? v - (W - 1) : 0, kx1 = v < 4 ? v : 4;
+                for (int ky = ky0; ky <= ky1; ++ky)
+                    for (int kx = kx0; kx <= kx1; ++kx) {
+                        const float* g = tile + ((u - ky - ry0) * C + (v - kx - cx0)) * 3;
+                        const float* wv = wl + (ky * 5 + kx) * 9;            // [i][o]
+#pragma unroll
+                        for (int o = 0; o < 3; ++o) {
+                            a0 = fmaf(g[o], wv[o], a0);
+                            a1 = fmaf(g[o], wv[3 + o], a1);
+                            a2 = fmaf(g[o], wv[6 + o], a2);
+                        }
+                    }
+            }
+        float* d = dx + (((long)n * H + y) * W + x) * 3;
+        d[0] += a0; d[1] += a1; d[2] += a2;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // First FAN convolution, throughput mode: 5x5, 3 -> 32, SAME (zeros), + bias + LeakyReLU + MaxPool2D(2) in one pass
 // (models/forensics.py:69-70) over the 8-byte bf16 pixels {c0, c1, c2, 1} written by cconv_kernel.
@@ -1090,6 +1184,17 @@ int nimg_cconv3_dgrad_border(const float* dc, const float* nf, float* dx, int n,
     const long g = (total + 255) / 256;
     hipLaunchKernelGGL(cdgrad_border_kernel, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, (hipStream_t)stream, dc, nf,
                        dx, n, h, wd);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_cconv3_dgrad_border_strips(const float* dc, const float* nf, float* dx, int n, int h, int wd, void* stream) {
+    if (n == 0) return NIMG_OK;
+    if (!dc || !nf || !dx || n < 0 || h < 4 || wd < 4) return NIMG_ERR_ARG;
+    const int xchunks = (wd + BSTRIP - 1) / BSTRIP, ychunks = (h - 4 + BSTRIP - 1) / BSTRIP;
+    const long units = (long)n * (2 * xchunks + 2 * ychunks);
+    hipLaunchKernelGGL(cdgrad_border_strip_kernel, dim3((unsigned)(units > 65536 ? 65536 : units)), dim3(2 * BSTRIP), 0,
+                       (hipStream_t)stream, dc, nf, dx, n, h, wd, xchunks, ychunks);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }

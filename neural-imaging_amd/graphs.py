@@ -21,6 +21,18 @@ import torch
 from . import ops, parallel
 
 
+def _refresh_stale_images(stores):
+    """A step captured while the bf16 weight images were current (models/tfmodel.ParamStore: the Adam launch of the step before
+    left them so) holds no image launch - its own Adam launch keeps them current from replay to replay.  Weights written between
+    two replays (a torch write through a parameter view, a checkpoint load) make them stale: then they are rebuilt here, eagerly,
+    on the stream the replay follows on.  Nothing is launched while they are current."""
+    for store in stores:
+        if store is not None and getattr(store, 'images', None) is not None:
+            store.refresh_images()
+            if ops.ADAM_IMAGES and ops.ADAM_CCONV and ops.COMPUTE == 'bf16' and store.constrained is not None:
+                store.constrained_filter()       # (the same for the normalised ConstrainedConv2D filter and its flipped form)
+
+
 class CapturedStep(object):
 
     def __init__(self, flow, batch_x, batch_y, learning_rate=1e-4, warmup=3, **kw):
@@ -78,6 +90,7 @@ class CapturedStep(object):
     def step(self):
         self.t += 1
         self._set_rate(self.t)
+        _refresh_stale_images(getattr(getattr(self.flow, name, None), '_model', None) for name in ('nip', 'fan', 'codec'))
         self.graph.replay()
         self.flow._step = self.t
         return self.out
@@ -136,6 +149,7 @@ class CapturedModelStep(object):
     def step(self):
         self.t += 1
         self._set_rate(self.t)
+        _refresh_stale_images([self.model._model])
         self.graph.replay()
         self.model._model.step = self.t
         return self.out

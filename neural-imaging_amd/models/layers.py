@@ -212,11 +212,24 @@ class ConstrainedConv2D(object):
 
     def init(self, store, gen=None):
         store.p[self.name + '/kernel'].copy_(torch.from_numpy(hk.residual_init_filter().astype(np.float32)))
+        if hasattr(store, 'register_constrained'):
+            store.register_constrained(self.name + '/kernel', self.strength)
+
+    _flip = (None, None)         # (normalised filter handed out by the last forward, its flipped form or None)
 
     def forward(self, store, x, c4_only=False):
         """-> (y, normalised filter): y float32 (N,H,W,3), or - c4_only, the throughput-mode front end - the same image as
         bf16 {y0,y1,y2,1} pixels (N,H,W,4), the only form the row-band conv1 kernels read."""
-        nf = ops.constrained_kernel(store.p[self.name + '/kernel'], self.strength)
+        cc = getattr(store, 'constrained', None)
+        if ops.ADAM_IMAGES and ops.ADAM_CCONV and ops.COMPUTE == 'bf16' and cc is not None and \
+                cc['kernel'] is store.p[self.name + '/kernel'] and cc['strength'] == self.strength:
+            # throughput mode: the filter and its flipped form as the last Adam launch left them in the store's buffers (made
+            # there only if a weight was written since) - valid until the next update, which comes after this step's backward
+            nf, flip = store.constrained_filter()
+            self._flip = (nf, flip)
+        else:
+            nf = ops.constrained_kernel(store.p[self.name + '/kernel'], self.strength)
+            self._flip = (None, None)
         y, c4 = ops.cconv3(x, nf, pad_mode=1, want_f32=not c4_only, want_c4=c4_only)
         return (c4 if c4_only else y), nf
 
@@ -232,4 +245,4 @@ class ConstrainedConv2D(object):
         if h < 4 or w < 4:
             dpad = ops.conv2d(dy, ops.flip_weights(nf), None, pads=(4, 4), out_hw=(h + 4, w + 4))
             return ops.fold_pad(dpad, 2, 1)
-        return ops.cconv3_dgrad(dy, nf)
+        return ops.cconv3_dgrad(dy, nf, nf_flip=self._flip[1] if nf is self._flip[0] else None)

@@ -56,10 +56,53 @@ class ParamStore(object):
         hi = self.flat_grad.numel() if before is None else self.offsets[before]
         return self.flat_grad[lo:hi]
 
+    # The record that the images are those of the present weights: (flat._version, ops.COMPUTE_EPOCH) at the moment they were
+    # made.  Parameters are handed out as torch views, and every torch write through one of them (mul_, copy_, load_state_dict)
+    # bumps the version counter they share with `flat`; the library's own launches do not, and of those only Adam writes weights.
+    _images_made = None
+
+    def images_current(self):
+        return self._images_made is not None and ops.COMPUTE == 'bf16' and \
+            self._images_made == (self.flat._version, ops.COMPUTE_EPOCH)
+
+    def invalidate_images(self):
+        self._images_made = self._cc_made = None
+
+    # A ConstrainedConv2D kernel of the model (models/layers.py registers it): its normalised filter and the flipped form that the
+    # input gradient reads live in two buffers of the store, under the same rule as the images - made by the Adam launch that
+    # updates the kernel, or here when a weight was written since.
+    constrained = None
+    _cc_made = None
+
+    def register_constrained(self, name, strength):
+        k = self.p[name]
+        if k.is_cuda and k.dim() == 4 and k.shape[0] == k.shape[1] and k.shape[2] == k.shape[3]:
+            self.constrained = {'kernel': k, 'strength': float(strength), 'nf': torch.empty_like(k), 'nft': torch.empty_like(k)}
+
+    def constrained_current(self):
+        return self._cc_made is not None and ops.COMPUTE == 'bf16' and self._cc_made == (self.flat._version, ops.COMPUTE_EPOCH)
+
+    def constrained_filter(self):
+        """-> (normalised filter, its flipped form) of the registered kernel, current."""
+        cc = self.constrained
+        if not self.constrained_current():
+            ops.constrained_kernel(cc['kernel'], cc['strength'], out=cc['nf'])
+            ops.flip_weights(cc['nf'], out=cc['nft'])
+            made = ops.COMPUTE == 'bf16' and not torch.cuda.is_current_stream_capturing()
+            self._cc_made = (self.flat._version, ops.COMPUTE_EPOCH) if made else None
+        return cc['nf'], cc['nft']
+
     def refresh_images(self):
-        """Call at the top of a forward pass: the kernels of this step read the images built here."""
-        if self.images is not None:
-            self.images.refresh()
+        """Call at the top of a forward pass: the kernels of this step read the images built here - or the ones the last Adam
+        launch left behind (ops.adam_step_images), if no weight was written since."""
+        if self.images is None:
+            return
+        if ops.ADAM_IMAGES and self.images_current():
+            return
+        self.images.refresh()
+        # (a launch that was only recorded into a graph has made nothing yet)
+        made = ops.ADAM_IMAGES and ops.COMPUTE == 'bf16' and not torch.cuda.is_current_stream_capturing()
+        self._images_made = (self.flat._version, ops.COMPUTE_EPOCH) if made else None
 
     def ensure_adam(self):
         if self.m is None:
@@ -77,8 +120,21 @@ class ParamStore(object):
         if step is None:
             self.step += 1
             step = self.step
+        rate = lr_t_dev if lr_t_dev is not None else self.lr_t_dev
+        if ops.ADAM_IMAGES and ops.COMPUTE == 'bf16' and self.images is not None and len(self.images.entries):
+            # throughput mode: the same launch leaves both bf16 images of every convolution kernel current.  With a skip flag
+            # the launch may write nothing, and then the images are current only if they were before
+            were, cc_were = self.images_current(), self.constrained_current()
+            cc = self.constrained if ops.ADAM_CCONV else None
+            ops.adam_step_images(self.flat, self.flat_grad, self.m, self.v, self.images, lr, step, grad_scale=grad_scale,
+                                 skip_flag=skip_flag, lr_t_dev=rate, constrained=cc)
+            now = (self.flat._version, ops.COMPUTE_EPOCH)
+            self._images_made = now if (were or skip_flag is None) else None
+            self._cc_made = now if cc is not None and (cc_were or skip_flag is None) else None
+            return
+        self._images_made = self._cc_made = None
         ops.adam_step(self.flat, self.flat_grad, self.m, self.v, lr, step, grad_scale=grad_scale, skip_flag=skip_flag,
-                      lr_t_dev=lr_t_dev if lr_t_dev is not None else self.lr_t_dev)
+                      lr_t_dev=rate)
 
 
 def glorot_uniform_(t, fan_in, fan_out, gen):
@@ -150,6 +206,8 @@ class TFModel(object):
             if tuple(a.shape) != tuple(v.shape):
                 raise ValueError('shape mismatch for {}: {} vs {}'.format(k, a.shape, tuple(v.shape)))
             v.copy_(torch.from_numpy(a))
+        if isinstance(self._model, ParamStore):
+            self._model.invalidate_images()      # (the copies bumped the version counter as well)
 
     # -- checkpoints (tfmodel.py:150-182) ------------------------------------------------------------------------
     _h5_skip = ()            # parameter names that are constants (not Keras variables) in the reference: never stored

@@ -25,10 +25,16 @@ COMPUTE = 'f32'
 STORE_BF16 = True
 
 
+COMPUTE_EPOCH = 0          # counts the changes of COMPUTE: what was derived from the weights under one mode (the record that a
+                           # model's bf16 weight images are current, models/tfmodel.ParamStore) does not outlive it
+
+
 def set_compute(mode):
-    global COMPUTE
+    global COMPUTE, COMPUTE_EPOCH
     if mode not in ('f32', 'bf16'):
         raise ValueError('compute mode must be f32 or bf16')
+    if mode != COMPUTE:
+        COMPUTE_EPOCH += 1
     COMPUTE = mode
 
 
@@ -74,6 +80,21 @@ class WeightImages(object):
     def refresh(self):
         if COMPUTE == 'bf16' and len(self.entries):
             _lib.call('nimg_conv_weights_bf16_batch', _p(self.table), len(self.entries), _stream())
+
+    def within(self, params):
+        """Do the registered weights lie inside the flat buffer `params`, in ascending order and apart, as (mode 0, mode 1)
+        pairs?  What adam_step_images asks of the table (the kernel cannot check it: the table is device memory)."""
+        key = (params.data_ptr(), params.numel())
+        if getattr(self, '_within', (None, False))[0] != key:        # the entries never change: one walk per buffer
+            lo, ok = params.data_ptr(), len(self.entries) % 2 == 0
+            for j in range(0, len(self.entries) if ok else 0, 2):
+                (w, m0), (w1, m1) = self.entries[j], self.entries[j + 1]
+                if w1 is not w or (m0, m1) != (0, 1) or w.dtype != torch.float32 or not w.is_contiguous() or w.data_ptr() < lo:
+                    ok = False
+                    break
+                lo = w.data_ptr() + 4 * w.numel()
+            self._within = (key, ok and lo <= params.data_ptr() + 4 * params.numel())
+        return self._within[1]
 
 
 def weights_bf16(w, mode):
@@ -1546,6 +1567,38 @@ def adam_step(params, grads, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, g
               float(beta2), float(eps), int(step), float(grad_scale), _p(skip_flag), _stream())
 
 
+# The Adam launch also writes the bf16 weight images from the updated values, so that the forward passes need not rebuild them
+# (NIMG_NO_ADAM_IMAGES=1: plain Adam, one image launch at the head of every forward; the same bits, A/B runs)
+ADAM_IMAGES = _os.environ.get('NIMG_NO_ADAM_IMAGES') is None
+# ... and the normalised ConstrainedConv2D filter with its flipped form (NIMG_NO_ADAM_CCONV=1: made at the head of every forward
+# pass and input gradient, by launches of their own; the same with NIMG_NO_ADAM_IMAGES=1, whose Adam launch makes neither)
+ADAM_CCONV = _os.environ.get('NIMG_NO_ADAM_CCONV') is None
+
+
+def adam_step_images(params, grads, m, v, images, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, skip_flag=None,
+                     lr_t_dev=None, constrained=None):
+    """adam_step and, in the same launch, both bf16 images of every weight registered in `images` (a WeightImages whose
+    weights are views of `params`) from the updated values: what adam_step followed by images.refresh() leaves behind.
+    constrained: optional {'kernel': a registered (ks,ks,c,c) weight, 'nf', 'nft', 'strength'} - nf = constrained_kernel(updated
+    kernel, strength) and nft = flip_weights(nf) are written too."""
+    join_side_stream()
+    _f32(params, grads, m, v, lr_t_dev)
+    if not images.within(params):
+        raise ValueError('adam_step_images: the registered weights must be views of the parameter buffer, in its order')
+    cc = (None, None, None, 0, 0, 0.0)
+    if constrained is not None:
+        k, nf, nft = constrained['kernel'], constrained['nf'], constrained['nft']
+        _f32(k, nf, nft)
+        kh, kw, ci, co = k.shape
+        if kh != kw or ci != co or nf.numel() != k.numel() or nft.numel() != k.numel() or \
+                not any(w is k for w, _ in images.entries):
+            raise ValueError('adam_step_images: a registered square (ks,ks,c,c) constrained kernel expected')
+        cc = (_p(k), _p(nf), _p(nft), kh, ci, float(constrained['strength']))
+    _lib.call('nimg_adam_step_images', _p(params), _p(grads), _p(m), _p(v), params.numel(), float(lr), _p(lr_t_dev),
+              float(beta1), float(beta2), float(eps), int(step), float(grad_scale), _p(skip_flag), _p(images.table),
+              len(images.entries), *cc, _stream())
+
+
 def int_fill(t, value=0):
     """t[...] = value for an int32 device tensor (the step's flag words) on the library's own kernel."""
     _chk(t)
@@ -1578,9 +1631,11 @@ def nan_flag(g, flag):
 
 # ----------------------------------------------------------------------------------------------------------------
 # constrained conv pieces, manipulations
-def constrained_kernel(kernel, strength=100.0):
-    _f32(kernel)
-    nf = torch.empty_like(kernel)
+def constrained_kernel(kernel, strength=100.0, out=None):
+    _f32(kernel, out)
+    nf = torch.empty_like(kernel) if out is None else out
+    if nf.numel() != kernel.numel():
+        raise ValueError('constrained_kernel: out must have the size of the kernel')
     _lib.call('nimg_constrained_kernel_fwd', _p(kernel), _p(nf), kernel.shape[0], kernel.shape[2], float(strength),
               _stream())
     return nf
@@ -1683,17 +1738,36 @@ def conv1_dgrad_pooled(g, idx, w, out=None):
     return out
 
 
-def cconv3_dgrad(dy, nf):
+def cconv3_dgrad(dy, nf, nf_flip=None):
     """Input gradient of the SYMMETRIC-padded 5x5 3 -> 3 filter nf: zero-padded correlation with the flipped / transposed
-    filter plus the mirror terms of the two outermost rows / columns."""
-    _f32(dy, nf)
+    filter (nf_flip = flip_weights(nf) where the caller holds it already) plus the mirror terms of the two outermost rows /
+    columns."""
+    _f32(dy, nf, nf_flip)
     n, h, wd, _ = dy.shape
+    if nf_flip is None:
+        nf_flip = flip_weights(nf)
     if COMPUTE == 'bf16' and wd % 64 == 0 and CCONV_DGRAD_MFMA:      # throughput mode: the main term on the matrix core
         dx = torch.empty_like(dy)
-        _lib.call('nimg_conv5c3_bf16', _p(dy), _p(flip_weights(nf)), _p(dx), n, h, wd, _stream())
+        _lib.call('nimg_conv5c3_bf16', _p(dy), _p(nf_flip), _p(dx), n, h, wd, _stream())
     else:
-        dx, _ = cconv3(dy, flip_weights(nf), pad_mode=0)
-    _lib.call('nimg_cconv3_dgrad_border', _p(dy), _p(nf), _p(dx), n, h, wd, _stream())
+        dx, _ = cconv3(dy, nf_flip, pad_mode=0)
+    cconv3_dgrad_border(dy, nf, dx)
+    return dx
+
+
+# The mirror terms of the constrained filter's input gradient from LDS-staged strips (NIMG_NO_BORDER_STRIPS=1: one thread per border
+# pixel reading L2 tap by tap; the same bits, A/B runs)
+BORDER_STRIPS = _os.environ.get('NIMG_NO_BORDER_STRIPS') is None
+
+
+def cconv3_dgrad_border(dy, nf, dx, strips=None):
+    """dx += the terms that the SYMMETRIC pad folds back onto the two outermost rows / columns."""
+    _f32(dy, nf, dx)
+    n, h, wd, _ = dy.shape
+    if tuple(dx.shape) != tuple(dy.shape) or dy.shape[3] != 3 or nf.numel() != 225:
+        raise ValueError('cconv3_dgrad_border: (N,H,W,3) gradients and a 5x5x3x3 filter expected')
+    entry = 'nimg_cconv3_dgrad_border_strips' if (BORDER_STRIPS if strips is None else strips) else 'nimg_cconv3_dgrad_border'
+    _lib.call(entry, _p(dy), _p(nf), _p(dx), n, h, wd, _stream())
     return dx
 
 
