@@ -887,6 +887,29 @@ int nimg_jpeg_tables_from_float(const float* t, int n_sets, int n_tabs, uint16_t
  *                           blocks" (32) and "bits beyond the end" (16) per interval.  Workspace:
  *                           nimg_jpeg_decode_restart_workspace_bytes.  restart_interval = 0 is nimg_jpeg_decode, where FF D0 .. D7
  *                           are markers like any other (bit 1). */
+/* Writing progressive files (libjpeg's jpeg_simple_progression, Pillow's progressive=True): the ten scans of
+ * one set of coefficients - DC first (Al 1, interleaved), Y 1-5 (Al 2), Cr 1-63 (Al 1), Cb 1-63 (Al 1), Y 6-63 (Al 2), Y 1-63 refine
+ * (Al 1), DC refine (interleaved), Cr, Cb, Y 1-63 refine (Al 0) - each coded with a table of its own.  The ten tables of an image stand
+ * in the order of the file's DHT segments: DC 00 (Y), DC 01 (Cb and Cr), then the AC tables of the scans 2, 3, 4, 5, 6, 8, 9, 10.
+ * Geometry, coefficients, table layout and restart_interval as above; n <= 16383, and n == 0 does nothing.  A DC coefficient outside
+ * +-2047 and an AC coefficient outside +-1023 are clamped to that before the point transform.  In a single-component scan the restart
+ * interval counts blocks.  Purely added: NIMG_ABI_VERSION stays.
+ *   progressive_histogram   coef -> hist (device) [n][10][257] uint32, zeroed by the call: how often each symbol of each table is
+ *                           emitted, the EOBn symbols of the end-of-band runs included.  Entry 256 is 0.  nimg_jpeg_optimal_tables on
+ *                           the 10 n histograms gives the tables libjpeg writes.
+ *   encode_progressive      out: the ten entropy-coded segments of every image back to back - stuffed, padded, the restart markers
+ *                           inside; headers, DHT, SOS and EOI are the caller's - none at or beyond out_capacity; lengths (device)
+ *                           [n][10]: the bytes of each segment, capacity or not.  status (device) [n] as nimg_jpeg_encode_tables':
+ *                           bits 1 = one of the ten tables is no prefix code (the image's segments are empty, or its markers alone) |
+ *                           2 = a symbol that occurs has no code (it and its value bits are left out).  A block never exceeds 27
+ *                           bits in a DC scan and 1580 in an AC scan; every store stays inside the workspace whatever the tables say. */
+size_t nimg_jpeg_progressive_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval);
+int nimg_jpeg_progressive_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint32_t* hist,
+                                    void* stream);
+int nimg_jpeg_encode_progressive(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, const uint8_t* tables,
+                                 uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 size_t nimg_jpeg_encode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval);
 int nimg_jpeg_encode_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint8_t* out,
                              size_t out_capacity, uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream);

@@ -22,6 +22,9 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
   encode_batch, compress_batch), allow_restart=         allow_restart - read back with every interval as an entry point of the parallel
   (parse_header, decode_batch, decode_coefficients,     decoder
   transcode_batch)
+  progressive= (jpeg_header, device_codec,              new: progressive files (SOF2), the ten scans of libjpeg's simple progression
+  encode_batch, compress_batch, transcode_batch),       byte for byte, every scan with a Huffman table of its own (DESIGN.md section 4l);
+  jpeg_progressive_pieces                               written only - parse_header refuses them as before
   JPEGMarkerStats (:133-250)                            host parsing of a file's segments
 
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
@@ -144,13 +147,62 @@ def _header_bytes(tables, restart_interval=0):
     return JPEG_HEADER_BYTES + extra + (_DRI_BYTES if restart_interval else 0), _DHT_OFFSET + extra
 
 
-def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None, *, restart_interval=0):
+def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None, *, restart_interval=0, progressive=False):
     """The bytes from SOI to the end of SOS as libjpeg writes them: 623 with default settings.  huffman: one image's four tables in
     DHT-id order 00 10 01 11 as (4, 272) bytes (16 counts, then the symbols in code order) - what libjpeg writes with optimize_coding:
     four DHT segments of 21 bytes + the table's symbols each.  The first DHT segment stays at offset 177.  qtables (with quality None,
     see check_qtables): these tables instead of a quality's, as libjpeg writes a caller's - zig-zag, one DQT segment each; a third
     table goes to Cr (selector 2 in SOF0) and moves everything behind it by 69 bytes: 692 in all, the first DHT at 246.
-    restart_interval (MCUs, 0..65535): above 0 the DRI segment FFDD 0004 RRRR between the last DHT segment and SOS, 6 bytes more."""
+    restart_interval (MCUs, 0..65535): above 0 the DRI segment FFDD 0004 RRRR between the last DHT segment and SOS, 6 bytes more.
+    progressive: the bytes in front of the FIRST scan of a progressive file - SOF2 in place of SOF0, the two DC tables of huffman
+    (10, 272) (which is needed: a progressive file has no default tables), the DRI segment, the first SOS; jpeg_progressive_pieces
+    gives what stands in front of every scan."""
+    if progressive:
+        return jpeg_progressive_pieces(h, w, quality, subsampling, huffman, qtables=qtables, restart_interval=restart_interval)[0]
+    return _jpeg_header(h, w, quality, subsampling, huffman, qtables, restart_interval)
+
+
+# libjpeg's jpeg_simple_progression for three components: (component 0 Y, 1 Cb, 2 Cr or None = all interleaved, Ss, Se, Ah, Al, which of
+# the image's ten tables is written in front of the scan).  Cr comes before Cb.
+_PROGRESSIVE_SCANS = ((None, 0, 0, 0, 1, None), (0, 1, 5, 0, 2, 2), (2, 1, 63, 0, 1, 3), (1, 1, 63, 0, 1, 4), (0, 6, 63, 0, 2, 5),
+                      (0, 1, 63, 2, 1, 6), (None, 0, 0, 1, 0, None), (2, 1, 63, 1, 0, 7), (1, 1, 63, 1, 0, 8), (0, 1, 63, 1, 0, 9))
+
+
+def _dht_segment(ident, table):
+    body = bytes([ident]) + table[:16 + int(table[:16].sum(dtype=np.int64))].tobytes()
+    return b'\xff\xc4' + struct.pack('>H', len(body) + 2) + body
+
+
+def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None, *, restart_interval=0):
+    """What stands in front of each of the ten entropy-coded segments of a progressive file, a list of ten bytes objects: [0] SOI,
+    APP0, the DQT segments, SOF2, the DC tables 00 and 01, the DRI segment, the first SOS; [k] the DHT segment of scan k's AC table
+    (none in front of the DC refine scan) and its SOS.  huffman: the image's ten tables (10, 272) in the order of these DHT segments.
+    file = pieces[0] + segment 0 + ... + pieces[9] + segment 9 + FFD9."""
+    huffman = None if huffman is None else np.asarray(huffman)
+    if huffman is None or huffman.dtype != np.uint8 or huffman.shape != (ops.JPEG_PROGRESSIVE_SCANS, 272):
+        raise ValueError('huffman: the (10, 272) uint8 tables of a progressive file are needed, got {}'.format(
+            None if huffman is None else (huffman.dtype, huffman.shape)))
+    ri = ops.jpeg_restart_interval(restart_interval)
+    base = _jpeg_header(h, w, quality, subsampling, None, qtables, 0)
+    dht = _header_bytes(None if qtables is None else check_qtables(qtables))[1]
+    sof = dht - 19
+    assert base[sof:sof + 2] == b'\xff\xc0'
+    first = base[:sof] + b'\xff\xc2' + base[sof + 2:dht] + _dht_segment(0x00, huffman[0]) + _dht_segment(0x01, huffman[1])
+    if ri:
+        first += b'\xff\xdd\x00\x04' + struct.pack('>H', ri)
+    pieces = []
+    for comp, ss, se, ah, al, table in _PROGRESSIVE_SCANS:
+        if comp is None:
+            dc = 0x10 if ah == 0 else 0x00
+            piece = bytes([0xff, 0xda, 0, 12, 3, 1, 0, 2, dc, 3, dc])
+        else:
+            piece = _dht_segment(0x10 | (comp != 0), huffman[table]) + bytes([0xff, 0xda, 0, 8, 1, comp + 1, int(comp != 0)])
+        pieces.append(piece + bytes([ss, se, (ah << 4) | al]))
+    pieces[0] = first + pieces[0]
+    return pieces
+
+
+def _jpeg_header(h, w, quality, subsampling, huffman, qtables, restart_interval):
     hs, vs = ops.jpeg_subsampling(subsampling)
     ri = ops.jpeg_restart_interval(restart_interval)
     quality, qtables = _quality_or_tables(quality, qtables, clamp=True)
@@ -222,6 +274,36 @@ def _device_codec_optimised(coef, n, h, w, hs, vs, restart_interval=0):
     return [blob[ends[i]:ends[i + 1]] for i in range(n)], tables
 
 
+def _progressive(coef, h, w, hs, vs, capacity, restart_interval=0):
+    """progressive histogram -> optimal tables -> encode_progressive on the device: (segments, lengths (n, 10) int32, tables
+    (n, 10, 272) uint8, status (n,) int32: the bits of JPEG_OPT_STATUS_BITS).  Nothing is read back."""
+    tables, tstatus = ops.jpeg_optimal_tables(ops.jpeg_progressive_histogram(coef, h, w, hs, vs, restart_interval=restart_interval))
+    data, lengths, status = ops.jpeg_encode_progressive(coef, tables, h, w, hs, vs, capacity=capacity, restart_interval=restart_interval)
+    return data, lengths, tables, status | (tstatus.max(dim=1).values << 2)
+
+
+def _device_codec_progressive(coef, n, h, w, hs, vs, restart_interval=0):
+    """([the ten segments of each image as a list of bytes], tables (n, 10, 272) uint8 numpy) - lengths, status and tables in one
+    download, then the segments."""
+    scans = ops.JPEG_PROGRESSIVE_SCANS
+    capacity = n * min(ops.jpeg_progressive_ecd_bound(h, w, hs, vs, restart_interval), 192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024)
+    data, lengths, tables, status = _progressive(coef, h, w, hs, vs, capacity, restart_interval)
+    flat = torch.cat([lengths.reshape(-1).view(torch.uint8), status.view(torch.uint8), tables.reshape(-1)]).cpu().numpy()
+    lengths, status = flat[:4 * scans * n].view(np.int32).astype(np.int64), flat[4 * scans * n:4 * (scans + 1) * n].view(np.int32)
+    _raise_on_opt_status(status)
+    if int(lengths.sum()) > capacity:
+        data = ops.jpeg_encode_progressive(coef, tables, h, w, hs, vs, capacity=int(lengths.sum()), restart_interval=restart_interval)[0]
+    tables = flat[4 * (scans + 1) * n:].reshape(n, scans, 272)
+    blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
+    ends = np.concatenate([[0], np.cumsum(lengths)])
+    return [[blob[ends[scans * i + k]:ends[scans * i + k + 1]] for k in range(scans)] for i in range(n)], tables
+
+
+def _progressive_file(h, w, quality, subsampling, segments, tables, qtables, restart_interval):
+    pieces = jpeg_progressive_pieces(h, w, quality, subsampling, tables, qtables=qtables, restart_interval=restart_interval)
+    return b''.join(p + s for p, s in zip(pieces, segments)) + b'\xff\xd9'
+
+
 def _device_codec_plain(coef, n, h, w, hs, vs, ws=None, restart_interval=0):
     """[segment bytes] with the Annex K tables: one download for the lengths, one for the segments."""
     # room for 3 bytes per sample (random noise at quality 100 needs about 2); the bound is 6.5, and a batch that needs more
@@ -245,14 +327,17 @@ def _device_tables(tables, items, device):
     return torch.from_numpy(np.repeat(t, items, axis=0).view(np.int16)).to(device)
 
 
-def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True, optimize=False, *, qtables=None, restart_interval=0):
+def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=True, optimize=False, *, qtables=None, restart_interval=0,
+                 progressive=False):
     """One batch through the GPU codec: x (n,h,w,3) device tensor, float32 or uint8 -> (decoded (n,h,w,3) float32 device tensor or
     None, list of the entropy-coded segments as bytes or None).  One host synchronisation (for the lengths) when want_bytes.
     With `optimize` the segments are coded with per-image optimal Huffman tables (histogram -> optimal tables -> encode_tables, the
     tables and the lengths coming back together) and a third value is returned: the tables, (n, 4, 272) uint8, or None.
     qtables (with quality None, see check_qtables): the whole batch is quantised with these tables instead of a quality's
     (ops.jpeg_transform_tables, ops.jpeg_reconstruct_tables).  restart_interval (MCUs, 0..65535): the segments carry a restart marker
-    behind every so many MCUs; the image is the same."""
+    behind every so many MCUs; the image is the same.  progressive: the ten scans of a progressive file
+     - `segments` is then a list of ten bytes objects per image and the tables, (n, 10, 272), are always
+    returned as the third value: a progressive file has optimised tables with `optimize` or without."""
     hs, vs = ops.jpeg_subsampling(subsampling)
     quality, qtables = _quality_or_tables(quality, qtables)
     ri = ops.jpeg_restart_interval(restart_interval)
@@ -265,7 +350,9 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
         qt = _device_tables(qtables[None], n, x.device)
         coef = ops.jpeg_transform_tables(x, qt, hs, vs, workspace=ws)[0]          # (check_qtables has seen every entry: no flag to read)
     segments = tables = None
-    if want_bytes and optimize:
+    if want_bytes and progressive:
+        segments, tables = _device_codec_progressive(coef, n, h, w, hs, vs, ri)
+    elif want_bytes and optimize:
         segments, tables = _device_codec_optimised(coef, n, h, w, hs, vs, ri)
     elif want_bytes:
         segments = _device_codec_plain(coef, n, h, w, hs, vs, ws, ri)
@@ -273,21 +360,27 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
     if want_image:
         image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if qtables is None else \
             ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, workspace=ws)
-    return (image, segments, tables) if optimize else (image, segments)
+    return (image, segments, tables) if optimize or progressive else (image, segments)
 
 
-def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0):
+def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0, progressive=False):
     """The JPEG files of a batch (n,h,w,3) or one image (h,w,3), a list of bytes.  uint8 input is coded as it is; float input goes
     through the reference's conversion (x / 255 first if its maximum exceeds 1, then (255 x) truncated).  `optimize`: every file with
     Huffman tables of its own, the files libjpeg writes with optimize_coding (Pillow: optimize=True).  qtables (with quality None, see
     check_qtables): the files libjpeg writes with these quantisation tables (Pillow: qtables=[...]).  restart_interval (MCUs in
     scan order, 0..65535): the files libjpeg writes with that restart interval (Pillow: restart_marker_blocks=) - a DRI segment and a
-    marker FFD0..FFD7 behind every so many MCUs that another follows; a whole number of MCU rows is rows * MCUs per row."""
+    marker FFD0..FFD7 behind every so many MCUs that another follows; a whole number of MCU rows is rows * MCUs per row.
+    progressive: the files libjpeg writes with jpeg_simple_progression (Pillow: progressive=True) - SOF2 and ten scans, each with an
+    optimal table of its own, the same bytes with `optimize` or without; in a single-component scan the restart interval counts
+    blocks."""
     quality, qtables = _quality_or_tables(quality, qtables)
     ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=True)
     if x.dim() == 3:
         x = x[None]
+    if progressive:
+        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, qtables=qtables, restart_interval=ri, progressive=True)
+        return [_progressive_file(x.shape[1], x.shape[2], quality, subsampling, s, t, qtables, ri) for s, t in zip(segments, tables)]
     if optimize:
         _, segments, tables = device_codec(x, quality, subsampling, want_image=False, optimize=True, qtables=qtables, restart_interval=ri)
         return [jpeg_header(x.shape[1], x.shape[2], quality, subsampling, huffman=t, qtables=qtables, restart_interval=ri) + s + b'\xff\xd9'
@@ -303,7 +396,8 @@ def _optimised_header_bytes(tables, base=JPEG_HEADER_BYTES):
     return base - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)
 
 
-def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0):
+def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0,
+                   progressive=False):
     """Compress an image or a batch with the standard JPEG codec (jpeg_helpers.py:82-114).  (h,w,3) -> (float64 image, bytes);
     (n,h,w,3) -> (float32 batch, list of bytes).  `effective` counts from the first Huffman table on instead of the whole file.
     Every input, uint8 included, goes through the reference's conversion: x / 255 in float32 if the maximum exceeds 1, then
@@ -312,7 +406,9 @@ def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', 
     qtables (with jpeg_quality None, see check_qtables): the codec with these quantisation tables instead of a quality's; the sizes
     are those of encode_batch(qtables=) - a third table costs 69 bytes of header, none of the effective size.
     restart_interval: the sizes are those of encode_batch(restart_interval=), the DRI segment and the markers counted (both lie
-    behind the first Huffman table, so `effective` counts them too); the image is the same."""
+    behind the first Huffman table, so `effective` counts them too); the image is the same.
+    progressive: the sizes are those of encode_batch(progressive=True), `effective` again from the first Huffman table on (offset 177
+    with two quantisation tables); the image is the same."""
     jpeg_quality, qtables = _quality_or_tables(jpeg_quality, qtables)
     ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=False)
@@ -320,7 +416,14 @@ def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', 
         raise ValueError('compress_batch needs an (h,w,3) image or an (n,h,w,3) batch')
     single = x.dim() == 3
     head, dht = _header_bytes(qtables, ri)
-    if optimize:
+    if progressive:
+        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, qtables=qtables, restart_interval=ri,
+                                               progressive=True)
+        h, w = x.shape[-3], x.shape[-2]
+        heads = [sum(len(p) for p in jpeg_progressive_pieces(h, w, jpeg_quality, subsampling, t, qtables=qtables, restart_interval=ri))
+                 for t in tables]
+        segments = [b''.join(s) for s in segments]
+    elif optimize:
         image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=True, qtables=qtables,
                                                restart_interval=ri)
         heads = _optimised_header_bytes(tables, head).tolist()
@@ -788,14 +891,15 @@ def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, 
     return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
 
 
-def transcode_batch(files, optimize=True, *, allow_restart=False):
+def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False):
     """Baseline files written again with their coefficients and their quantisation tables untouched - a list of bytes in input order.
     The Huffman tables are the optimal ones of each image (what jpegtran -optimize does) or, with optimize=False, Annex K's.  Every
     file parse_header accepts is read; the header written is the one of encode_batch - JFIF APP0, two DQT segments where the file's Cb
     and Cr tables are equal, else three; APPn and COM segments are dropped.  Files go up in one copy, every group of equal (h, w,
     sampling) is decoded (nimg_jpeg_decode) and coded again on the device without a pixel being computed.  Damaged data raises as in
     decode_batch.  allow_restart: files with a restart interval are read too, and every file keeps its interval - DRI segment and
-    markers are written again."""
+    markers are written again.  progressive: baseline files in, progressive files out (the lossless jpegtran -progressive); their
+    tables are optimal whatever `optimize` says."""
     single = isinstance(files, (bytes, bytearray, memoryview))
     files = [bytes(files)] if single else [bytes(f) for f in files]
     headers, groups = _decode_groups(files, 0, None, allow_restart)
@@ -804,14 +908,17 @@ def transcode_batch(files, optimize=True, *, allow_restart=False):
     result = [None] * len(files)
     for idx, (h, w, hs, vs), coef, _, _, _ in groups:
         ri = headers[idx[0]].restart_interval                               # the group's: files are grouped by it
-        if optimize:
+        if progressive:
+            segments, tables = _device_codec_progressive(coef, len(idx), h, w, hs, vs, ri)
+        elif optimize:
             segments, tables = _device_codec_optimised(coef, len(idx), h, w, hs, vs, ri)
         else:
             segments, tables = _device_codec_plain(coef, len(idx), h, w, hs, vs, restart_interval=ri), [None] * len(idx)
         for i, s, t in zip(idx, segments, tables):
             qt = headers[i].qtables
             qt = qt[:2] if np.array_equal(qt[1], qt[2]) else qt
-            result[i] = jpeg_header(h, w, None, names[(hs, vs)], huffman=t, qtables=qt, restart_interval=ri) + s + b'\xff\xd9'
+            result[i] = _progressive_file(h, w, None, names[(hs, vs)], s, t, qt, ri) if progressive else \
+                jpeg_header(h, w, None, names[(hs, vs)], huffman=t, qtables=qt, restart_interval=ri) + s + b'\xff\xd9'
     return result
 
 

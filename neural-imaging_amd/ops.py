@@ -2754,6 +2754,72 @@ def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None,
     return out, lengths, status
 
 
+# progressive files: ten scans, ten tables per image in the order of the file's DHT segments
+JPEG_PROGRESSIVE_SCANS = 10
+JPEG_PROGRESSIVE_DC_BITS_MAX, JPEG_PROGRESSIVE_AC_BITS_MAX = 27, 1580          # csrc/jpegprog.h: the longest block of a DC / an AC scan
+
+
+def _jpeg_progressive_args(name, coef, h, w, hs, vs, restart_interval):
+    _chk(coef)
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('{}: coefficients {} {} do not match the geometry'.format(name, coef.dtype, tuple(coef.shape)))
+    return n, jpeg_restart_interval(restart_interval)
+
+
+def jpeg_progressive_ecd_bound(h, w, hs, vs, restart_interval=0):
+    """Upper bound of the ten entropy-coded segments of one image in bytes: every block of every scan at its longest, every byte
+    stuffed; a restart marker adds at most 4."""
+    blocks, scan, comps = jpeg_geometry(h, w, hs, vs)
+    ny, nc = comps[0][0] * comps[0][1], comps[1][0] * comps[1][1]
+    ri = jpeg_restart_interval(restart_interval)
+    markers = 0 if not ri else 2 * (-(-(scan // (hs * vs + 2)) // ri) - 1) + 4 * (-(-ny // ri) - 1) + 4 * (-(-nc // ri) - 1)
+    return 2 * (2 * -(-scan * JPEG_PROGRESSIVE_DC_BITS_MAX // 8) + 4 * -(-ny * JPEG_PROGRESSIVE_AC_BITS_MAX // 8) +
+                4 * -(-nc * JPEG_PROGRESSIVE_AC_BITS_MAX // 8)) + 4 * markers
+
+
+def jpeg_progressive_histogram(coef, h, w, hs=1, vs=1, out=None, *, restart_interval=0):
+    """Coefficients of jpeg_transform -> (n, 10, 257) int32: how often the progressive coder (jpeg_encode_progressive) emits each
+    symbol of each of its ten tables - DC 00, DC 01, then the AC tables of the scans 2, 3, 4, 5, 6, 8, 9, 10 -, the EOBn symbols of
+    the end-of-band runs included; entry 256 is 0.  jpeg_optimal_tables on it gives the tables libjpeg writes."""
+    n, ri = _jpeg_progressive_args('jpeg_progressive_histogram', coef, h, w, hs, vs, restart_interval)
+    shape = (n, JPEG_PROGRESSIVE_SCANS, 257)
+    hist = torch.empty(shape, dtype=torch.int32, device=coef.device) if out is None else out
+    _chk(hist)
+    if hist.dtype != torch.int32 or tuple(hist.shape) != shape:
+        raise RuntimeError('jpeg_progressive_histogram: output {} {}, int32 {} needed'.format(hist.dtype, tuple(hist.shape), shape))
+    _lib.call('nimg_jpeg_progressive_histogram', _p(coef), n, h, w, hs, vs, ri, _p(hist), _stream())
+    return hist
+
+
+def jpeg_encode_progressive(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None, *, restart_interval=0):
+    """The ten scans of libjpeg's simple progression with the tables of each image given: tables (n, 10, 272) uint8 -> (the ten
+    entropy-coded segments of every image back to back (uint8), lengths (n, 10) int32, status (n,) int32: bits 1 = tables that are no
+    prefix code, 2 = a symbol of the image has no code).  Headers, DHT and SOS segments and EOI are the caller's."""
+    n, ri = _jpeg_progressive_args('jpeg_encode_progressive', coef, h, w, hs, vs, restart_interval)
+    _chk(tables)
+    if tables.dtype != torch.uint8 or tuple(tables.shape) != (n, JPEG_PROGRESSIVE_SCANS, JPEG_TABLE_BYTES):
+        raise RuntimeError('jpeg_encode_progressive: tables {} {}, ({}, 10, 272) uint8 needed'.format(tables.dtype, tuple(tables.shape), n))
+    need = int(_lib.load().nimg_jpeg_progressive_workspace_bytes(n, h, w, hs, vs, ri))
+    if need == 0 and n:
+        raise RuntimeError('unsupported progressive JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=coef.device)
+    _chk(workspace)
+    if workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError('JPEG workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
+    if out is None:
+        out = torch.empty(max(n * jpeg_progressive_ecd_bound(h, w, hs, vs, ri) if capacity is None else int(capacity), 1), dtype=torch.uint8,
+                          device=coef.device)
+    _chk(out)
+    lengths = torch.empty((n, JPEG_PROGRESSIVE_SCANS), dtype=torch.int32, device=coef.device)
+    status = torch.empty(n, dtype=torch.int32, device=coef.device)
+    capacity = out.numel() if capacity is None else int(capacity)
+    _lib.call('nimg_jpeg_encode_progressive', _p(coef), n, h, w, hs, vs, ri, _p(tables), _p(out), capacity, _p(lengths), _p(status),
+              _p(workspace), need, _stream())
+    return out, lengths, status
+
+
 # any quantisation tables (DESIGN.md section 4h): a table set is (3, 64) uint16 [Y, Cb, Cr] in natural order, one set per item
 def _jpeg_qtabs(qtabs, name):
     _chk(qtabs)

@@ -15,6 +15,10 @@ image - the sequential decode the parallel one is measured against.  One JSON li
 --optimize times writing with optimised Huffman tables: nimg_jpeg_histogram, nimg_jpeg_optimal_tables and
 nimg_jpeg_encode_tables next to nimg_jpeg_encode on the same coefficients, encode_batch with and without optimize from host batch
 to files, and the segment and whole-file bytes either way.  One JSON line per sub-sampling.
+--progressive times writing progressive files: nimg_jpeg_progressive_histogram, nimg_jpeg_optimal_tables on
+the 10 n histograms and nimg_jpeg_encode_progressive next to nimg_jpeg_encode_tables on the same coefficients, encode_batch with
+progressive=True from host batch to files, and the bytes of the baseline, the optimised and the progressive files.  One JSON line
+per sub-sampling.
 --qtables times the table form with libjpeg's tables of --quality, so that its numbers stand next to the
 default mode's: nimg_jpeg_transform_tables (the divisors read from device memory), nimg_jpeg_encode on its coefficients,
 nimg_jpeg_reconstruct_tables and compress_batch(qtables=); the coefficients are checked against the quality form's.  One JSON line
@@ -24,7 +28,7 @@ per sub-sampling.
 sub-sampling: the default mode then times nimg_jpeg_encode_restart and compress_batch(restart_interval=), and --decode times
 nimg_jpeg_decode_restart and decode_batch(allow_restart=True) on those files.  Every line names its interval.
 
-    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode | --optimize | --qtables]
+    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode | --optimize | --progressive | --qtables]
                               [--restart N | --restart-rows R]
 For the split of the calls into their kernels: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_time.py ...
 """
@@ -192,6 +196,36 @@ def measure_optimize(x_host, quality, subsampling, reps, dev):
             'ms': {k: round(v, 4) for k, v in ms.items()}, 'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
 
 
+def measure_progressive(x_host, quality, subsampling, reps, dev):
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    n, h, w, _ = x_host.shape
+    lib = ops._lib.load()
+    coef = ops.jpeg_transform(torch.from_numpy(x_host).to(dev), quality, hs, vs)
+    ws_t = torch.empty(int(lib.nimg_jpeg_encode_tables_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    ws_p = torch.empty(int(lib.nimg_jpeg_progressive_workspace_bytes(n, h, w, hs, vs, 0)), dtype=torch.uint8, device=dev)
+    out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
+    hist = torch.empty((n, 10, 257), dtype=torch.int32, device=dev)
+    tables4 = ops.jpeg_optimal_tables(ops.jpeg_histogram(coef, h, w, hs, vs))[0]
+    ms = {}
+    ms['encode_tables'], _ = timed(lambda: ops.jpeg_encode_tables(coef, tables4, h, w, hs, vs, out=out, workspace=ws_t), reps)
+    ms['progressive_histogram'], _ = timed(lambda: ops.jpeg_progressive_histogram(coef, h, w, hs, vs, out=hist), reps)
+    ms['optimal_tables'], (tables, tstatus) = timed(lambda: ops.jpeg_optimal_tables(hist), reps)
+    ms['encode_progressive'], (_, lengths, status) = timed(
+        lambda: ops.jpeg_encode_progressive(coef, tables, h, w, hs, vs, out=out, workspace=ws_p), reps)
+    assert int(tstatus.abs().sum()) == 0 and int(status.abs().sum()) == 0
+    lengths = lengths.cpu().numpy().astype(np.int64)
+    plain = jpeg_helpers.encode_batch(x_host, quality, subsampling)
+    ms['encode_batch_optimize_total'], optimised = timed(lambda: jpeg_helpers.encode_batch(x_host, quality, subsampling, optimize=True), max(3, reps // 4))
+    ms['encode_batch_progressive_total'], files = timed(lambda: jpeg_helpers.encode_batch(x_host, quality, subsampling, progressive=True), max(3, reps // 4))
+    assert sum(len(f) for f in files) - int(lengths.sum()) == sum(
+        sum(len(p) for p in jpeg_helpers.jpeg_progressive_pieces(h, w, quality, subsampling, t)) + 2 for t in tables.cpu().numpy())
+    return {'mode': 'progressive', 'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality,
+            'segment_bytes_progressive': int(lengths.sum()), 'file_bytes': int(sum(len(f) for f in plain)),
+            'file_bytes_optimize': int(sum(len(f) for f in optimised)), 'file_bytes_progressive': int(sum(len(f) for f in files)),
+            'workspace_bytes_tables': ws_t.numel(), 'workspace_bytes_progressive': ws_p.numel(),
+            'ms': {k: round(v, 4) for k, v in ms.items()}, 'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}}
+
+
 def measure_qtables(x_host, quality, subsampling, reps, dev):
     hs, vs = ops.jpeg_subsampling(subsampling)
     n, h, w, _ = x_host.shape
@@ -238,6 +272,7 @@ def main():
     ap.add_argument('--pillow', action='store_true', help='time Pillow on the host instead (no GPU needed)')
     ap.add_argument('--decode', action='store_true', help='time the decoder instead, per subseq_bits setting')
     ap.add_argument('--optimize', action='store_true', help='time writing with optimised Huffman tables next to nimg_jpeg_encode')
+    ap.add_argument('--progressive', action='store_true', help='time writing progressive files next to nimg_jpeg_encode_tables')
     ap.add_argument('--qtables', action='store_true', help="time the table form with libjpeg's tables of --quality instead")
     ap.add_argument('--restart', type=int, default=0, help='restart interval in MCUs of the files written and read (default mode, --decode)')
     ap.add_argument('--restart-rows', type=int, default=0, help='the same in MCU rows: the interval follows the sub-sampling')
@@ -261,6 +296,11 @@ def main():
         for subsampling in SUBSAMPLINGS:
             measure_optimize(x[:4], args.quality, subsampling, 2, dev)                # warm-up
             print(json.dumps(dict(measure_optimize(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())), flush=True)
+        return
+    if args.progressive:
+        for subsampling in SUBSAMPLINGS:
+            measure_progressive(x[:4], args.quality, subsampling, 2, dev)             # warm-up
+            print(json.dumps(dict(measure_progressive(x, args.quality, subsampling, args.reps, dev), csrc_sha16=csrc_sha16())), flush=True)
         return
     if args.qtables:
         for subsampling in SUBSAMPLINGS:
