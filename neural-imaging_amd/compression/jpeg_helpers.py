@@ -29,6 +29,7 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
 
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
 """
+import functools
 import struct
 from collections import OrderedDict, namedtuple
 
@@ -173,6 +174,14 @@ def _dht_segment(ident, table):
     return b'\xff\xc4' + struct.pack('>H', len(body) + 2) + body
 
 
+_ANNEX_K_DHT = b''.join(_dht_segment(t[0], np.frombuffer(t, np.uint8, offset=1)) for t in _DHT)
+
+
+def _dri_segment(ri):
+    """FFDD 0004 RRRR; nothing for interval 0."""
+    return b'\xff\xdd\x00\x04' + struct.pack('>H', ri) if ri else b''
+
+
 def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None, *, restart_interval=0):
     """What stands in front of each of the ten entropy-coded segments of a progressive file, a list of ten bytes objects: [0] SOI,
     APP0, the DQT segments, SOF2, the DC tables 00 and 01, the DRI segment, the first SOS; [k] the DHT segment of scan k's AC table
@@ -187,9 +196,7 @@ def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qt
     dht = _header_bytes(None if qtables is None else check_qtables(qtables))[1]
     sof = dht - 19
     assert base[sof:sof + 2] == b'\xff\xc0'
-    first = base[:sof] + b'\xff\xc2' + base[sof + 2:dht] + _dht_segment(0x00, huffman[0]) + _dht_segment(0x01, huffman[1])
-    if ri:
-        first += b'\xff\xdd\x00\x04' + struct.pack('>H', ri)
+    first = base[:sof] + b'\xff\xc2' + base[sof + 2:dht] + _dht_segment(0x00, huffman[0]) + _dht_segment(0x01, huffman[1]) + _dri_segment(ri)
     pieces = []
     for comp, ss, se, ah, al, table in _PROGRESSIVE_SCANS:
         if comp is None:
@@ -213,17 +220,13 @@ def _jpeg_header(h, w, quality, subsampling, huffman, qtables, restart_interval)
     for t, table in enumerate(qtables):
         out += bytes.fromhex('ffdb0043') + bytes([t]) + table[order].astype(np.uint8).tobytes()
     out += bytes.fromhex('ffc00011' '08') + struct.pack('>HH', h, w) + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, len(qtables) - 1])
-    tables = _DHT
+    dht = _ANNEX_K_DHT
     if huffman is not None:
         huffman = np.asarray(huffman)
         if huffman.dtype != np.uint8 or huffman.shape != (4, 272):
             raise ValueError('huffman: (4, 272) uint8 needed, got {} {}'.format(huffman.dtype, huffman.shape))
-        tables = [bytes([ident]) + t[:16 + int(t[:16].sum(dtype=np.int64))].tobytes() for ident, t in zip((0x00, 0x10, 0x01, 0x11), huffman)]
-    for t in tables:
-        out += b'\xff\xc4' + struct.pack('>H', len(t) + 2) + t
-    if ri:
-        out += b'\xff\xdd\x00\x04' + struct.pack('>H', ri)
-    return out + bytes.fromhex('ffda000c' '03' '0100' '0211' '0311' '00' '3f' '00')
+        dht = b''.join(_dht_segment(ident, t) for ident, t in zip((0x00, 0x10, 0x01, 0x11), huffman))
+    return out + dht + _dri_segment(ri) + bytes.fromhex('ffda000c' '03' '0100' '0211' '0311' '00' '3f' '00')
 
 
 def _device_batch(batch_x, keep_bytes, device=None):
@@ -242,13 +245,24 @@ JPEG_OPT_STATUS_BITS = OrderedDict([(1, 'Huffman table that is no prefix code'),
                                     (4, 'Huffman code size above 32'), (8, 'symbol histogram total of 2^32 or more')])
 
 
-def _optimised(coef, h, w, hs, vs, capacity, restart_interval=0):
-    """histogram -> optimal tables -> encode_tables on the device: (segments, lengths (n,) int32, tables (n,4,272) uint8, status (n,)
-    int32: the bits of JPEG_OPT_STATUS_BITS).  Nothing is read back."""
-    tables, tstatus = ops.jpeg_optimal_tables(ops.jpeg_histogram(coef, h, w, hs, vs, restart_interval=restart_interval))
-    data, lengths, status = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=capacity, restart_interval=restart_interval)
-    tstatus = tstatus[:, 0] | tstatus[:, 1] | tstatus[:, 2] | tstatus[:, 3]
-    return data, lengths, tables, status | (tstatus << 2)
+def _coding(optimize=False, progressive=False):
+    """What codes a batch in a mode: (the op that counts the symbols of its tables, None = the Annex K tables; the encode op; the bound
+    of one image's segments).  Looked up in ops when asked, so that what is set there holds."""
+    if progressive:
+        return ops.jpeg_progressive_histogram, ops.jpeg_encode_progressive, ops.jpeg_progressive_ecd_bound
+    if optimize:
+        return ops.jpeg_histogram, ops.jpeg_encode_tables, ops.jpeg_ecd_bound_tables
+    return None, ops.jpeg_encode, ops.jpeg_ecd_bound
+
+
+def _optimised(coding, coef, h, w, hs, vs, capacity, restart_interval=0):
+    """histogram -> optimal tables -> encode on the device with the ops of `coding` (_coding: 4 tables per image, or the 10 of a
+    progressive file): (segments, lengths (n,) or (n, 10) int32, tables (n, T, 272) uint8, status (n,) int32: the bits of
+    JPEG_OPT_STATUS_BITS).  Nothing is read back."""
+    histogram, encode, _ = coding
+    tables, tstatus = ops.jpeg_optimal_tables(histogram(coef, h, w, hs, vs, restart_interval=restart_interval))
+    data, lengths, status = encode(coef, tables, h, w, hs, vs, capacity=capacity, restart_interval=restart_interval)
+    return data, lengths, tables, status | (functools.reduce(torch.bitwise_or, tstatus.unbind(1)) << 2)
 
 
 def _raise_on_opt_status(status):
@@ -259,64 +273,34 @@ def _raise_on_opt_status(status):
                 i, s, ' | '.join(text for bit, text in JPEG_OPT_STATUS_BITS.items() if s & bit)) for i, s in bad)))
 
 
-def _device_codec_optimised(coef, n, h, w, hs, vs, restart_interval=0):
-    """([segment bytes], tables (n,4,272) uint8 numpy) - lengths, status and tables in one download, then the segments."""
-    capacity = n * min(ops.jpeg_ecd_bound_tables(h, w, hs, vs, restart_interval), 192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024)
-    data, lengths, tables, status = _optimised(coef, h, w, hs, vs, capacity, restart_interval)
-    flat = torch.cat([lengths.view(torch.uint8), status.view(torch.uint8), tables.reshape(-1)]).cpu().numpy()
-    lengths, status = flat[:4 * n].view(np.int32).astype(np.int64), flat[4 * n:8 * n].view(np.int32)
-    _raise_on_opt_status(status)
-    if int(lengths.sum()) > capacity:
-        data = ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=int(lengths.sum()), restart_interval=restart_interval)[0]
-    tables = flat[8 * n:].reshape(n, 4, 272)
-    blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
-    ends = np.concatenate([[0], np.cumsum(lengths)])
-    return [blob[ends[i]:ends[i + 1]] for i in range(n)], tables
-
-
-def _progressive(coef, h, w, hs, vs, capacity, restart_interval=0):
-    """progressive histogram -> optimal tables -> encode_progressive on the device: (segments, lengths (n, 10) int32, tables
-    (n, 10, 272) uint8, status (n,) int32: the bits of JPEG_OPT_STATUS_BITS).  Nothing is read back."""
-    tables, tstatus = ops.jpeg_optimal_tables(ops.jpeg_progressive_histogram(coef, h, w, hs, vs, restart_interval=restart_interval))
-    data, lengths, status = ops.jpeg_encode_progressive(coef, tables, h, w, hs, vs, capacity=capacity, restart_interval=restart_interval)
-    return data, lengths, tables, status | (tstatus.max(dim=1).values << 2)
-
-
-def _device_codec_progressive(coef, n, h, w, hs, vs, restart_interval=0):
-    """([the ten segments of each image as a list of bytes], tables (n, 10, 272) uint8 numpy) - lengths, status and tables in one
-    download, then the segments."""
-    scans = ops.JPEG_PROGRESSIVE_SCANS
-    capacity = n * min(ops.jpeg_progressive_ecd_bound(h, w, hs, vs, restart_interval), 192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024)
-    data, lengths, tables, status = _progressive(coef, h, w, hs, vs, capacity, restart_interval)
-    flat = torch.cat([lengths.reshape(-1).view(torch.uint8), status.view(torch.uint8), tables.reshape(-1)]).cpu().numpy()
-    lengths, status = flat[:4 * scans * n].view(np.int32).astype(np.int64), flat[4 * scans * n:4 * (scans + 1) * n].view(np.int32)
-    _raise_on_opt_status(status)
-    if int(lengths.sum()) > capacity:
-        data = ops.jpeg_encode_progressive(coef, tables, h, w, hs, vs, capacity=int(lengths.sum()), restart_interval=restart_interval)[0]
-    tables = flat[4 * (scans + 1) * n:].reshape(n, scans, 272)
-    blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
-    ends = np.concatenate([[0], np.cumsum(lengths)])
-    return [[blob[ends[scans * i + k]:ends[scans * i + k + 1]] for k in range(scans)] for i in range(n)], tables
-
-
-def _progressive_file(h, w, quality, subsampling, segments, tables, qtables, restart_interval):
-    pieces = jpeg_progressive_pieces(h, w, quality, subsampling, tables, qtables=qtables, restart_interval=restart_interval)
-    return b''.join(p + s for p, s in zip(pieces, segments)) + b'\xff\xd9'
-
-
-def _device_codec_plain(coef, n, h, w, hs, vs, ws=None, restart_interval=0):
-    """[segment bytes] with the Annex K tables: one download for the lengths, one for the segments."""
+def _device_segments(coding, coef, n, h, w, hs, vs, ws=None, restart_interval=0):
+    """The entropy-coded segments of a batch in the mode of `coding` (_coding) -> (segments, tables): per image its segment as bytes, or
+    a list of the ten of a progressive file; the tables (n, T, 272) uint8 numpy, None for Annex K's.  One download for the lengths -
+    status and tables, where the mode has them, come in the same copy -, one for the segments.  `ws`: a workspace of
+    ops.jpeg_workspace_bytes the encoder may use (without tables: theirs is another)."""
+    histogram, encode, bound = coding
     # room for 3 bytes per sample (random noise at quality 100 needs about 2); the bound is 6.5, and a batch that needs more
     # than it was given reports so through its lengths and is coded again with exactly what it needs
-    scan = ops.jpeg_geometry(h, w, hs, vs)[1]
-    capacity = n * min(ops.jpeg_ecd_bound(h, w, hs, vs, restart_interval), 192 * scan + 1024)
-    data, lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=capacity, restart_interval=restart_interval)
-    lengths = lengths.cpu().numpy().astype(np.int64)
-    if int(lengths.sum()) > capacity:
-        data, _ = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=int(lengths.sum()), restart_interval=restart_interval)
-    blob = data[:int(lengths.sum())].cpu().numpy().tobytes()
+    capacity = n * min(bound(h, w, hs, vs, restart_interval), 192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024)
+    if histogram is None:
+        tables, again = None, functools.partial(encode, coef, h, w, hs, vs, workspace=ws, restart_interval=restart_interval)
+        data, lengths = again(capacity=capacity)
+        shape, lengths = tuple(lengths.shape), lengths.cpu().numpy().astype(np.int64)
+    else:
+        data, lengths, tables, status = _optimised(coding, coef, h, w, hs, vs, capacity, restart_interval)
+        again = functools.partial(encode, coef, tables, h, w, hs, vs, restart_interval=restart_interval)
+        shape, words = tuple(lengths.shape), lengths.numel()
+        flat = torch.cat([lengths.reshape(-1).view(torch.uint8), status.view(torch.uint8), tables.reshape(-1)]).cpu().numpy()
+        lengths, status = flat[:4 * words].view(np.int32).astype(np.int64), flat[4 * words:4 * (words + n)].view(np.int32)
+        _raise_on_opt_status(status)
+        tables = flat[4 * (words + n):].reshape(tuple(tables.shape))
+    total = int(lengths.sum())
+    if total > capacity:
+        data = again(capacity=total)[0]
+    blob = data[:total].cpu().numpy().tobytes()
     ends = np.concatenate([[0], np.cumsum(lengths)])
-    return [blob[ends[i]:ends[i + 1]] for i in range(n)]
+    pieces = [blob[a:b] for a, b in zip(ends[:-1], ends[1:])]
+    return (pieces if len(shape) == 1 else [pieces[i * shape[1]:(i + 1) * shape[1]] for i in range(n)]), tables
 
 
 def _device_tables(tables, items, device):
@@ -342,20 +326,15 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
     quality, qtables = _quality_or_tables(quality, qtables)
     ri = ops.jpeg_restart_interval(restart_interval)
     n, h, w, _ = x.shape
-    ws = torch.empty(int(ops._lib.load().nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, ri) if ri else
-                         ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
+    ws = torch.empty(ops.jpeg_workspace_bytes(n, h, w, hs, vs, ri) or 1, dtype=torch.uint8, device=x.device)
     if qtables is None:
         coef = ops.jpeg_transform(x, quality, hs, vs, workspace=ws)
     else:
         qt = _device_tables(qtables[None], n, x.device)
         coef = ops.jpeg_transform_tables(x, qt, hs, vs, workspace=ws)[0]          # (check_qtables has seen every entry: no flag to read)
     segments = tables = None
-    if want_bytes and progressive:
-        segments, tables = _device_codec_progressive(coef, n, h, w, hs, vs, ri)
-    elif want_bytes and optimize:
-        segments, tables = _device_codec_optimised(coef, n, h, w, hs, vs, ri)
-    elif want_bytes:
-        segments = _device_codec_plain(coef, n, h, w, hs, vs, ws, ri)
+    if want_bytes:
+        segments, tables = _device_segments(_coding(optimize, progressive), coef, n, h, w, hs, vs, ws, ri)
     image = None
     if want_image:
         image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if qtables is None else \
@@ -378,22 +357,31 @@ def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtabl
     x = _device_batch(batch_x, keep_bytes=True)
     if x.dim() == 3:
         x = x[None]
+    _, segments, tables = (device_codec(x, quality, subsampling, want_image=False, optimize=optimize, qtables=qtables, restart_interval=ri,
+                                        progressive=progressive) + (None,))[:3]                    # (Annex K: no tables come back)
+    return _jpeg_files(x.shape[1], x.shape[2], quality, subsampling, segments, tables, qtables, ri, progressive)
+
+
+def _jpeg_files(h, w, quality, subsampling, segments, tables, qtables, ri, progressive):
+    """The files of images of one geometry and setting, from what _device_segments returns: around each image's segment(s) the
+    header(s) that carry its `tables` - None: one header with the Annex K tables serves them all - and EOI."""
     if progressive:
-        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, qtables=qtables, restart_interval=ri, progressive=True)
-        return [_progressive_file(x.shape[1], x.shape[2], quality, subsampling, s, t, qtables, ri) for s, t in zip(segments, tables)]
-    if optimize:
-        _, segments, tables = device_codec(x, quality, subsampling, want_image=False, optimize=True, qtables=qtables, restart_interval=ri)
-        return [jpeg_header(x.shape[1], x.shape[2], quality, subsampling, huffman=t, qtables=qtables, restart_interval=ri) + s + b'\xff\xd9'
-                for s, t in zip(segments, tables)]
-    _, segments = device_codec(x, quality, subsampling, want_image=False, qtables=qtables, restart_interval=ri)
-    head = jpeg_header(x.shape[1], x.shape[2], quality, subsampling, qtables=qtables, restart_interval=ri)
-    return [head + s + b'\xff\xd9' for s in segments]
+        pieces = (jpeg_progressive_pieces(h, w, quality, subsampling, t, qtables=qtables, restart_interval=ri) for t in tables)
+        return [b''.join(p + s for p, s in zip(front, ten)) + b'\xff\xd9' for front, ten in zip(pieces, segments)]
+    heads = [_jpeg_header(h, w, quality, subsampling, None, qtables, ri)] * len(segments) if tables is None else \
+        [_jpeg_header(h, w, quality, subsampling, t, qtables, ri) for t in tables]
+    return [head + s + b'\xff\xd9' for head, s in zip(heads, segments)]
 
 
-def _optimised_header_bytes(tables, base=JPEG_HEADER_BYTES):
-    """SOI .. SOS with the DHT segments of `tables` (..., 4, 272): `base` (623, or 692 with three quantisation tables) with each
-    table's symbols in place of Annex K's 348."""
-    return base - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)
+def _header_lengths(h, w, quality, subsampling, n, tables, qtables, ri, progressive):
+    """The bytes _jpeg_files writes per image beside its segment(s) and EOI, a list of n: SOI .. SOS - 623, or 692 with three
+    quantisation tables, a DRI segment counted, and with `tables` (n, 4, 272) each table's symbols in place of Annex K's 348 -, or
+    everything in front of the ten scans of a progressive file."""
+    if progressive:
+        pieces = (jpeg_progressive_pieces(h, w, quality, subsampling, t, qtables=qtables, restart_interval=ri) for t in tables)
+        return [sum(len(p) for p in front) for front in pieces]
+    head = _header_bytes(qtables, ri)[0]
+    return [head] * n if tables is None else (head - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)).tolist()
 
 
 def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0,
@@ -415,22 +403,11 @@ def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', 
     if x.dim() not in (3, 4):
         raise ValueError('compress_batch needs an (h,w,3) image or an (n,h,w,3) batch')
     single = x.dim() == 3
-    head, dht = _header_bytes(qtables, ri)
-    if progressive:
-        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, qtables=qtables, restart_interval=ri,
-                                               progressive=True)
-        h, w = x.shape[-3], x.shape[-2]
-        heads = [sum(len(p) for p in jpeg_progressive_pieces(h, w, jpeg_quality, subsampling, t, qtables=qtables, restart_interval=ri))
-                 for t in tables]
-        segments = [b''.join(s) for s in segments]
-    elif optimize:
-        image, segments, tables = device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=True, qtables=qtables,
-                                               restart_interval=ri)
-        heads = _optimised_header_bytes(tables, head).tolist()
-    else:
-        image, segments = device_codec(x[None] if single else x, jpeg_quality, subsampling, qtables=qtables, restart_interval=ri)
-        heads = [head] * len(segments)
-    sizes = [hd + len(s) + 2 - (dht if effective else 0) for hd, s in zip(heads, segments)]
+    image, segments, tables = (device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=optimize, qtables=qtables,
+                                            restart_interval=ri, progressive=progressive) + (None,))[:3]
+    heads = _header_lengths(x.shape[-3], x.shape[-2], jpeg_quality, subsampling, len(segments), tables, qtables, ri, progressive)
+    dht = _header_bytes(qtables, ri)[1] if effective else 0
+    sizes = [head + (sum(len(scan) for scan in s) if progressive else len(s)) + 2 - dht for head, s in zip(heads, segments)]
     image = image.cpu().numpy()
     if single:
         return np.rint(image[0] * np.float32(255)).astype(np.uint8) / 255, sizes[0]
@@ -484,9 +461,8 @@ def _file_bytes(lengths, effective, tables=None):
 
 def _qualities_per_call(n, h, w, hs, vs, total):
     """How many qualities of a sweep over n images fit one item call: the workspace within RD_WORKSPACE_BUDGET (at least one)."""
-    size = ops._lib.load().nimg_jpeg_workspace_bytes
     k = max(1, min(total, 65535 // n))
-    while k > 1 and int(size(k * n, h, w, hs, vs)) > RD_WORKSPACE_BUDGET:
+    while k > 1 and ops.jpeg_workspace_bytes(k * n, h, w, hs, vs) > RD_WORKSPACE_BUDGET:
         k -= 1
     return k
 
@@ -499,7 +475,7 @@ def _item_round(x, item_q, hs, vs, want_lengths, want_images, optimize=False, it
     device in place of the qualities (item_q is None then)."""
     _, h, w, _ = x.shape
     items = len(item_q) if item_tables is None else item_tables.shape[0]
-    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(items, h, w, hs, vs)) or 1, dtype=torch.uint8, device=x.device)
+    ws = torch.empty(ops.jpeg_workspace_bytes(items, h, w, hs, vs) or 1, dtype=torch.uint8, device=x.device)
     if item_tables is None:
         q = ops.jpeg_item_qualities(item_q, items, x.device)
         coef, _ = ops.jpeg_transform_items(x, q, hs, vs, workspace=ws)
@@ -507,7 +483,7 @@ def _item_round(x, item_q, hs, vs, want_lengths, want_images, optimize=False, it
         coef, _ = ops.jpeg_transform_tables(x, item_tables, hs, vs, workspace=ws)
     status = None
     if want_lengths and optimize:
-        _, lengths, tables, status = _optimised(coef, h, w, hs, vs, 1)                                         # byte counts only
+        _, lengths, tables, status = _optimised(_coding(optimize=True), coef, h, w, hs, vs, 1)                # byte counts only
         lengths = lengths + (tables[:, :, :16].sum(dim=(1, 2), dtype=torch.int32) - 348)
     else:
         lengths = ops.jpeg_encode(coef, h, w, hs, vs, workspace=ws, capacity=1)[1] if want_lengths else None      # byte counts only
@@ -840,6 +816,11 @@ def _raise_on_status(groups, status):
             [i for i, _ in bad], '; '.join('{}: status {} ({})'.format(i, s, _status_text(s)) for i, s in bad)))
 
 
+def _as_files(files):
+    """One file or several -> a list of bytes."""
+    return [bytes(files)] if isinstance(files, (bytes, bytearray, memoryview)) else [bytes(f) for f in files]
+
+
 def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False):
     """Decode baseline JPEG files on the GPU: a list of bytes (or one bytes) -> (n,h,w,3) uint8, the array imageio.imread returns for
     each (libjpeg's islow inverse DCT and fancy up-sampling, bit for bit), or float32(byte) / 255 with as_float.  Files of different
@@ -848,8 +829,7 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     one reconstruct call, status and images come down once; device_output keeps the images on the device.  Damaged data raises
     ValueError naming the indices and the status bits (JPEG_STATUS_BITS).  allow_restart: files with a restart interval are read
     too (parse_header); a group is then the files of equal geometry and interval, and every interval is decoded from its own start."""
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    files = [bytes(files)] if single else [bytes(f) for f in files]
+    files = _as_files(files)
     headers, groups = _decode_groups(files, subseq_bits, device, allow_restart)
     images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
               for _, (h, w, hs, vs), coef, _, _, qt in groups]
@@ -880,8 +860,7 @@ def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, 
     of DESIGN.md section 4c - [Y | Cb | Cr][block row][block col][zig-zag] - and the (n, 3, 64) uint16 quantisation tables per
     component in natural order; jpeg_qf_estimation(tables[i, c].reshape(8, 8), c) names the quality they came from).
     allow_restart: as decode_batch's; the files must then share their restart interval too."""
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    files = [bytes(files)] if single else [bytes(f) for f in files]
+    files = _as_files(files)
     headers, groups = _decode_groups(files, subseq_bits, device, allow_restart)
     if len(groups) != 1:
         raise ValueError('decode_coefficients needs files of one geometry{}, got {}'.format(
@@ -900,25 +879,19 @@ def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=Fa
     decode_batch.  allow_restart: files with a restart interval are read too, and every file keeps its interval - DRI segment and
     markers are written again.  progressive: baseline files in, progressive files out (the lossless jpegtran -progressive); their
     tables are optimal whatever `optimize` says."""
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    files = [bytes(files)] if single else [bytes(f) for f in files]
+    files = _as_files(files)
     headers, groups = _decode_groups(files, 0, None, allow_restart)
     _raise_on_status(groups, np.split(torch.cat([g[3] for g in groups]).cpu().numpy(), np.cumsum([len(g[0]) for g in groups])[:-1]))
     names = {v: k for k, v in ops.JPEG_SUBSAMPLING.items()}
     result = [None] * len(files)
     for idx, (h, w, hs, vs), coef, _, _, _ in groups:
         ri = headers[idx[0]].restart_interval                               # the group's: files are grouped by it
-        if progressive:
-            segments, tables = _device_codec_progressive(coef, len(idx), h, w, hs, vs, ri)
-        elif optimize:
-            segments, tables = _device_codec_optimised(coef, len(idx), h, w, hs, vs, ri)
-        else:
-            segments, tables = _device_codec_plain(coef, len(idx), h, w, hs, vs, restart_interval=ri), [None] * len(idx)
-        for i, s, t in zip(idx, segments, tables):
+        segments, tables = _device_segments(_coding(optimize, progressive), coef, len(idx), h, w, hs, vs, restart_interval=ri)
+        for j, i in enumerate(idx):                                         # a file at a time: each keeps its quantisation tables
             qt = headers[i].qtables
             qt = qt[:2] if np.array_equal(qt[1], qt[2]) else qt
-            result[i] = _progressive_file(h, w, None, names[(hs, vs)], s, t, qt, ri) if progressive else \
-                jpeg_header(h, w, None, names[(hs, vs)], huffman=t, qtables=qt, restart_interval=ri) + s + b'\xff\xd9'
+            result[i], = _jpeg_files(h, w, None, names[(hs, vs)], segments[j:j + 1], None if tables is None else tables[j:j + 1], qt, ri,
+                                     progressive)
     return result
 
 

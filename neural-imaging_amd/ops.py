@@ -2494,27 +2494,56 @@ def jpeg_ecd_bound(h, w, hs, vs, restart_interval=0):
     return 2 * -(-jpeg_geometry(h, w, hs, vs)[1] * JPEG_BLOCK_BITS_MAX // 8) + 4 * jpeg_restart_markers(h, w, hs, vs, restart_interval)
 
 
-def _jpeg_workspace(n, h, w, hs, vs, device, workspace, restart_interval=0):
-    need = int(_lib.load().nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, restart_interval) if restart_interval else
-               _lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs))
-    if need == 0:
-        raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
+def jpeg_workspace_bytes(n, h, w, hs, vs, restart_interval=0):
+    """Bytes of workspace the transforms, jpeg_encode and the reconstructions need for n images, 0 = a batch the library does not
+    serve.  A restart interval only adds to it, so one workspace of the interval's size serves all three stages of a batch."""
+    return int(_lib.load().nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, jpeg_restart_interval(restart_interval)))
+
+
+def _jpeg_workspace(need, batch, device, workspace, name='JPEG workspace', empty_ok=False):
+    """The one workspace check: `need` bytes as the library counts them, 0 = it does not serve this batch (`batch` says which; an
+    empty batch passes where `empty_ok`) -> (the caller's workspace, or a new one where it gave none; need)."""
+    need = int(need)
+    if need == 0 and not empty_ok:
+        raise RuntimeError('unsupported {}'.format(batch))
     if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
     _chk(workspace)
     if workspace.numel() * workspace.element_size() < need:
-        raise RuntimeError('JPEG workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
+        raise RuntimeError('{} of {} bytes, {} needed'.format(name, workspace.numel() * workspace.element_size(), need))
     return workspace, need
+
+
+def _jpeg_batch(n, h, w, hs, vs, kind='JPEG'):
+    return '{} batch: n={} h={} w={} sampling {}x{}'.format(kind, n, h, w, hs, vs)
+
+
+def _jpeg_pixel_workspace(n, h, w, hs, vs, device, workspace):
+    """The workspace of a transform or a reconstruction: these know no restart interval."""
+    return _jpeg_workspace(_lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs), _jpeg_batch(n, h, w, hs, vs), device, workspace)
+
+
+def _jpeg_coef(name, coef, h, w, hs, vs):
+    """The one check of coefficients against the geometry: int16 of shape (n, real blocks, 64) -> n."""
+    n = coef.shape[0]
+    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
+        raise RuntimeError('{}: coefficients {} {} do not match the geometry'.format(name, coef.dtype, tuple(coef.shape)))
+    return n
+
+
+def _jpeg_rgb(name, x):
+    """The one input check of the transforms."""
+    _chk(x)
+    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
+        raise RuntimeError('{} needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(name, x.dtype, tuple(x.shape)))
 
 
 def jpeg_transform(x, quality, hs=1, vs=1, workspace=None):
     """(n,h,w,3) float32 or uint8 -> (n, real blocks, 64) int16 quantised coefficients in zig-zag order, the blocks of an image
     ordered [Y | Cb | Cr][block row][block col]."""
-    _chk(x)
-    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
-        raise RuntimeError('jpeg_transform needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(x.dtype, tuple(x.shape)))
+    _jpeg_rgb('jpeg_transform', x)
     n, h, w, _ = x.shape
-    ws, need = _jpeg_workspace(n, h, w, hs, vs, x.device, workspace)
+    ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, x.device, workspace)
     coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
     _lib.call('nimg_jpeg_transform', _p(x), int(x.dtype == torch.uint8), n, h, w, hs, vs, int(quality), _p(coef), _p(ws), need,
               _stream())
@@ -2526,32 +2555,41 @@ def jpeg_encode(coef, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None,
     or beyond `capacity` (default: the whole of `out`; without `out`: the upper bound, so that every segment fits).
     restart_interval: MCUs between two restart markers (nimg_jpeg_encode_restart), 0 = none; the workspace is then
     nimg_jpeg_encode_restart_workspace_bytes."""
+    return _jpeg_encode('jpeg_encode', 'nimg_jpeg_encode_restart', 'nimg_jpeg_encode_restart_workspace_bytes', jpeg_ecd_bound, None, (),
+                        coef, None, h, w, hs, vs, out, workspace, capacity, restart_interval)[:2]
+
+
+def _jpeg_encode(name, entry, size, bound, n_tables, per_image, coef, tables, h, w, hs, vs, out, workspace, capacity, restart_interval,
+                 kind='JPEG', empty_ok=False):
+    """The body of jpeg_encode, jpeg_encode_tables and jpeg_encode_progressive: the library's `entry`, its workspace sized by `size`, on
+    the coefficients and - where the mode has them - the (n, n_tables, 272) Huffman tables of each image -> (segments, lengths
+    (n,) + per_image, status (n,); None without tables).  bound(h, w, hs, vs, ri) is the room of one image where the caller gave
+    neither `out` nor `capacity`; `empty_ok`: the entry point takes a batch of no images, and an output of no bytes."""
     _chk(coef)
-    n = coef.shape[0]
+    _chk(tables)
     ri = jpeg_restart_interval(restart_interval)
-    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
-        raise RuntimeError('jpeg_encode: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
-    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace, ri)
+    n = _jpeg_coef(name, coef, h, w, hs, vs)
+    if n_tables and (tables.dtype != torch.uint8 or tuple(tables.shape) != (n, n_tables, JPEG_TABLE_BYTES)):
+        raise RuntimeError('{}: tables {} {}, ({}, {}, 272) uint8 needed'.format(name, tables.dtype, tuple(tables.shape), n, n_tables))
+    ws, need = _jpeg_workspace(getattr(_lib.load(), size)(n, h, w, hs, vs, ri), _jpeg_batch(n, h, w, hs, vs, kind), coef.device, workspace,
+                               empty_ok=empty_ok and n == 0)
     if out is None:
-        out = torch.empty(n * jpeg_ecd_bound(h, w, hs, vs, ri) if capacity is None else int(capacity), dtype=torch.uint8,
-                          device=coef.device)
+        room = n * bound(h, w, hs, vs, ri) if capacity is None else int(capacity)
+        out = torch.empty(max(room, 1) if empty_ok else room, dtype=torch.uint8, device=coef.device)
     _chk(out)
-    lengths = torch.empty(n, dtype=torch.int32, device=coef.device)
+    lengths = torch.empty((n,) + per_image, dtype=torch.int32, device=coef.device)
+    status = torch.empty(n, dtype=torch.int32, device=coef.device) if n_tables else None
     capacity = out.numel() if capacity is None else int(capacity)
-    if ri:
-        _lib.call('nimg_jpeg_encode_restart', _p(coef), n, h, w, hs, vs, ri, _p(out), capacity, _p(lengths), _p(ws), need, _stream())
-    else:
-        _lib.call('nimg_jpeg_encode', _p(coef), n, h, w, hs, vs, _p(out), capacity, _p(lengths), _p(ws), need, _stream())
-    return out, lengths
+    _lib.call(entry, _p(coef), n, h, w, hs, vs, ri, *((_p(tables),) if n_tables else ()), _p(out), capacity, _p(lengths),
+              *((_p(status),) if n_tables else ()), _p(ws), need, _stream())
+    return out, lengths, status
 
 
 def jpeg_reconstruct(coef, h, w, quality, hs=1, vs=1, workspace=None, out=None):
     """Coefficients of jpeg_transform -> the (n,h,w,3) float32 image libjpeg decodes from them, in [0, 1]."""
     _chk(coef)
-    n = coef.shape[0]
-    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
-        raise RuntimeError('jpeg_reconstruct: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
-    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    n = _jpeg_coef('jpeg_reconstruct', coef, h, w, hs, vs)
+    ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
     y = torch.empty((n, h, w, 3), dtype=torch.float32, device=coef.device) if out is None else out
     _f32(y)
     _lib.call('nimg_jpeg_reconstruct', _p(coef), n, h, w, hs, vs, int(quality), _p(y), _p(ws), need, _stream())
@@ -2579,13 +2617,11 @@ def jpeg_transform_items(x, quality, hs=1, vs=1, workspace=None, err=None):
     """(n_src,h,w,3) float32 or uint8 and one quality per item -> ((n_items, real blocks, 64) int16 coefficients laid out as
     jpeg_transform's, (1,) int32 error flag: non-zero = a quality byte outside 1..100 was clamped).  Item j codes source image
     j % n_src at quality[j]; n_items = len(quality), so a quality-major sweep reads the sources in place."""
-    _chk(x)
-    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
-        raise RuntimeError('jpeg_transform_items needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(x.dtype, tuple(x.shape)))
+    _jpeg_rgb('jpeg_transform_items', x)
     n_src, h, w, _ = x.shape
     n_items = int(quality.numel() if isinstance(quality, torch.Tensor) else np.size(quality))
     q = jpeg_item_qualities(quality, n_items, x.device)
-    ws, need = _jpeg_workspace(n_items, h, w, hs, vs, x.device, workspace)
+    ws, need = _jpeg_pixel_workspace(n_items, h, w, hs, vs, x.device, workspace)
     coef = torch.empty((n_items, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
     err = torch.zeros((1,), dtype=torch.int32, device=x.device) if err is None else err
     _lib.call('nimg_jpeg_transform_items', _p(x), int(x.dtype == torch.uint8), n_src, h, w, hs, vs, _p(q), n_items, _p(coef), _p(err),
@@ -2597,11 +2633,9 @@ def jpeg_reconstruct_items(coef, h, w, quality, hs=1, vs=1, workspace=None, out=
     """Coefficients of n_items images and one quality per item -> ((n_items,h,w,3) float32 decoded images, (1,) int32 error flag as
     jpeg_transform_items')."""
     _chk(coef)
-    n = coef.shape[0]
-    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
-        raise RuntimeError('jpeg_reconstruct_items: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    n = _jpeg_coef('jpeg_reconstruct_items', coef, h, w, hs, vs)
     q = jpeg_item_qualities(quality, n, coef.device)
-    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
     y = torch.empty((n, h, w, 3), dtype=torch.float32, device=coef.device) if out is None else out
     _f32(y)
     err = torch.zeros((1,), dtype=torch.int32, device=coef.device) if err is None else err
@@ -2631,24 +2665,14 @@ def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspac
         raise RuntimeError('jpeg_decode: Huffman tables {} {}, ({}, 6, 272) uint8 needed'.format(huffman.dtype, tuple(huffman.shape), n))
     subseq_bits = int(subseq_bits)
     ri = jpeg_restart_interval(restart_interval)
-    need = int(_lib.load().nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, ri, ecd.numel(), subseq_bits) if ri else
-               _lib.load().nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
-    if need == 0:
-        raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{} subseq_bits={}'.format(n, h, w, hs, vs, subseq_bits))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=ecd.device)
-    _chk(workspace)
-    if workspace.numel() * workspace.element_size() < need:
-        raise RuntimeError('JPEG decode workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
+    workspace, _ = _jpeg_workspace(_lib.load().nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, ri, ecd.numel(), subseq_bits),
+                                   '{} subseq_bits={}'.format(_jpeg_batch(n, h, w, hs, vs), subseq_bits), ecd.device, workspace,
+                                   name='JPEG decode workspace')
     coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
     status = torch.empty(n, dtype=torch.int32, device=ecd.device)
     rounds = torch.empty(n, dtype=torch.int32, device=ecd.device)
-    if ri:
-        _lib.call('nimg_jpeg_decode_restart', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, ri, subseq_bits, _p(coef), _p(status),
-                  _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
-    else:
-        _lib.call('nimg_jpeg_decode', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, subseq_bits, _p(coef), _p(status), _p(rounds),
-                  _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    _lib.call('nimg_jpeg_decode_restart', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, ri, subseq_bits, _p(coef), _p(status),
+              _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
     return coef, status, rounds
 
 
@@ -2657,12 +2681,10 @@ def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspa
     in natural order.  Returns (n,h,w,3) uint8 - the bytes libjpeg decodes - when out_u8, else float32 = byte / 255."""
     _chk(coef)
     _chk(qtabs)
-    n = coef.shape[0]
-    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
-        raise RuntimeError('jpeg_reconstruct_tables: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
+    n = _jpeg_coef('jpeg_reconstruct_tables', coef, h, w, hs, vs)
     if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, 3, 64):
         raise RuntimeError('jpeg_reconstruct_tables: tables {} {}, ({}, 3, 64) 16-bit integers needed'.format(qtabs.dtype, tuple(qtabs.shape), n))
-    ws, need = _jpeg_workspace(n, h, w, hs, vs, coef.device, workspace)
+    ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
     dtype = torch.uint8 if out_u8 else torch.float32
     y = torch.empty((n, h, w, 3), dtype=dtype, device=coef.device) if out is None else out
     _chk(y)
@@ -2687,19 +2709,19 @@ def jpeg_ecd_bound_tables(h, w, hs, vs, restart_interval=0):
 def jpeg_histogram(coef, h, w, hs=1, vs=1, out=None, *, restart_interval=0):
     """Coefficients of jpeg_transform -> (n, 4, 257) int32: how often jpeg_encode emits each symbol of each table; entry 256 is 0.
     restart_interval: as jpeg_encode's - the DC differences at the start of an interval are taken from 0."""
+    return _jpeg_histogram('jpeg_histogram', 'nimg_jpeg_histogram_restart', 4, coef, h, w, hs, vs, out, restart_interval)
+
+
+def _jpeg_histogram(name, entry, n_tables, coef, h, w, hs, vs, out, restart_interval):
+    """The body of jpeg_histogram and jpeg_progressive_histogram: `entry` fills (n, n_tables, 257) int32."""
     _chk(coef)
-    n = coef.shape[0]
     ri = jpeg_restart_interval(restart_interval)
-    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
-        raise RuntimeError('jpeg_histogram: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
-    hist = torch.empty((n, 4, 257), dtype=torch.int32, device=coef.device) if out is None else out
+    shape = (_jpeg_coef(name, coef, h, w, hs, vs), n_tables, 257)
+    hist = torch.empty(shape, dtype=torch.int32, device=coef.device) if out is None else out
     _chk(hist)
-    if hist.dtype != torch.int32 or tuple(hist.shape) != (n, 4, 257):
-        raise RuntimeError('jpeg_histogram: output {} {}, int32 {} needed'.format(hist.dtype, tuple(hist.shape), (n, 4, 257)))
-    if ri:
-        _lib.call('nimg_jpeg_histogram_restart', _p(coef), n, h, w, hs, vs, ri, _p(hist), _stream())
-    else:
-        _lib.call('nimg_jpeg_histogram', _p(coef), n, h, w, hs, vs, _p(hist), _stream())
+    if hist.dtype != torch.int32 or tuple(hist.shape) != shape:
+        raise RuntimeError('{}: output {} {}, int32 {} needed'.format(name, hist.dtype, tuple(hist.shape), shape))
+    _lib.call(entry, _p(coef), shape[0], h, w, hs, vs, ri, _p(hist), _stream())
     return hist
 
 
@@ -2721,50 +2743,13 @@ def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None,
     """jpeg_encode with the Huffman tables of each image given: tables (n, 4, 272) uint8 -> (segments back to back (uint8), lengths
     (n,) int32, status (n,) int32: bits 1 = tables that are no prefix code (length 0, or the restart markers alone), 2 = a symbol of
     the image has no code).  restart_interval: as jpeg_encode's (nimg_jpeg_encode_tables_restart)."""
-    _chk(coef)
-    _chk(tables)
-    n = coef.shape[0]
-    ri = jpeg_restart_interval(restart_interval)
-    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
-        raise RuntimeError('jpeg_encode_tables: coefficients {} {} do not match the geometry'.format(coef.dtype, tuple(coef.shape)))
-    if tables.dtype != torch.uint8 or tuple(tables.shape) != (n, 4, JPEG_TABLE_BYTES):
-        raise RuntimeError('jpeg_encode_tables: tables {} {}, ({}, 4, 272) uint8 needed'.format(tables.dtype, tuple(tables.shape), n))
-    need = int(_lib.load().nimg_jpeg_encode_tables_restart_workspace_bytes(n, h, w, hs, vs, ri) if ri else
-               _lib.load().nimg_jpeg_encode_tables_workspace_bytes(n, h, w, hs, vs))
-    if need == 0:
-        raise RuntimeError('unsupported JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=coef.device)
-    _chk(workspace)
-    if workspace.numel() * workspace.element_size() < need:
-        raise RuntimeError('JPEG workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
-    if out is None:
-        out = torch.empty(n * jpeg_ecd_bound_tables(h, w, hs, vs, ri) if capacity is None else int(capacity), dtype=torch.uint8,
-                          device=coef.device)
-    _chk(out)
-    lengths = torch.empty(n, dtype=torch.int32, device=coef.device)
-    status = torch.empty(n, dtype=torch.int32, device=coef.device)
-    capacity = out.numel() if capacity is None else int(capacity)
-    if ri:
-        _lib.call('nimg_jpeg_encode_tables_restart', _p(coef), n, h, w, hs, vs, ri, _p(tables), _p(out), capacity, _p(lengths),
-                  _p(status), _p(workspace), need, _stream())
-    else:
-        _lib.call('nimg_jpeg_encode_tables', _p(coef), n, h, w, hs, vs, _p(tables), _p(out), capacity, _p(lengths), _p(status),
-                  _p(workspace), need, _stream())
-    return out, lengths, status
+    return _jpeg_encode('jpeg_encode_tables', 'nimg_jpeg_encode_tables_restart', 'nimg_jpeg_encode_tables_restart_workspace_bytes',
+                        jpeg_ecd_bound_tables, 4, (), coef, tables, h, w, hs, vs, out, workspace, capacity, restart_interval)
 
 
 # progressive files (DESIGN.md section 4l): ten scans, ten tables per image in the order of the file's DHT segments
 JPEG_PROGRESSIVE_SCANS = 10
 JPEG_PROGRESSIVE_DC_BITS_MAX, JPEG_PROGRESSIVE_AC_BITS_MAX = 27, 1580          # csrc/jpegprog.h: the longest block of a DC / an AC scan
-
-
-def _jpeg_progressive_args(name, coef, h, w, hs, vs, restart_interval):
-    _chk(coef)
-    n = coef.shape[0]
-    if coef.dtype != torch.int16 or tuple(coef.shape) != (n, jpeg_geometry(h, w, hs, vs)[0], 64):
-        raise RuntimeError('{}: coefficients {} {} do not match the geometry'.format(name, coef.dtype, tuple(coef.shape)))
-    return n, jpeg_restart_interval(restart_interval)
 
 
 def jpeg_progressive_ecd_bound(h, w, hs, vs, restart_interval=0):
@@ -2782,42 +2767,17 @@ def jpeg_progressive_histogram(coef, h, w, hs=1, vs=1, out=None, *, restart_inte
     """Coefficients of jpeg_transform -> (n, 10, 257) int32: how often the progressive coder (jpeg_encode_progressive) emits each
     symbol of each of its ten tables - DC 00, DC 01, then the AC tables of the scans 2, 3, 4, 5, 6, 8, 9, 10 -, the EOBn symbols of
     the end-of-band runs included; entry 256 is 0.  jpeg_optimal_tables on it gives the tables libjpeg writes."""
-    n, ri = _jpeg_progressive_args('jpeg_progressive_histogram', coef, h, w, hs, vs, restart_interval)
-    shape = (n, JPEG_PROGRESSIVE_SCANS, 257)
-    hist = torch.empty(shape, dtype=torch.int32, device=coef.device) if out is None else out
-    _chk(hist)
-    if hist.dtype != torch.int32 or tuple(hist.shape) != shape:
-        raise RuntimeError('jpeg_progressive_histogram: output {} {}, int32 {} needed'.format(hist.dtype, tuple(hist.shape), shape))
-    _lib.call('nimg_jpeg_progressive_histogram', _p(coef), n, h, w, hs, vs, ri, _p(hist), _stream())
-    return hist
+    return _jpeg_histogram('jpeg_progressive_histogram', 'nimg_jpeg_progressive_histogram', JPEG_PROGRESSIVE_SCANS, coef, h, w, hs, vs, out,
+                           restart_interval)
 
 
 def jpeg_encode_progressive(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None, *, restart_interval=0):
     """The ten scans of libjpeg's simple progression with the tables of each image given: tables (n, 10, 272) uint8 -> (the ten
     entropy-coded segments of every image back to back (uint8), lengths (n, 10) int32, status (n,) int32: bits 1 = tables that are no
     prefix code, 2 = a symbol of the image has no code).  Headers, DHT and SOS segments and EOI are the caller's."""
-    n, ri = _jpeg_progressive_args('jpeg_encode_progressive', coef, h, w, hs, vs, restart_interval)
-    _chk(tables)
-    if tables.dtype != torch.uint8 or tuple(tables.shape) != (n, JPEG_PROGRESSIVE_SCANS, JPEG_TABLE_BYTES):
-        raise RuntimeError('jpeg_encode_progressive: tables {} {}, ({}, 10, 272) uint8 needed'.format(tables.dtype, tuple(tables.shape), n))
-    need = int(_lib.load().nimg_jpeg_progressive_workspace_bytes(n, h, w, hs, vs, ri))
-    if need == 0 and n:
-        raise RuntimeError('unsupported progressive JPEG batch: n={} h={} w={} sampling {}x{}'.format(n, h, w, hs, vs))
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=coef.device)
-    _chk(workspace)
-    if workspace.numel() * workspace.element_size() < need:
-        raise RuntimeError('JPEG workspace of {} bytes, {} needed'.format(workspace.numel() * workspace.element_size(), need))
-    if out is None:
-        out = torch.empty(max(n * jpeg_progressive_ecd_bound(h, w, hs, vs, ri) if capacity is None else int(capacity), 1), dtype=torch.uint8,
-                          device=coef.device)
-    _chk(out)
-    lengths = torch.empty((n, JPEG_PROGRESSIVE_SCANS), dtype=torch.int32, device=coef.device)
-    status = torch.empty(n, dtype=torch.int32, device=coef.device)
-    capacity = out.numel() if capacity is None else int(capacity)
-    _lib.call('nimg_jpeg_encode_progressive', _p(coef), n, h, w, hs, vs, ri, _p(tables), _p(out), capacity, _p(lengths), _p(status),
-              _p(workspace), need, _stream())
-    return out, lengths, status
+    return _jpeg_encode('jpeg_encode_progressive', 'nimg_jpeg_encode_progressive', 'nimg_jpeg_progressive_workspace_bytes',
+                        jpeg_progressive_ecd_bound, JPEG_PROGRESSIVE_SCANS, (JPEG_PROGRESSIVE_SCANS,), coef, tables, h, w, hs, vs, out,
+                        workspace, capacity, restart_interval, kind='progressive JPEG', empty_ok=True)
 
 
 # any quantisation tables (DESIGN.md section 4h): a table set is (3, 64) uint16 [Y, Cb, Cr] in natural order, one set per item
@@ -2832,13 +2792,11 @@ def jpeg_transform_tables(x, qtabs, hs=1, vs=1, workspace=None, err=None):
     """(n_src,h,w,3) float32 or uint8 and one table set per item, qtabs (n_items, 3, 64) uint16 (or int16 bit patterns) in natural order
     on the device -> ((n_items, real blocks, 64) int16 coefficients laid out as jpeg_transform's, (1,) int32 error flag: non-zero = an
     entry outside 1..255 was clamped).  Item j codes source image j % n_src with qtabs[j]."""
-    _chk(x)
-    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
-        raise RuntimeError('jpeg_transform_tables needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(x.dtype, tuple(x.shape)))
+    _jpeg_rgb('jpeg_transform_tables', x)
     qtabs = _jpeg_qtabs(qtabs, 'jpeg_transform_tables')
     n_src, h, w, _ = x.shape
     n_items = qtabs.shape[0]
-    ws, need = _jpeg_workspace(n_items, h, w, hs, vs, x.device, workspace)
+    ws, need = _jpeg_pixel_workspace(n_items, h, w, hs, vs, x.device, workspace)
     coef = torch.empty((n_items, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
     err = torch.zeros((1,), dtype=torch.int32, device=x.device) if err is None else err
     _lib.call('nimg_jpeg_transform_tables', _p(x), int(x.dtype == torch.uint8), n_src, h, w, hs, vs, _p(qtabs), n_items, _p(coef), _p(err),

@@ -170,7 +170,7 @@ def test_header_pieces():
             assert pieces[0] == jh.jpeg_header(case.h, case.w, case.quality, case.subsampling, huffman=tables, qtables=cases.qtables(case),
                                                restart_interval=case.ri, progressive=True)
             assert pieces[6] == bytes.fromhex('ffda000c' '03' '0100' '0200' '0300' '00' '00' '10')          # no DHT in front of the DC refine scan
-            assert jh._progressive_file(case.h, case.w, case.quality, case.subsampling, segments, tables, cases.qtables(case), case.ri) == data
+            assert jh._jpeg_files(case.h, case.w, case.quality, case.subsampling, [segments], [tables], cases.qtables(case), case.ri, True) == [data]
 
 
 def test_refusals_and_defaults():

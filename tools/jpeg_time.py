@@ -78,9 +78,7 @@ def measure(x_host, quality, subsampling, reps, dev, ri=0):
     hs, vs = ops.jpeg_subsampling(subsampling)
     n, h, w, _ = x_host.shape
     x = torch.from_numpy(x_host).to(dev)
-    lib = ops._lib.load()
-    ws = torch.empty(int(lib.nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, ri) if ri else
-                         lib.nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(ops.jpeg_workspace_bytes(n, h, w, hs, vs, ri), dtype=torch.uint8, device=dev)
     out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
     ms = {}
     ms['transform'], coef = timed(lambda: ops.jpeg_transform(x, quality, hs, vs, workspace=ws), reps)
@@ -143,9 +141,7 @@ def measure_decode(x_host, quality, subsampling, reps, dev, ri=0):
     whole = -(-8 * max(len(s) for s in segments) // 32) * 32
     rows = []
     for subseq_bits in (256, 512, 1024, 2048, whole):
-        lib = ops._lib.load()
-        size = int(lib.nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, ri, ecd.numel(), subseq_bits) if ri else
-                   lib.nimg_jpeg_decode_workspace_bytes(n, h, w, hs, vs, ecd.numel(), subseq_bits))
+        size = int(ops._lib.load().nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, ri, ecd.numel(), subseq_bits))
         ws = torch.empty(size, dtype=torch.uint8, device=dev)
 
         def decode():
@@ -172,7 +168,7 @@ def measure_optimize(x_host, quality, subsampling, reps, dev):
     n, h, w, _ = x_host.shape
     lib = ops._lib.load()
     coef = ops.jpeg_transform(torch.from_numpy(x_host).to(dev), quality, hs, vs)
-    ws = torch.empty(int(lib.nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(ops.jpeg_workspace_bytes(n, h, w, hs, vs), dtype=torch.uint8, device=dev)
     ws_t = torch.empty(int(lib.nimg_jpeg_encode_tables_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
     out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
     hist = torch.empty((n, 4, 257), dtype=torch.int32, device=dev)
@@ -187,7 +183,7 @@ def measure_optimize(x_host, quality, subsampling, reps, dev):
     ms['encode_batch_total'], plain = timed(lambda: jpeg_helpers.encode_batch(x_host, quality, subsampling), max(3, reps // 4))
     ms['encode_batch_optimize_total'], files = timed(lambda: jpeg_helpers.encode_batch(x_host, quality, subsampling, optimize=True), max(3, reps // 4))
     assert [len(f) for f in plain] == (base + jpeg_helpers.JPEG_HEADER_BYTES + 2).tolist()
-    heads = jpeg_helpers._optimised_header_bytes(tables.cpu().numpy())
+    heads = jpeg_helpers._header_lengths(h, w, quality, subsampling, n, tables.cpu().numpy(), None, 0, False)
     assert [len(f) for f in files] == (lengths + heads + 2).tolist()
     return {'mode': 'optimize', 'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality,
             'segment_bytes': int(base.sum()), 'segment_bytes_optimize': int(lengths.sum()),
@@ -232,7 +228,7 @@ def measure_qtables(x_host, quality, subsampling, reps, dev):
     x = torch.from_numpy(x_host).to(dev)
     pair = np.stack([jpeg_helpers.libjpeg_qtable(quality, c).ravel() for c in (0, 1)])
     qt = jpeg_helpers._device_tables(jpeg_helpers.check_qtables(pair)[None], n, dev)
-    ws = torch.empty(int(ops._lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(ops.jpeg_workspace_bytes(n, h, w, hs, vs), dtype=torch.uint8, device=dev)
     out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
     ms = {}
     ms['transform'], (coef, err) = timed(lambda: ops.jpeg_transform_tables(x, qt, hs, vs, workspace=ws), reps)

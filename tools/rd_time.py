@@ -55,11 +55,10 @@ def measure(x_host, subsampling, reps, dev):
     hs, vs = ops.jpeg_subsampling(subsampling)
     n, h, w, _ = x_host.shape
     x = torch.from_numpy(x_host).to(dev)
-    size = ops._lib.load().nimg_jpeg_workspace_bytes
     items = np.repeat(QUALITIES, n)
     q = ops.jpeg_item_qualities(items, len(items), dev)
-    ws_items = torch.empty(int(size(len(items), h, w, hs, vs)), dtype=torch.uint8, device=dev)
-    ws = torch.empty(int(size(n, h, w, hs, vs)), dtype=torch.uint8, device=dev)
+    ws_items = torch.empty(ops.jpeg_workspace_bytes(len(items), h, w, hs, vs), dtype=torch.uint8, device=dev)
+    ws = torch.empty(ops.jpeg_workspace_bytes(n, h, w, hs, vs), dtype=torch.uint8, device=dev)
     out = torch.empty(n * (192 * ops.jpeg_geometry(h, w, hs, vs)[1] + 1024), dtype=torch.uint8, device=dev)
 
     def one_call_kernels():
