@@ -925,6 +925,31 @@ int nimg_jpeg_decode_restart(const uint8_t* ecd, const uint64_t* ecd_off, const 
                              int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* Reading progressive files: the entropy-coded segments of every scan of n files -> the coefficients of
+ * nimg_jpeg_transform, with any legal scan script (T.81 G.1.1.1).  All images of a call share the geometry, the restart interval and
+ * the script; tables and segments are per image.
+ *   ecd, ecd_off   the segments back to back as they stand in the files (stuffed, restart markers inside), image-major: segment
+ *                  image * n_scans + scan is the bytes [ecd_off[.], ecd_off[. + 1]) - n * n_scans + 1 offsets on the device.
+ *   script         HOST, n_scans x 6 int32: component mask (bit c = component c; 7 = all three interleaved, DC scans only), Ss, Se,
+ *                  Ah, Al, level.  1 <= n_scans <= 64.  A DC scan (Ss = Se = 0) holds one component or all three, an AC scan
+ *                  (1 <= Ss <= Se <= 63) one; a coefficient's first scan has Ah = 0, every later one Ah = the Al before it and
+ *                  Al = Ah - 1; a component's DC first scan precedes its AC scans; every coefficient of every component reaches
+ *                  Al = 0; level = 1 + the highest level of an earlier scan of a shared component whose band overlaps (a scan reads
+ *                  only what lower levels wrote; the scans of a level run side by side).  Anything else is NIMG_ERR_ARG before any
+ *                  launch, as is a workspace too short for the batch.
+ *   huffman        (device) [n][n_scans][3][272]: slot c = the table of the scan's c-th component (DC tables in a DC scan, the AC
+ *                  table in an AC scan), 16 counts + 256 symbols; zero where the scan has none (DC refine scans have no symbols).
+ *   coef, status   as nimg_jpeg_decode_restart; an image's status is the OR over its scans, the bits those of nimg_jpeg_decode and
+ *                  512, and 1024: an end-of-band run beyond the blocks of its scan (of its restart interval).  In a single-component
+ *                  scan the restart interval counts blocks.
+ *   rounds         (device) [n][n_scans]: the synchronisation rounds of every first scan (Ah = 0), 0 for a refinement.
+ * subseq_bits as nimg_jpeg_decode.  Purely added: NIMG_ABI_VERSION stays. */
+size_t nimg_jpeg_decode_progressive_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, int n_scans,
+                                                    size_t ecd_bytes, int subseq_bits);
+int nimg_jpeg_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans, const uint8_t* huffman,
+                                 int n, int h, int w, int hs, int vs, int restart_interval, int subseq_bits, int16_t* coef,
+                                 uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Sign planes of the FAN's bf16-stored pooled activations: all that a layer's input gradient reads of the
  * activation in front of it is LeakyReLU', one bit per value.  A plane is (n, h, w, c / 8) bytes next to a bf16 tensor (n, h, w, c),
  * c % 8 == 0: bit e of byte c' / 8 is 1 iff the STORED bf16 value of channel c' + e is > 0 (-0, +0 and NaN give 0) - the predicate of

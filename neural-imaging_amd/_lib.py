@@ -215,6 +215,8 @@ PROTOTYPES = {
     'nimg_jpeg_encode_tables_restart': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, P, c_size_t, P]),
     'nimg_jpeg_decode_restart_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_size_t, c_int]),
     'nimg_jpeg_decode_restart': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+    'nimg_jpeg_decode_progressive_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_size_t, c_int]),
+    'nimg_jpeg_decode_progressive': (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     'nimg_jpeg_progressive_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'nimg_jpeg_progressive_histogram': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     'nimg_jpeg_encode_progressive': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, P, c_size_t, P]),

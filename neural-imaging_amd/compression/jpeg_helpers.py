@@ -617,12 +617,29 @@ def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4',
 
 
 # ---- reading files ---------------------------------------------------------------------------------
-JPEGHeader = namedtuple('JPEGHeader', 'h w hs vs qtables huffman ecd_offset ecd_end restart_interval', defaults=(0,))
+class JPEGHeader(namedtuple('JPEGHeader', 'h w hs vs qtables huffman ecd_offset ecd_end restart_interval', defaults=(0,))):
+    """parse_header's result.  The tuple keeps the nine fields it had before progressive files were read (callers unpack it and count
+    on restart_interval as its last); `scans` - a JPEGScan per scan of a progressive file, () for a baseline file - is an attribute
+    next to them, set by with_scans."""
+    scans = ()
+
+    def with_scans(self, scans):
+        out = self._replace()
+        out.scans = tuple(scans)
+        return out
+
+
+# one scan of a progressive file: components (indices in frame order), the band and the bit positions of its SOS segment, huffman = the
+# (16 counts, symbols) table of each component of the scan (empty for a DC refine scan, which has no symbols), and where its
+# entropy-coded segment stands in the file
+JPEGScan = namedtuple('JPEGScan', 'components ss se ah al huffman ecd_offset ecd_end')
+JPEG_SCANS_MAX = ops.JPEG_SCANS_MAX
 JPEG_STATUS_BITS = OrderedDict([(1, 'marker inside the entropy-coded segment'), (2, 'invalid Huffman code'), (4, 'zig-zag index past 63'),
                                 (8, 'coefficient category out of range'), (16, 'bits needed beyond the end of the stream'),
                                 (32, 'fewer blocks than the scan has'), (64, 'DC value outside int16'),
                                 (128, 'Huffman table that is no prefix code'), (256, 'bad segment offsets'),
-                                (512, 'restart markers missing, surplus or out of sequence')])
+                                (512, 'restart markers missing, surplus or out of sequence'),
+                                (1024, 'end-of-band run beyond the blocks of the scan')])
 _MAX_SIDE = 4096
 _SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless', 0xc5: 'differential sequential',
               0xc6: 'differential progressive', 0xc7: 'differential lossless', 0xc9: 'arithmetic-coded sequential',
@@ -630,7 +647,7 @@ _SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless'
               0xce: 'arithmetic-coded differential progressive', 0xcf: 'arithmetic-coded differential lossless'}
 
 
-def parse_header(data, allow_restart=False):
+def parse_header(data, allow_restart=False, allow_progressive=False):
     """The header of a baseline JPEG file, read on the host without decoding: JPEGHeader(h, w, hs, vs, qtables (3, 64) uint16 in
     natural order per component, huffman = six (16 counts, symbols) pairs of bytes in the order Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC
     as the DHT bodies have them, ecd_offset, ecd_end = the offset of the final FFD9, restart_interval).  Accepted: SOF0 with 8-bit
@@ -639,14 +656,19 @@ def parse_header(data, allow_restart=False):
     reason.  allow_restart: a file with a restart interval (a DRI segment with a value above 0) is accepted
     too - restart_interval is that value in MCUs, and the markers FFD0 .. FFD7 in the entropy-coded segment are stepped over (their
     number and sequence are the decoder's to check, status bit 512).  Still refused: a restart marker in a file whose interval is 0,
-    and several DRI segments with different values (libjpeg would let the last one hold)."""
+    and several DRI segments with different values (libjpeg would let the last one hold).  allow_progressive: a progressive file
+    (SOF2, Huffman-coded, 8-bit samples, three components, the samplings above) is accepted too, with any legal scan script (DESIGN.md
+    section 4n).  All its scans are walked: `scans` holds one JPEGScan per scan with the tables in force at its SOS, `huffman` is (),
+    ecd_offset / ecd_end span the first scan to the final FFD9.  Refused by name: a script that breaks T.81's rules or leaves a
+    coefficient short of Al = 0, a restart interval that changes between scans, more than 64 scans, a DNL marker, a missing table,
+    any marker between scans but DHT, DRI, COM and APPn."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise ValueError('JPEG data: bytes needed, got {}'.format(type(data).__name__))
     data = bytes(data)
     if data[:2] != b'\xff\xd8':
         raise ValueError('not a JPEG file: no SOI marker')
     order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
-    qt, huff, frame, pos, restart = {}, {}, None, 2, None
+    qt, huff, frame, pos, restart, progressive = {}, {}, None, 2, None, False
     while True:
         if pos + 4 > len(data):
             raise ValueError('truncated file: no SOS marker')
@@ -676,16 +698,9 @@ def parse_header(data, allow_restart=False):
                 qt[body[k] & 15] = table
                 k += 65
         elif marker == 0xc4:
-            k = 0
-            while k < len(body):
-                if k + 17 > len(body) or (body[k] >> 4) > 1 or (body[k] & 15) > 3:
-                    raise ValueError('malformed DHT segment')
-                count = sum(body[k + 1:k + 17])
-                if count > 256 or k + 17 + count > len(body):
-                    raise ValueError('malformed DHT segment')
-                huff[body[k]] = (bytes(body[k + 1:k + 17]), bytes(body[k + 17:k + 17 + count]))
-                k += 17 + count
-        elif marker == 0xc0:
+            huff.update(_dht_tables(body))
+        elif marker == 0xc0 or (marker == 0xc2 and allow_progressive):
+            progressive = marker == 0xc2
             if frame is not None:
                 raise ValueError('several frame headers')
             if len(body) < 6 or len(body) != 6 + 3 * body[5]:
@@ -726,6 +741,8 @@ def parse_header(data, allow_restart=False):
     if frame is None:
         raise ValueError('no frame header (SOF0) before the scan')
     h, w, comps = frame
+    if progressive:
+        return _parse_scans(data, pos, frame, qt, huff, restart or 0, allow_restart)
     if len(body) < 1 or len(body) != 4 + 2 * body[0]:
         raise ValueError('malformed SOS segment')
     if body[0] != 3:
@@ -772,39 +789,196 @@ def parse_header(data, allow_restart=False):
     return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, tuple(tables), ecd_offset, k, restart or 0)
 
 
+def _segment_end(data, k, restart, allow_restart):
+    """The offset of the first marker behind the entropy-coded segment that starts at k; restart markers are stepped over."""
+    while True:
+        k = data.find(b'\xff', k)
+        if k < 0 or k + 1 >= len(data):
+            raise ValueError('no EOI marker behind the entropy-coded segment')
+        nxt = data[k + 1]
+        if nxt == 0:
+            k += 2
+        elif 0xd0 <= nxt <= 0xd7:
+            if not allow_restart:
+                raise ValueError('restart marker FF{:02X} in the entropy-coded segment: files with restart markers are not read'.format(nxt))
+            if not restart:
+                raise ValueError('restart marker FF{:02X} in the entropy-coded segment of a file whose restart interval is 0'.format(nxt))
+            k += 2
+        elif nxt == 0xff:
+            k += 1
+        else:
+            return k
+
+
+def jpeg_script_check(script):
+    """script: [(components, Ss, Se, Ah, Al)] -> the level of every scan (1 + the highest level of an earlier
+    scan of a shared component whose band overlaps); ValueError names the rule of T.81 G.1.1.1 a script breaks."""
+    if len(script) > JPEG_SCANS_MAX:
+        raise ValueError('progressive file with {} scans (at most {} are read)'.format(len(script), JPEG_SCANS_MAX))
+    al_of, levels = [[None] * 64 for _ in range(3)], []
+    for i, (cs, ss, se, ah, al) in enumerate(script):
+        where = 'scan {} (components {} Ss={} Se={} Ah={} Al={})'.format(i, list(cs), ss, se, ah, al)
+        if ss == 0 and se != 0:
+            raise ValueError('illegal progressive script: {} mixes DC and AC coefficients'.format(where))
+        if ss > se or se > 63 or ah > 13 or al > 13:
+            raise ValueError('illegal progressive script: {} has a band or bit position out of range'.format(where))
+        if tuple(cs) not in ((0,), (1,), (2,), (0, 1, 2)) or (ss > 0 and len(cs) != 1):
+            raise ValueError('illegal progressive script: {} - a DC scan holds one component or all three in frame order, an AC scan '
+                             'exactly one'.format(where))
+        for c in cs:
+            if ss > 0 and al_of[c][0] is None:
+                raise ValueError('illegal progressive script: {} comes before the DC first scan of its component'.format(where))
+            for k in range(ss, se + 1):
+                if (al_of[c][k] is not None) if ah == 0 else (al_of[c][k] != ah or al != ah - 1):
+                    raise ValueError('illegal progressive script: {} - a first scan has Ah = 0 and is the first of its coefficients, a '
+                                     'refinement has Ah = the Al before it and Al = Ah - 1'.format(where))
+                al_of[c][k] = al
+        levels.append(1 + max([lv for lv, (ce, se0, se1, _, _) in zip(levels, script) if set(ce) & set(cs) and se0 <= se and ss <= se1]
+                              or [0]))
+    short = [(c, k) for c in range(3) for k in range(64) if al_of[c][k] != 0]
+    if short:
+        raise ValueError('incomplete progression: coefficient {} of component {} never reaches Al = 0 ({} such coefficients; libjpeg '
+                         'smooths such files)'.format(short[0][1], short[0][0], len(short)))
+    return levels
+
+
+def _parse_scans(data, pos, frame, qt, huff, restart, allow_restart):
+    """The scans of a progressive file from its first SOS marker (at pos) on -> its JPEGHeader."""
+    h, w, comps = frame
+    huff, scans = dict(huff), []
+    ids = [c[0] for c in comps]
+    while True:
+        size = struct.unpack_from('>H', data, pos + 2)[0]
+        body = data[pos + 4:pos + 2 + size]
+        if len(body) < 1 or len(body) != 4 + 2 * body[0]:
+            raise ValueError('malformed SOS segment')
+        if len(scans) == JPEG_SCANS_MAX:
+            raise ValueError('progressive file with more than {} scans'.format(JPEG_SCANS_MAX))
+        ns = body[0]
+        if any(body[1 + 2 * c] not in ids for c in range(ns)):
+            raise ValueError('malformed SOS segment: unknown component')
+        cs = tuple(ids.index(body[1 + 2 * c]) for c in range(ns))
+        ss, se, ah, al = body[1 + 2 * ns], body[2 + 2 * ns], body[3 + 2 * ns] >> 4, body[3 + 2 * ns] & 15
+        tables = []
+        for c in range(ns):
+            sel = body[2 + 2 * c]
+            if (sel >> 4) > 3 or (sel & 15) > 3:
+                raise ValueError('malformed SOS segment')
+            if ss == 0 and ah:
+                tables.append((bytes(16), b''))
+                continue
+            key = (sel >> 4) if ss == 0 else (0x10 | (sel & 15))
+            if key not in huff:
+                raise ValueError('missing Huffman table: {} table {} of component {} in scan {}'.format(
+                    'AC' if ss else 'DC', key & 15, cs[c], len(scans)))
+            tables.append(huff[key])
+        start = pos + 2 + size
+        k = _segment_end(data, start, restart, allow_restart)
+        scans.append(JPEGScan(cs, ss, se, ah, al, tuple(tables), start, k))
+        pos = k
+        while True:                                                      # the markers between two scans
+            marker = data[pos + 1]
+            if marker == 0xd9:
+                break
+            if pos + 4 > len(data):
+                raise ValueError('truncated file behind scan {}'.format(len(scans) - 1))
+            size = struct.unpack_from('>H', data, pos + 2)[0]
+            if size < 2 or pos + 2 + size > len(data):
+                raise ValueError('truncated segment FF{:02X} at offset {}'.format(marker, pos))
+            body = data[pos + 4:pos + 2 + size]
+            if marker == 0xda:
+                break
+            if marker == 0xc4:
+                huff.update(_dht_tables(body))
+            elif marker == 0xdd:
+                if len(body) != 2:
+                    raise ValueError('malformed DRI segment')
+                value = struct.unpack('>H', body)[0]
+                if value != restart:
+                    raise ValueError('the restart interval changes between scans ({} then {}): not read'.format(restart, value))
+            elif marker == 0xdc:
+                raise ValueError('DNL marker behind scan {}: not read'.format(len(scans) - 1))
+            elif not (0xe0 <= marker <= 0xef or marker == 0xfe):
+                raise ValueError('unsupported marker FF{:02X} between the scans of a progressive file'.format(marker))
+            pos += 2 + size
+            while pos + 1 < len(data) and data[pos] == 0xff and data[pos + 1] == 0xff:          # fill bytes
+                pos += 1
+            if pos + 1 >= len(data):
+                raise ValueError('truncated file behind scan {}: no EOI marker'.format(len(scans) - 1))
+            if data[pos] != 0xff:
+                raise ValueError('no marker at offset {}'.format(pos))
+        if data[pos + 1] == 0xd9:
+            break
+    jpeg_script_check([s[:5] for s in scans])
+    qtables = np.zeros((3, 64), np.uint16)
+    for c in range(3):
+        if comps[c][3] not in qt:
+            raise ValueError('missing quantisation table {} of component {}'.format(comps[c][3], c))
+        qtables[c] = qt[comps[c][3]]
+    return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, (), scans[0].ecd_offset, pos, restart).with_scans(scans)
+
+
+def _dht_tables(body):
+    """The tables of one DHT segment: {Tc << 4 | Th: (16 counts, symbols)}."""
+    out, k = {}, 0
+    while k < len(body):
+        if k + 17 > len(body) or (body[k] >> 4) > 1 or (body[k] & 15) > 3:
+            raise ValueError('malformed DHT segment')
+        count = sum(body[k + 1:k + 17])
+        if count > 256 or k + 17 + count > len(body):
+            raise ValueError('malformed DHT segment')
+        out[body[k]] = (bytes(body[k + 1:k + 17]), bytes(body[k + 17:k + 17 + count]))
+        k += 17 + count
+    return out
+
+
 def _status_text(status):
     return ' | '.join(text for bit, text in JPEG_STATUS_BITS.items() if status & bit)
 
 
-def _decode_groups(files, subseq_bits, device, allow_restart=False):
-    """Headers parsed, one upload, one nimg_jpeg_decode[_restart] per group of equal (h, w, hs, vs, restart interval).  Returns
+def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progressive=False):
+    """Headers parsed, one upload, one nimg_jpeg_decode[_restart] per group of equal (h, w, hs, vs, restart interval) - for progressive
+    files (allow_progressive) one nimg_jpeg_decode_progressive per group of equal geometry, interval and scan script.  Returns
     (headers, groups) with groups = [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back."""
-    headers = [parse_header(f, allow_restart) for f in files]
+    headers = [parse_header(f, allow_restart, allow_progressive) for f in files]
     if not headers:
         raise ValueError('no files to decode')
     keys = OrderedDict()
     for i, hd in enumerate(headers):
-        keys.setdefault((hd.h, hd.w, hd.hs, hd.vs, hd.restart_interval), []).append(i)
+        keys.setdefault((hd.h, hd.w, hd.hs, hd.vs, hd.restart_interval, tuple(s[:5] for s in hd.scans)), []).append(i)
     dev = device if device is not None else default_device()
     order = [i for idx in keys.values() for i in idx]                    # the segments back to back, group after group
-    blob = b''.join(files[i][headers[i].ecd_offset:headers[i].ecd_end] for i in order)
-    huff = np.zeros((len(order), 6, 272), np.uint8)
-    for j, i in enumerate(order):
-        for t, (counts, symbols) in enumerate(headers[i].huffman):
-            huff[j, t, :16] = np.frombuffer(counts, np.uint8)
-            huff[j, t, 16:16 + len(symbols)] = np.frombuffer(symbols, np.uint8)
+    spans = [[(s.ecd_offset, s.ecd_end) for s in headers[i].scans] or [(headers[i].ecd_offset, headers[i].ecd_end)] for i in order]
+    blob = b''.join(files[i][lo:hi] for i, sp in zip(order, spans) for lo, hi in sp)
+    tables = []                                                          # baseline: six per file; progressive: three per scan
+    for i in order:
+        per = [headers[i].huffman] if not headers[i].scans else [s.huffman + ((bytes(16), b''),) * (3 - len(s.huffman))
+                                                                 for s in headers[i].scans]
+        tables += [t for group in per for t in group]
+    huff = np.zeros((len(tables), 272), np.uint8)
+    for j, (counts, symbols) in enumerate(tables):
+        huff[j, :16] = np.frombuffer(counts, np.uint8)
+        huff[j, 16:16 + len(symbols)] = np.frombuffer(symbols, np.uint8)
     qt = np.stack([headers[i].qtables for i in order]).view(np.int16)
     ecd = torch.from_numpy(np.frombuffer(blob if blob else b'\0', np.uint8).copy()).to(dev)
     huff, qt = torch.from_numpy(huff).to(dev), torch.from_numpy(qt).to(dev)
-    groups, j0, b0 = [], 0, 0
-    for (h, w, hs, vs, ri), idx in keys.items():
-        lengths = [headers[i].ecd_end - headers[i].ecd_offset for i in idx]
+    groups, j0, b0, t0 = [], 0, 0, 0
+    for (h, w, hs, vs, ri, script), idx in keys.items():
+        lengths = [hi - lo for sp in spans[j0:j0 + len(idx)] for lo, hi in sp]
         off = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
         part = ecd[b0:b0 + max(sum(lengths), 1)]
-        coef, status, rounds = ops.jpeg_decode(part, off, huff[j0:j0 + len(idx)], h, w, hs, vs, subseq_bits=subseq_bits,
-                                               restart_interval=ri)
+        if script:
+            rows = np.array([[sum(1 << c for c in cs), ss, se, ah, al, lv]
+                             for (cs, ss, se, ah, al), lv in zip(script, jpeg_script_check(script))], np.int32)
+            count = len(idx) * len(script) * 3
+            coef, status, rounds = ops.jpeg_decode_progressive(part, off, huff[t0:t0 + count].view(len(idx), len(script), 3, 272), rows, h, w,
+                                                               hs, vs, subseq_bits=subseq_bits, restart_interval=ri)
+        else:
+            count = len(idx) * 6
+            coef, status, rounds = ops.jpeg_decode(part, off, huff[t0:t0 + count].view(len(idx), 6, 272), h, w, hs, vs,
+                                                   subseq_bits=subseq_bits, restart_interval=ri)
         groups.append((idx, (h, w, hs, vs), coef, status, rounds, qt[j0:j0 + len(idx)]))
-        j0, b0 = j0 + len(idx), b0 + sum(lengths)
+        j0, b0, t0 = j0 + len(idx), b0 + sum(lengths), t0 + count
     return headers, groups
 
 
@@ -821,16 +995,18 @@ def _as_files(files):
     return [bytes(files)] if isinstance(files, (bytes, bytearray, memoryview)) else [bytes(f) for f in files]
 
 
-def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False):
+def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False):
     """Decode baseline JPEG files on the GPU: a list of bytes (or one bytes) -> (n,h,w,3) uint8, the array imageio.imread returns for
     each (libjpeg's islow inverse DCT and fancy up-sampling, bit for bit), or float32(byte) / 255 with as_float.  Files of different
     geometry give a list of (h,w,3) arrays in input order.  Any 8-bit quantisation and Huffman tables are read from each file
     (parse_header names what is refused).  The segments go up in one copy, every group of equal (h, w, sampling) takes one decode and
     one reconstruct call, status and images come down once; device_output keeps the images on the device.  Damaged data raises
     ValueError naming the indices and the status bits (JPEG_STATUS_BITS).  allow_restart: files with a restart interval are read
-    too (parse_header); a group is then the files of equal geometry and interval, and every interval is decoded from its own start."""
+    too (parse_header); a group is then the files of equal geometry and interval, and every interval is decoded from its own start.
+    allow_progressive: progressive files of any legal scan script are read too (parse_header), next to baseline
+    ones in the same call; a group is then the files of equal geometry, interval and script (nimg_jpeg_decode_progressive)."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive)
     images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
               for _, (h, w, hs, vs), coef, _, _, qt in groups]
     words = [len(g[0]) for g in groups]
@@ -855,22 +1031,23 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     return result
 
 
-def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, *, allow_restart=False):
+def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False):
     """The quantised coefficients of baseline files of ONE geometry, as stored in the files: ((n, real blocks, 64) int16 in the layout
     of DESIGN.md section 4c - [Y | Cb | Cr][block row][block col][zig-zag] - and the (n, 3, 64) uint16 quantisation tables per
     component in natural order; jpeg_qf_estimation(tables[i, c].reshape(8, 8), c) names the quality they came from).
-    allow_restart: as decode_batch's; the files must then share their restart interval too."""
+    allow_restart: as decode_batch's; the files must then share their restart interval too.  allow_progressive: as decode_batch's;
+    the files must then share their scan script too (baseline files count as one script)."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive)
     if len(groups) != 1:
         raise ValueError('decode_coefficients needs files of one geometry{}, got {}'.format(
-            ' and restart interval' if allow_restart else '', [g[1] for g in groups]))
+            (' and restart interval' if allow_restart else '') + (' and scan script' if allow_progressive else ''), [g[1] for g in groups]))
     _, _, coef, status, _, _ = groups[0]
     _raise_on_status(groups, [status.cpu().numpy()])
     return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
 
 
-def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False):
+def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False, allow_progressive=False):
     """Baseline files written again with their coefficients and their quantisation tables untouched - a list of bytes in input order.
     The Huffman tables are the optimal ones of each image (what jpegtran -optimize does) or, with optimize=False, Annex K's.  Every
     file parse_header accepts is read; the header written is the one of encode_batch - JFIF APP0, two DQT segments where the file's Cb
@@ -878,9 +1055,11 @@ def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=Fa
     sampling) is decoded (nimg_jpeg_decode) and coded again on the device without a pixel being computed.  Damaged data raises as in
     decode_batch.  allow_restart: files with a restart interval are read too, and every file keeps its interval - DRI segment and
     markers are written again.  progressive: baseline files in, progressive files out (the lossless jpegtran -progressive); their
-    tables are optimal whatever `optimize` says."""
+    tables are optimal whatever `optimize` says.  allow_progressive: progressive files of any legal scan script are read too
+    (parse_header) and written as baseline files - jpegtran -optimize of a progressive file - or, with progressive, as libjpeg's simple
+    progression whatever script came in."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, 0, None, allow_restart)
+    headers, groups = _decode_groups(files, 0, None, allow_restart, allow_progressive)
     _raise_on_status(groups, np.split(torch.cat([g[3] for g in groups]).cpu().numpy(), np.cumsum([len(g[0]) for g in groups])[:-1]))
     names = {v: k for k, v in ops.JPEG_SUBSAMPLING.items()}
     result = [None] * len(files)

@@ -20,6 +20,7 @@
 // again, a run ends with its interval's blocks, and the DC sums restart with every interval.
 #include "jpegc.h"
 #include "jpegd.h"
+#include "jpegd_prepare.h"
 
 namespace {
 
@@ -96,15 +97,8 @@ __device__ __forceinline__ size_t slot_start(const DArgs& a, uint64_t off, int i
 }
 
 // ---- prepare ------------------------------------------------------------------------------------------------------------
-// what the un-stuffing scan sums: the bytes kept - with restart intervals also the markers met, in the upper half
-template <bool RST> struct PrepSum { typedef uint32_t type; };
-template <> struct PrepSum<true> { typedef unsigned long long type; };
-
 template <bool RST>
 __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DLayout d) {
-    typedef typename PrepSum<RST>::type Sum;
-    __shared__ Sum wtot[SCAN_THREADS / 64];
-    __shared__ uint32_t s_max;
     const int img = blockIdx.x, tid = threadIdx.x;
     const uint64_t o0 = a.off[img], o1 = a.off[img + 1];
     uint32_t* ibit = RST ? d.ibit + (size_t)img * (a.K + 1u) : nullptr;
@@ -118,76 +112,8 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DL
     }
     if (tid < 6 && !jpegd_build_table(a.huffman + ((size_t)img * 6 + tid) * JPEGD_DHT_BYTES, d.tabs + (size_t)img * 6 + tid))
         atomicOr(a.status + img, JPEGD_ST_TABLE);
-    const uint32_t len = (uint32_t)(o1 - o0), cap_bytes = ((len + 3u) / 4u + 1u) * 4u;
-    const uint8_t* src = a.ecd + o0;
-    uint8_t* out = (uint8_t*)(d.raw + raw_start(o0, img));
-    Sum carry = 0;
-    uint32_t flags = 0;
-    for (uint32_t base = 0; base < len; base += 4u * SCAN_THREADS) {
-        const uint32_t j = base + 4u * tid;
-        uint8_t b[6];                                  // the byte before, four of this thread's, the byte after
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            const uint32_t k = j + (uint32_t)q - 1u;
-            b[q] = (j + (uint32_t)q >= 1u && k < len) ? src[k] : (uint8_t)1;        // outside the segment: neither FF nor 00
-        }
-        uint32_t keep = 0, kept = 0, mark = 0, marks = 0;
-#pragma unroll
-        for (int q = 1; q <= 4; ++q) {
-            if (j + (uint32_t)q - 1u >= len) break;
-            if (RST && b[q] == 0xff && (b[q + 1] & 0xf8) == 0xd0) { mark |= 1u << q; ++marks; continue; }       // a restart marker:
-            if (RST && b[q - 1] == 0xff && (b[q] & 0xf8) == 0xd0) continue;                                      // both bytes go
-            if (b[q] == 0xff && b[q + 1] != 0) flags |= JPEGD_ST_MARKER;
-            if (!(b[q] == 0 && b[q - 1] == 0xff)) { keep |= 1u << q; ++kept; }
-        }
-        Sum sum;
-        const Sum before = carry + block_excl_scan((Sum)kept | (RST ? (Sum)((unsigned long long)marks << 32) : (Sum)0), wtot, sum);
-        carry += sum;
-        uint32_t at = (uint32_t)before, idx = RST ? (uint32_t)((unsigned long long)before >> 32) : 0u;
-#pragma unroll
-        for (int q = 1; q <= 4; ++q) {
-            if (keep >> q & 1u) {
-                if (at < cap_bytes) out[(at & ~3u) + 3u - (at & 3u)] = b[q];       // byte k of the stream: bits 31 - 8 (k & 3) .. of word k / 4
-                ++at;
-            }
-            if (RST && (mark >> q & 1u)) flags |= jpegd_marker(idx++, b[q + 1], at, a.K, ibit);
-        }
-    }
-    const uint32_t total = 8u * (uint32_t)carry;
-    if (!RST) {
-        if (flags) atomicOr(a.status + img, flags);
-        if (tid == 0) {
-            d.total_bits[img] = total;
-            d.nsub[img] = total == 0 ? 1u : (total + a.sb - 1u) / a.sb;
-        }
-        return;
-    }
-    // the interval table: the markers met filled entries 1 .. their number; the intervals of missing markers are empty
-    const uint32_t met = (uint32_t)((unsigned long long)carry >> 32);
-    if (met + 1u != a.K) flags |= JPEGD_ST_RESTART;
-    if (flags) atomicOr(a.status + img, flags);
-    for (uint32_t k = min(met, a.K - 1u) + 1u + tid; k <= a.K; k += SCAN_THREADS) ibit[k] = total;
-    if (tid == 0) { ibit[0] = 0; s_max = 0; }
-    __syncthreads();
-    // the subsequences: every interval is cut on its own
-    uint32_t first = 0, longest = 0;
-    for (uint32_t base = 0; base < a.K; base += SCAN_THREADS) {
-        const uint32_t k = base + tid;
-        const uint32_t subs = k < a.K ? jpegd_interval_subs(ibit[k + 1u] - ibit[k], a.sb) : 0u;
-        uint32_t sum;
-        const uint32_t ex = first + block_excl_scan(subs, (uint32_t*)wtot, sum);
-        first += sum;
-        if (k < a.K) sub0[k] = ex;
-        longest = max(longest, subs);
-    }
-    atomicMax(&s_max, longest);
-    __syncthreads();
-    if (tid == 0) {
-        sub0[a.K] = first;
-        d.total_bits[img] = total;
-        d.nsub[img] = first;
-        d.maxsub[img] = s_max;
-    }
+    jpegd_prepare_segment<RST>(a.ecd + o0, (uint32_t)(o1 - o0), (uint8_t*)(d.raw + raw_start(o0, img)), a.K, a.sb, ibit, sub0, a.status + img,
+                               d.total_bits + img, d.nsub + img, RST ? d.maxsub + img : nullptr);
 }
 
 // the six tables of an image into LDS

@@ -2676,6 +2676,45 @@ def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspac
     return coef, status, rounds
 
 
+JPEG_SCANS_MAX = 64
+
+
+def jpeg_decode_progressive(ecd, ecd_off, huffman, script, h, w, hs=1, vs=1, subseq_bits=0, workspace=None, *, restart_interval=0):
+    """The entropy-coded segments of the scans of n progressive files of one geometry, restart interval and scan script
+    (nimg_jpeg_decode_progressive) -> (coefficients (n, real blocks, 64) int16 as jpeg_decode gives them, status
+    (n,) int32 - the OR over an image's scans of include/nimg.h's bits - and rounds (n, n_scans) int32, the synchronisation rounds of
+    every first scan).  ecd: uint8 device tensor, the segments back to back, image-major; ecd_off: (n * n_scans + 1,) int64 offsets
+    into it; huffman: (n, n_scans, 3, 272) uint8, slot c = the table of the scan's c-th component, zero where it has none; script:
+    (n_scans, 6) int32 on the host - component mask, Ss, Se, Ah, Al, level.  A script that breaks the rules of the header comment is
+    refused by the library (NIMG_ERR_ARG) before anything is launched."""
+    _chk(ecd)
+    _chk(ecd_off)
+    _chk(huffman)
+    script = np.ascontiguousarray(script, np.int32)
+    if script.ndim != 2 or script.shape[1] != 6 or not 1 <= script.shape[0] <= JPEG_SCANS_MAX:
+        raise RuntimeError('jpeg_decode_progressive: script {}, (1..{}, 6) int32 needed'.format(script.shape, JPEG_SCANS_MAX))
+    n_scans = script.shape[0]
+    n = (ecd_off.numel() - 1) // n_scans
+    if ecd.dtype != torch.uint8 or ecd_off.dtype != torch.int64 or n < 1 or ecd_off.numel() != n * n_scans + 1:
+        raise RuntimeError('jpeg_decode_progressive: uint8 segments and (n * {} + 1,) int64 offsets needed, got {} and {} {}'.format(
+            n_scans, ecd.dtype, ecd_off.dtype, tuple(ecd_off.shape)))
+    if huffman.dtype != torch.uint8 or tuple(huffman.shape) != (n, n_scans, 3, 272):
+        raise RuntimeError('jpeg_decode_progressive: Huffman tables {} {}, ({}, {}, 3, 272) uint8 needed'.format(
+            huffman.dtype, tuple(huffman.shape), n, n_scans))
+    subseq_bits = int(subseq_bits)
+    ri = jpeg_restart_interval(restart_interval)
+    workspace, _ = _jpeg_workspace(
+        _lib.load().nimg_jpeg_decode_progressive_workspace_bytes(n, h, w, hs, vs, ri, n_scans, ecd.numel(), subseq_bits),
+        '{} scans={} subseq_bits={}'.format(_jpeg_batch(n, h, w, hs, vs), n_scans, subseq_bits), ecd.device, workspace,
+        name='JPEG decode workspace')
+    coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
+    status = torch.empty(n, dtype=torch.int32, device=ecd.device)
+    rounds = torch.empty((n, n_scans), dtype=torch.int32, device=ecd.device)
+    _lib.call('nimg_jpeg_decode_progressive', _p(ecd), _p(ecd_off), script.ctypes.data, n_scans, _p(huffman), n, h, w, hs, vs, ri,
+              subseq_bits, _p(coef), _p(status), _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    return coef, status, rounds
+
+
 def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspace=None, out=None):
     """jpeg_reconstruct with the quantisation tables given per image and component: qtabs (n, 3, 64) uint16 (or int16 bit patterns)
     in natural order.  Returns (n,h,w,3) uint8 - the bytes libjpeg decodes - when out_u8, else float32 = byte / 255."""

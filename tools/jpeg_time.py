@@ -27,8 +27,14 @@ per sub-sampling.
 --restart N / --restart-rows R give the files a restart interval of N MCUs / of R MCU rows at either
 sub-sampling: the default mode then times nimg_jpeg_encode_restart and compress_batch(restart_interval=), and --decode times
 nimg_jpeg_decode_restart and decode_batch(allow_restart=True) on those files.  Every line names its interval.
+--decode-progressive times reading progressive files on the files encode_batch(progressive=True) writes for
+the same images: nimg_jpeg_decode_progressive as a whole and per kernel kind (prepare, first scans, DC refine, AC refine - from the
+profiler's kernel records), the synchronisation rounds of the first scans, and decode_batch(allow_progressive=True) from bytes to
+bytes next to decode_batch on the baseline twins of the same coefficients (encode_batch(optimize=True)) in the same process, at
+subseq_bits 256, 512, 1024, 2048 and at one subsequence per scan and interval.  One JSON line per sub-sampling and setting.
 
-    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20] [--pillow | --decode | --optimize | --progressive | --qtables]
+    python tools/jpeg_time.py --batch 64 --size 256 --quality 75 [--reps 20]
+                              [--pillow | --decode | --decode-progressive | --optimize | --progressive | --qtables]
                               [--restart N | --restart-rows R]
 For the split of the calls into their kernels: rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_time.py ...
 """
@@ -103,8 +109,9 @@ DECODE_STAGES = (('prepare', ('jpegd_prepare_kernel',)), ('speculate', ('jpegd_d
                  ('dc', ('jpegd_dc_kernel',)))
 
 
-def kernel_ms(fn, reps):
+def kernel_ms(fn, reps, stages=None):
     """mean milliseconds per call of every decoder kernel, from the profiler's device records; None where it records none"""
+    stages = DECODE_STAGES if stages is None else stages
     from torch.profiler import ProfilerActivity, profile
     try:
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
@@ -115,7 +122,7 @@ def kernel_ms(fn, reps):
     except Exception:
         return None
     out = {}
-    for stage, keys in DECODE_STAGES:
+    for stage, keys in stages:
         times = [t for name, t in events if any(k in name for k in keys)]
         if not times:                                                # a stage without a record: no partial table
             return None
@@ -161,6 +168,58 @@ def measure_decode(x_host, quality, subsampling, reps, dev, ri=0):
                      'ms': {k: round(v, 4) for k, v in ms.items()}, 'kernel_ms': kernel_ms(decode, reps),
                      'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}})
     return rows
+
+
+PROGRESSIVE_STAGES = (('prepare', ('jpegd_prog_prepare_kernel',)), ('first', ('jpegd_prog_first_kernel',)),
+                      ('dc_refine', ('jpegd_prog_dc_refine_kernel',)), ('ac_refine', ('jpegd_prog_ac_refine_kernel',)))
+
+
+def measure_decode_progressive(x_host, quality, subsampling, reps, dev):
+    """one dict per subseq_bits setting"""
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    n, h, w, _ = x_host.shape
+    files = jpeg_helpers.encode_batch(x_host, quality, subsampling, progressive=True)
+    twins = jpeg_helpers.encode_batch(x_host, quality, subsampling, optimize=True)
+    heads = [jpeg_helpers.parse_header(f, allow_progressive=True) for f in files]
+    script = [s[:5] for s in heads[0].scans]
+    assert all([s[:5] for s in hd.scans] == script for hd in heads)
+    rows6 = np.array([[sum(1 << c for c in cs), ss, se, ah, al, lv]
+                      for (cs, ss, se, ah, al), lv in zip(script, jpeg_helpers.jpeg_script_check(script))], np.int32)
+    segments = [f[s.ecd_offset:s.ecd_end] for f, hd in zip(files, heads) for s in hd.scans]
+    ecd = torch.from_numpy(np.frombuffer(b''.join(segments), np.uint8).copy()).to(dev)
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(s) for s in segments])]).astype(np.int64)).to(dev)
+    huff = np.zeros((n, len(script), 3, 272), np.uint8)
+    for i, hd in enumerate(heads):
+        for k, sc in enumerate(hd.scans):
+            for c, (counts, symbols) in enumerate(sc.huffman):
+                huff[i, k, c, :16], huff[i, k, c, 16:16 + len(symbols)] = np.frombuffer(counts, np.uint8), np.frombuffer(symbols, np.uint8)
+    huff = torch.from_numpy(huff).to(dev)
+    want = ops.jpeg_transform(torch.from_numpy(x_host).to(dev), quality, hs, vs)
+    first = [k for k, sc in enumerate(script) if sc[3] == 0]
+    whole = -(-8 * max(len(s) for s in segments) // 32) * 32
+    out = []
+    for subseq_bits in (256, 512, 1024, 2048, whole):
+        size = int(ops._lib.load().nimg_jpeg_decode_progressive_workspace_bytes(n, h, w, hs, vs, 0, len(script), ecd.numel(), subseq_bits))
+        ws = torch.empty(size, dtype=torch.uint8, device=dev)
+
+        def decode():
+            return ops.jpeg_decode_progressive(ecd, off, huff, rows6, h, w, hs, vs, subseq_bits=subseq_bits, workspace=ws)
+        ms = {}
+        ms['decode_progressive'], (coef, status, rounds) = timed(decode, reps)
+        assert int(status.abs().sum()) == 0 and torch.equal(coef, want)
+        ms['decode_batch_progressive'], yp = timed(
+            lambda: jpeg_helpers.decode_batch(files, subseq_bits=subseq_bits, allow_progressive=True), max(3, reps // 4))
+        ms['decode_batch_baseline_twins'], yb = timed(lambda: jpeg_helpers.decode_batch(twins, subseq_bits=subseq_bits), max(3, reps // 4))
+        assert np.array_equal(yp, yb)
+        r = rounds.cpu().numpy()[:, first]
+        out.append({'mode': 'decode_progressive', 'subsampling': subsampling, 'batch': n, 'size': [h, w], 'quality': quality,
+                    'subseq_bits': subseq_bits, 'sequential': subseq_bits == whole, 'segment_bytes': int(ecd.numel()),
+                    'baseline_bytes': sum(len(f) for f in twins), 'progressive_bytes': sum(len(f) for f in files), 'workspace_bytes': size,
+                    'rounds': {'min': int(r.min()), 'median': float(np.median(r)), 'max': int(r.max())},
+                    'rounds_per_scan_max': r.max(axis=0).tolist(),
+                    'ms': {k: round(v, 4) for k, v in ms.items()}, 'kernel_ms': kernel_ms(decode, reps, PROGRESSIVE_STAGES),
+                    'images_per_s': {k: n / v * 1e3 for k, v in ms.items()}})
+    return out
 
 
 def measure_optimize(x_host, quality, subsampling, reps, dev):
@@ -267,6 +326,7 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--pillow', action='store_true', help='time Pillow on the host instead (no GPU needed)')
     ap.add_argument('--decode', action='store_true', help='time the decoder instead, per subseq_bits setting')
+    ap.add_argument('--decode-progressive', action='store_true', help='time reading progressive files, per subseq_bits setting')
     ap.add_argument('--optimize', action='store_true', help='time writing with optimised Huffman tables next to nimg_jpeg_encode')
     ap.add_argument('--progressive', action='store_true', help='time writing progressive files next to nimg_jpeg_encode_tables')
     ap.add_argument('--qtables', action='store_true', help="time the table form with libjpeg's tables of --quality instead")
@@ -286,6 +346,12 @@ def main():
             ri = interval_of(args, args.size, args.size, subsampling)
             measure_decode(x[:4], args.quality, subsampling, 2, dev, ri)              # warm-up
             for row in measure_decode(x, args.quality, subsampling, args.reps, dev, ri):
+                print(json.dumps(dict(row, csrc_sha16=csrc_sha16())), flush=True)
+        return
+    if args.decode_progressive:
+        for subsampling in SUBSAMPLINGS:
+            measure_decode_progressive(x[:4], args.quality, subsampling, 2, dev)      # warm-up
+            for row in measure_decode_progressive(x, args.quality, subsampling, args.reps, dev):
                 print(json.dumps(dict(row, csrc_sha16=csrc_sha16())), flush=True)
         return
     if args.optimize:
