@@ -47,8 +47,11 @@ static const float COLOR_I[3][4] = {
 /* x,y: (n,h,w,3) float32 NHWC.  q: (3,8,8) float32 tables for Y,Cb,Cr.
  * idx (optional): (n,3,h/8,w/8,8,8) int16 quantisation indices rint(X/Q).
  * xd  (optional): same shape float32 dequantised coefficients (second output of the reference model).
+ * pre (optional): (n,h,w,3) float32, the value before the clamp.  mask (optional): (n,h,w) uint8, bit c set iff
+ * 0 <= pre_c <= 1 - the CLOSED interval on which the clamp passes the gradient (the kernel's clip mask).
  * returns 0, or -1 on bad shape. */
-int djpeg_ref_forward(const float *x, float *y, const float *q, int16_t *idx, float *xd, int n, int h, int w)
+static int forward_body(const float *x, float *y, const float *q, int16_t *idx, float *xd, float *pre, uint8_t *mask,
+                        int n, int h, int w)
 {
     if (h % 8 || w % 8 || n < 0) return -1;
     const int hb = h / 8, wb = w / 8;
@@ -102,7 +105,9 @@ int djpeg_ref_forward(const float *x, float *y, const float *q, int16_t *idx, fl
                 }
                 for (int i = 0; i < 8; ++i)
                     for (int j = 0; j < 8; ++j) {
-                        float *py = y + (((size_t)im * h + by * 8 + i) * w + bx * 8 + j) * 3;
+                        const size_t p = ((size_t)im * h + by * 8 + i) * w + bx * 8 + j;
+                        float *py = y + p * 3;
+                        uint8_t m = 0;
                         for (int c = 0; c < 3; ++c) {
                             float acc = COLOR_I[c][0];
                             acc = fmaf(out[0][i][j], COLOR_I[c][1], acc);
@@ -110,10 +115,25 @@ int djpeg_ref_forward(const float *x, float *y, const float *q, int16_t *idx, fl
                             acc = fmaf(out[2][i][j], COLOR_I[c][3], acc);
                             acc = acc / 255.0f;
                             py[c] = acc < 0.0f ? 0.0f : (acc > 1.0f ? 1.0f : acc);
+                            if (pre) pre[p * 3 + c] = acc;
+                            if (acc >= 0.0f && acc <= 1.0f) m |= (uint8_t)(1u << c);
                         }
+                        if (mask) mask[p] = m;
                     }
             }
     return 0;
+}
+
+int djpeg_ref_forward(const float *x, float *y, const float *q, int16_t *idx, float *xd, int n, int h, int w)
+{
+    return forward_body(x, y, q, idx, xd, NULL, NULL, n, h, w);
+}
+
+/* The same forward pass, also returning the pre-clip value and the clip mask (tests/djpeg_cases.py). */
+int djpeg_ref_forward_ex(const float *x, float *y, const float *q, int16_t *idx, float *xd, float *pre, uint8_t *mask,
+                         int n, int h, int w)
+{
+    return forward_body(x, y, q, idx, xd, pre, mask, n, h, w);
 }
 
 /* IJG quality scaling, compression/jpeg_helpers.py:264-305 (float32 arithmetic like the numpy reference). */
