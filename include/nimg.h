@@ -865,6 +865,25 @@ int nimg_jpeg_transform_tables(const void* x, int is_u8, int n_src, int h, int w
                                int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream);
 int nimg_jpeg_tables_from_float(const float* t, int n_sets, int n_tabs, uint16_t* qtabs, uint32_t* status, void* stream);
 
+/* The real codec as the forward of a training step (purely added, NIMG_ABI_VERSION stays): x (n,h,w,3) float32
+ * and ONE table set qtabs (device) [3][64] uint16, natural order (Y, Cb, Cr) ->
+ *   y     (n,h,w,3) float32 = float32(byte) / 255 of the image libjpeg decodes from the file it would write for x: bit-identical to
+ *         nimg_jpeg_transform_tables + nimg_jpeg_reconstruct_tables for every x with all values in [0, 1].  The input conversion is
+ *         255 * v in float32, truncated, clamped to 0..255 per value: there is NO batch-wide "any value above 1" flag, a value above 1
+ *         is 255 (the transform would divide the whole batch by 255 instead).
+ *   mask  (n,h,w) uint8 or NULL (not written), the layout nimg_djpeg_fwd writes and nimg_djpeg_bwd / nimg_djpeg_sub_bwd read: bit c is
+ *         set iff output channel c (R, G, B after libjpeg's YCC -> RGB) lies in 0..255 before its range limit.  The range limit that
+ *         ends the inverse DCT is not part of the mask.
+ *   err   (device int, zeroed by the caller) |= 1 when a table entry outside 1..255 was clamped, as in nimg_jpeg_transform_tables.
+ * (hs, vs) = (1,1), (2,1) or (2,2); whole MCUs only: h % (8 vs) == 0 and w % (8 hs) == 0.  One launch at 4:4:4; a chroma and a luma
+ * launch otherwise, with the reconstructed reduced planes in the caller's workspace (nimg_jpeg_ste_workspace_bytes: 2 n h w / (hs vs)
+ * bytes; 0 at 4:4:4 and for an empty or refused shape).  No allocation, no synchronisation, no atomics, nothing read back: capturable.
+ * n == 0 is a no-op.  NIMG_ERR_ARG before any launch: a null x / qtabs / y / err, other factors, a ragged shape, sizes outside the
+ * limits of nimg_jpeg_transform.  NIMG_ERR_WORKSPACE before any launch: a short workspace. */
+size_t nimg_jpeg_ste_workspace_bytes(int n, int h, int w, int hs, int vs);
+int nimg_jpeg_ste_fwd(const float* x, const uint16_t* qtabs, int n, int h, int w, int hs, int vs, float* y, uint8_t* mask, int* err,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* Writing files with restart intervals (libjpeg's restart_interval, Pillow's restart_marker_blocks): the
  * writing entry points above with `restart_interval` = Ri MCUs in scan order, 0..65535 (anything else is NIMG_ERR_ARG).  Behind every
  * Ri MCUs that another MCU follows the coder fills the current byte up with 1-bits, writes the marker FF D0 .. FF D7 (the k-th is

@@ -208,6 +208,8 @@ PROTOTYPES = {
     'nimg_jpeg_encode_tables': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, P, c_size_t, P]),
     'nimg_jpeg_transform_tables': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
     'nimg_jpeg_tables_from_float': (c_int, [P, c_int, c_int, P, P, P]),
+    'nimg_jpeg_ste_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'nimg_jpeg_ste_fwd': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     'nimg_jpeg_encode_restart_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'nimg_jpeg_encode_restart': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, c_size_t, P]),
     'nimg_jpeg_histogram_restart': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),

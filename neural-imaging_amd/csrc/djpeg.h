@@ -129,8 +129,9 @@ __device__ __forceinline__ void write_row24(float* lds, int b, int r, const floa
 
 // 8x8 transposes among the 8 lanes of a block through LDS tiles [ch][block][8][9], NC channels at once
 // "rows -> cols": lane (b,r) holds v[c][k] = M_c[r][k]; afterwards lane (b,r) holds M_c[k][r]  (its column r)
-template <int NC>
-__device__ __forceinline__ void transpose_tiles(float* tile, int b, int r, float (&v)[NC][8]) {
+// T: float, or int for the integer codec's kernels (jpeg_ste.hip)
+template <int NC, typename T>
+__device__ __forceinline__ void transpose_tiles(T* tile, int b, int r, T (&v)[NC][8]) {
 #pragma unroll
     for (int c = 0; c < NC; ++c)
 #pragma unroll

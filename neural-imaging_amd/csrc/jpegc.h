@@ -159,6 +159,17 @@ __device__ __forceinline__ void load_rgb(const void* img, int w, int y, int x, b
     }
 }
 
+// libjpeg's fixed-point RGB -> YCbCr (jccolor.c), one sample: the luma, and Cb (comp = 1) or Cr (comp = 2)
+__device__ __forceinline__ int luma_of(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+__device__ __forceinline__ int chroma_of(int comp, int r, int g, int b) {
+    return comp == 1 ? (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+                     : (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+// libjpeg's h2v1 / h2v2 down-sampling (jcsample.c): the sum of the 2 x vs chroma samples under reduced column x -> their mean, with
+// the bias that alternates 0, 1 (h2v1) or 1, 2 (h2v2) from column to column
+__device__ __forceinline__ int downsample_of(int sum, int vs, int x) { return vs == 2 ? (sum + 1 + (x & 1)) >> 2 : (sum + (x & 1)) >> 1; }
+
 // sample (y, x) of component `comp` as the forward DCT sees it: the right edge replicated at full resolution, the bottom row up
 // to a multiple of the vertical factor, chroma down-sampled, then the component's last row replicated downwards
 template <bool U8>
@@ -166,18 +177,17 @@ __device__ __forceinline__ int sample(const void* img, const JpegGeo& g, int com
     int r, gg, b;
     if (comp == 0) {
         load_rgb<U8>(img, g.w, min(y, g.h - 1), min(x, g.w - 1), div, r, gg, b);
-        return (19595 * r + 38470 * gg + 7471 * b + 32768) >> 16;
+        return luma_of(r, gg, b);
     }
     const int cy = min(y, g.ceh - 1);
     int sum = 0;
     for (int dy = 0; dy < g.vs; ++dy)
         for (int dx = 0; dx < g.hs; ++dx) {
             load_rgb<U8>(img, g.w, min(cy * g.vs + dy, g.h - 1), min(x * g.hs + dx, g.w - 1), div, r, gg, b);
-            sum += comp == 1 ? (-11059 * r - 21709 * gg + 32768 * b + (128 << 16) + 32767) >> 16
-                             : (32768 * r - 27439 * gg - 5329 * b + (128 << 16) + 32767) >> 16;
+            sum += chroma_of(comp, r, gg, b);
         }
     if (g.hs == 1) return sum;
-    return g.vs == 2 ? (sum + 1 + (x & 1)) >> 2 : (sum + (x & 1)) >> 1;
+    return downsample_of(sum, g.vs, x);
 }
 
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
@@ -229,6 +239,13 @@ __device__ __forceinline__ void idct8(int* d, int n) {
     d[3 * S] = descale(t13 + a0, n); d[4 * S] = descale(t13 - a0, n);
 }
 
+// jcdctmgr.c's quantisation of one forward-DCT output (scaled up by 8) by the table entry `divisor`: round half away from zero
+__device__ __forceinline__ int quantise_coef(int v, int divisor) {
+    const int qv = divisor << 3;
+    const int m = (int)(((unsigned)abs(v) + (unsigned)(qv >> 1)) / (unsigned)qv);
+    return v < 0 ? -m : m;
+}
+
 // real block t of the batch -> image, component, block row / column
 __device__ __forceinline__ void locate(const JpegGeo& g, long t, int& img, int& comp, int& br, int& bc) {
     img = (int)(t / g.NB);
@@ -269,9 +286,7 @@ __global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restr
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
         const int nat = c_nat_of_zz[k];
-        const int v = d[nat], qv = tabs.divisor(q, nat) << 3;
-        const int m = (int)(((unsigned)abs(v) + (unsigned)(qv >> 1)) / (unsigned)qv);
-        const uint32_t c16 = (uint32_t)(v < 0 ? -m : m) & 0xffffu;
+        const uint32_t c16 = (uint32_t)quantise_coef(d[nat], tabs.divisor(q, nat)) & 0xffffu;
         if (k & 1) o[k >> 1] |= c16 << 16;
         else o[k >> 1] = c16;
     }
@@ -281,9 +296,23 @@ __global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restr
 }
 
 // ---- reconstruct --------------------------------------------------------------------------------------------------------
+// libjpeg's fixed-point YCbCr -> RGB (jdcolor.c) of one pixel, cb and cr with their 128 taken off, BEFORE the range limit
+__device__ __forceinline__ int red_of(int yy, int cr) { return yy + ((91881 * cr + 32768) >> 16); }
+__device__ __forceinline__ int green_of(int yy, int cb, int cr) { return yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16); }
+__device__ __forceinline__ int blue_of(int yy, int cb) { return yy + ((116130 * cb + 32768) >> 16); }
+// the range limit of a sample: what the inverse DCT and the colour conversion both end with
+__device__ __forceinline__ int limit_byte(int v) { return min(max(v, 0), 255); }
+
 __device__ __forceinline__ uint8_t* plane_of(uint8_t* planes, const JpegGeo& g, int img, int comp) {
     return planes + (size_t)img * g.NB * 64 + (comp ? (size_t)g.nbY * 64 + (size_t)(comp - 1) * g.nbC * 64 : 0);
 }
+
+// The arithmetic of libjpeg's "fancy" up-sampling (jdsample.c) at full-resolution column x, from the sample under the pixel (`near`)
+// and its neighbour on the pixel's side (`nb`).  h2v1: (3 near + nb + 1) >> 2 at even x, + 2 at odd x.  h2v2: the column sums
+// 3 near + far of both rows first, then (3 si + sn + 8) >> 4 at even x, + 7 at odd x.
+__device__ __forceinline__ int fancy_h2v1(int near, int nb, int x) { return (3 * near + nb + 1 + (x & 1)) >> 2; }
+__device__ __forceinline__ int fancy_column(int near, int far) { return 3 * near + far; }
+__device__ __forceinline__ int fancy_h2v2(int si, int sn, int x) { return (3 * si + sn + 8 - (x & 1)) >> 4; }
 
 // chroma sample at full-resolution (y, x): libjpeg's "fancy" triangle filter over the component's real extent; with at most two
 // chroma columns libjpeg replicates instead
@@ -294,10 +323,10 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const Jp
     if (g.cew <= 2) return p[(size_t)j * stride + i];
     const int nb = (x & 1) ? min(i + 1, g.cew - 1) : max(i - 1, 0);
     const uint8_t* near = p + (size_t)j * stride;
-    if (g.vs == 1) return (3 * near[i] + near[nb] + 1 + (x & 1)) >> 2;
+    if (g.vs == 1) return fancy_h2v1(near[i], near[nb], x);
     const uint8_t* far = p + (size_t)((y & 1) ? min(j + 1, g.ceh - 1) : max(j - 1, 0)) * stride;
-    const int si = 3 * near[i] + far[i], sn = 3 * near[nb] + far[nb];
-    return (3 * si + sn + 8 - (x & 1)) >> 4;
+    const int si = fancy_column(near[i], far[i]), sn = fancy_column(near[nb], far[nb]);
+    return fancy_h2v2(si, sn, x);
 }
 
 // one thread per real block: dequantise, inverse DCT (columns, then rows), + 128, clamp -> the component's sample plane
@@ -332,8 +361,8 @@ __global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t* __restric
         uint32_t lo = 0, hi = 0;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            lo |= (uint32_t)min(max(d[8 * r + c] + 128, 0), 255) << (8 * c);
-            hi |= (uint32_t)min(max(d[8 * r + 4 + c] + 128, 0), 255) << (8 * c);
+            lo |= (uint32_t)limit_byte(d[8 * r + c] + 128) << (8 * c);
+            hi |= (uint32_t)limit_byte(d[8 * r + 4 + c] + 128) << (8 * c);
         }
         *reinterpret_cast<uint2*>(p + (size_t)r * stride) = make_uint2(lo, hi);
     }

@@ -215,9 +215,9 @@ __global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ 
     const int yy = plane_of(planes, g, img, 0)[(size_t)y * 8 * g.bwY + x];
     const int cb = chroma_at(plane_of(planes, g, img, 1), g, y, x) - 128;
     const int cr = chroma_at(plane_of(planes, g, img, 2), g, y, x) - 128;
-    const int R = min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
-    const int G = min(max(yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16), 0), 255);
-    const int B = min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
+    const int R = min(max(red_of(yy, cr), 0), 255);
+    const int G = min(max(green_of(yy, cb, cr), 0), 255);
+    const int B = min(max(blue_of(yy, cb), 0), 255);
     if (U8) {
         uint8_t* o = (uint8_t*)out + t * 3;
         o[0] = (uint8_t)R; o[1] = (uint8_t)G; o[2] = (uint8_t)B;

@@ -16,6 +16,11 @@ libjpeg's triangle up-sampling; csrc/djpeg_sub.hip, DESIGN.md section 4j).  '4:4
 New: entropy_weight=w - the rate term the reference left commented out (:245-249, "takes too much memory"): the soft entropy of the
 quantised DCT coefficients (csrc/djpeg_entropy.hip), reported by process(return_entropy=True) and added to the
 gradients by backward(entropy_coef=).  None (the default) is the reference's model: the entropy is NaN and nothing else changes.
+New: codec='libjpeg+identity' / 'libjpeg+sin' / 'libjpeg+harmonic' - a straight-through estimator of the real codec (csrc/jpeg_ste.hip,
+DESIGN.md section 4o): the forward pass IS the real codec (the image libjpeg decodes from the file it would write, bit for bit, plus
+the clip mask), the backward pass the differentiable codec's adjoint at the same input with the rounding surrogate named after '+'
+('soft' has 'sin's backward and gets no name).  Fixed quality: libjpeg's own integer tables in both directions.  trainable=True: the
+float weights of the differentiable model; the forward runs at their file_tables() rounding, the backward at the weights themselves.
 """
 import numpy as np
 import torch
@@ -27,6 +32,9 @@ from ..compression.jpeg_helpers import compress_batch, device_codec, encode_batc
 from .tfmodel import ParamStore, TFModel
 
 _common_codec = None
+
+# codec name -> rounding surrogate of the backward pass: the real codec forward, that surrogate's adjoint backward
+STE_CODECS = {'libjpeg+identity': 'identity', 'libjpeg+sin': 'sin', 'libjpeg+harmonic': 'harmonic'}
 
 
 def is_valid_quality(quality):
@@ -96,8 +104,16 @@ class JPEG(TFModel):
 
     def __init__(self, quality=None, codec='soft', trainable=False, device=None, subsampling='4:4:4', entropy_weight=None):
         super().__init__(device=device)
-        if codec is not None and codec not in ['libjpeg', 'soft', 'sin', 'harmonic']:
+        if codec is not None and codec not in ['libjpeg', 'soft', 'sin', 'harmonic'] and codec not in STE_CODECS:
             raise ValueError('Unsupported codec version: {}'.format(codec))
+        self._ste = STE_CODECS.get(codec)        # the backward surrogate of a real-codec forward, None for every other codec
+        if self._ste is not None:
+            if entropy_weight is not None:
+                raise ValueError('entropy_weight: the rate of a real codec is its bytes, which process_files reports - codec "{}" has '
+                                 'no soft rate term'.format(codec))
+            if trainable and self._ste == 'identity':
+                raise ValueError('codec "libjpeg+identity" with trainable=True: the table gradient of the identity surrogate is '
+                                 'identically zero - train the tables through "libjpeg+sin" or "libjpeg+harmonic"')
         if entropy_weight is not None:
             if isinstance(entropy_weight, bool) or not is_number(entropy_weight) or not entropy_weight >= 0:
                 raise ValueError('entropy_weight: None or a number >= 0 expected, got {!r}'.format(entropy_weight))
@@ -110,8 +126,12 @@ class JPEG(TFModel):
         self._entropy_ws = {}                    # (shape, device) -> workspace: allocated once, re-used by every step
         self.subsampling = subsampling
         self._factors = ops.jpeg_subsampling(subsampling)         # ValueError for anything but 4:4:4, 4:2:2, 4:2:0
-        self._codec_model = None if codec == 'libjpeg' else DifferentiableJPEG(quality, codec, trainable=trainable,
+        # (the codec model of a straight-through codec only holds the trainable weights, initialised as the differentiable model's)
+        approx = codec if self._ste is None else (None if self._ste == 'identity' else self._ste)
+        self._codec_model = None if codec == 'libjpeg' else DifferentiableJPEG(quality, approx, trainable=trainable,
                                                                                device=self.device, subsampling=subsampling)
+        self._rounding = codec if self._ste is None else self._ste          # what the kernels are told
+        self._ste_cache = {}                     # (quality, device) -> (uint16 tables of the forward, float32 tables of the backward)
         # no trainable parameters unless trainable=True: then the two quantisation tables (models/jpeg.py:57-62)
         self._model = self._codec_model.params if (trainable and self._codec_model is not None) else ParamStore([], self.device)
         self.trainable = bool(trainable)
@@ -159,6 +179,8 @@ class JPEG(TFModel):
         # this call (models/jpeg.py:210-243)
         resolved = self.resolve_quality(self.quality if quality is None else quality)
         learned = bool(self.trainable) and is_number(self.quality) and resolved == self.quality
+        if self._ste is not None:
+            return self._forward_ste(x, resolved, learned, training, out)
         if learned:
             q = self._codec_model.trainable_tables()
         else:
@@ -173,6 +195,29 @@ class JPEG(TFModel):
         if self.entropy_weight is not None:
             ctx['entropy'], ctx['entropy_ws'] = self._entropy(x, q)
         return y, ctx
+
+    def _ste_tables(self, quality, device):
+        """libjpeg's own integer tables of a quality on the device, for both directions of a straight-through codec: ((1,3,64) int16
+        holding the uint16 entries for the forward, (3,8,8) float32 for the backward)."""
+        key = (int(quality), str(device))
+        if key not in self._ste_cache:
+            t = np.stack([libjpeg_qtable(quality, c).ravel() for c in (0, 1, 1)])
+            self._ste_cache[key] = (torch.from_numpy(t.astype(np.int16).reshape(1, 3, 64)).to(device),
+                                    torch.from_numpy(t.astype(np.float32).reshape(3, 8, 8)).to(device))
+        return self._ste_cache[key]
+
+    def _forward_ste(self, x, resolved, learned, training, out):
+        """The real codec forward (ops.jpeg_ste_fwd).  Learned tables: the file_tables() rule on the device (ops.jpeg_tables_from_float),
+        no status read in the step; the backward differentiates at the float weights."""
+        if learned:
+            q = self._codec_model.trainable_tables()
+            qtabs, _ = ops.jpeg_tables_from_float(q.view(1, 3, 64))
+        else:
+            qtabs, q = self._ste_tables(resolved, x.device)
+        y, mask, _ = ops.jpeg_ste_fwd(x, qtabs, *self._factors, want_mask=training, out=out)
+        if not training:
+            return y, None
+        return y, {'x': x, 'mask': mask, 'q': q, 'learned': learned}
 
     def _entropy(self, x, q):
         """(entropy (1,) on the device, workspace) of the batch x at the tables q.  The workspace belongs to the model and serves
@@ -200,12 +245,12 @@ class JPEG(TFModel):
             raise NotImplementedError('the libjpeg codec has no gradient')
         if self._factors != (1, 1):
             if ctx.get('learned'):
-                return ops.djpeg_sub_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec, *self._factors,
+                return ops.djpeg_sub_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self._rounding, *self._factors,
                                          dq=self._model.flat_grad, accumulate=accumulate)
-            return ops.djpeg_sub_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec, *self._factors)
+            return ops.djpeg_sub_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self._rounding, *self._factors)
         if ctx.get('learned'):
-            return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec, dq=self._model.flat_grad, accumulate=accumulate)
-        return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self.codec)
+            return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self._rounding, dq=self._model.flat_grad, accumulate=accumulate)
+        return ops.djpeg_bwd(ctx['x'], dy, ctx['mask'], ctx['q'], self._rounding)
 
     def process(self, batch_x, quality=None, return_entropy=False):
         """Compress a batch (NHW3 rgb): number -> that quality; 2 numbers -> random integer in [lo, hi);
@@ -229,6 +274,11 @@ class JPEG(TFModel):
         if self._codec_model is None:
             if not is_number(self.quality):
                 raise ValueError('file_tables needs a numeric quality with codec="libjpeg", got {}'.format(self.quality))
+            q = self.resolve_quality(self.quality)
+            return np.stack([libjpeg_qtable(q, c).ravel() for c in (0, 1)]).astype(np.uint16), np.zeros((2, 64), bool)
+        if self._ste is not None and not self.trainable:           # a straight-through codec divides by libjpeg's own tables
+            if not is_number(self.quality):
+                raise ValueError('file_tables needs a numeric quality with codec="{}", got {}'.format(self.codec, self.quality))
             q = self.resolve_quality(self.quality)
             return np.stack([libjpeg_qtable(q, c).ravel() for c in (0, 1)]).astype(np.uint16), np.zeros((2, 64), bool)
         if self.trainable:

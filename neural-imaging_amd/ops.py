@@ -2856,3 +2856,50 @@ def jpeg_tables_from_float(t):
     status = torch.empty(t.shape[0], dtype=torch.int32, device=t.device)
     _lib.call('nimg_jpeg_tables_from_float', _p(t), t.shape[0], t.shape[1], _p(qtabs), _p(status), _stream())
     return qtabs, status
+
+
+# the real codec as a training forward
+def jpeg_ste_shape(x, hs, vs):
+    """(n, h, w) of an NHW3 batch of whole MCUs at the sampling factors (1,1), (2,1) or (2,2); a ValueError otherwise.  Needs no device."""
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError('jpeg_ste_fwd expects NHW3 images, got {}'.format(tuple(x.shape)))
+    if (hs, vs) not in JPEG_SUBSAMPLING.values():
+        raise ValueError('jpeg_ste_fwd: sampling factors (1,1), (2,1) or (2,2) expected, got ({},{})'.format(hs, vs))
+    n, h, w, _ = x.shape
+    if h <= 0 or w <= 0 or h % (8 * vs) or w % (8 * hs):
+        raise ValueError('jpeg_ste_fwd needs whole MCUs: h % {} == 0 and w % {} == 0, got {} x {}'.format(8 * vs, 8 * hs, h, w))
+    if n > 65535 or h > 4096 or w > 4096:
+        raise ValueError('jpeg_ste_fwd: at most 65535 images of at most 4096 x 4096, got {} of {} x {}'.format(n, h, w))
+    return n, h, w
+
+
+def jpeg_ste_workspace_bytes(n, h, w, hs, vs):
+    """Bytes of workspace jpeg_ste_fwd needs: the reduced chroma planes, 0 at 4:4:4 and for a batch the library does not serve."""
+    return int(_lib.load().nimg_jpeg_ste_workspace_bytes(n, h, w, hs, vs))
+
+
+def jpeg_ste_fwd(x, qtabs, hs=1, vs=1, want_mask=True, out=None, workspace=None, err=None):
+    """The real codec as the forward of a training step (include/nimg.h nimg_jpeg_ste_fwd): x (n,h,w,3) float32 and ONE table set
+    qtabs (3, 64) or (1, 3, 64) uint16 (or int16 bit patterns), natural order -> (y float32 = byte / 255 of the image libjpeg decodes
+    from the file it would write, mask (n,h,w) uint8 as djpeg_bwd / djpeg_sub_bwd read it or None, err (1,) int32: non-zero = a table
+    entry outside 1..255 was clamped).  Equal to jpeg_transform_tables + jpeg_reconstruct_tables on input in [0, 1]; a value above 1 is
+    255 here, with no batch-wide rescaling.  workspace None: the launch stream's scratch buffer."""
+    n, h, w = jpeg_ste_shape(x, hs, vs)
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (n, h, w, 3)):
+        raise ValueError('jpeg_ste_fwd: output {} {}, float32 {} needed'.format(out.dtype, tuple(out.shape), (n, h, w, 3)))
+    _f32(x, out)
+    if qtabs.dim() == 2:
+        qtabs = qtabs.unsqueeze(0)
+    qtabs = _jpeg_qtabs(qtabs, 'jpeg_ste_fwd')
+    if qtabs.shape[0] != 1:
+        raise RuntimeError('jpeg_ste_fwd: one table set (3, 64) for the batch needed, got {}'.format(tuple(qtabs.shape)))
+    _chk(workspace, err)
+    y = torch.empty_like(x) if out is None else out
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if want_mask else None
+    err = torch.zeros((1,), dtype=torch.int32, device=x.device) if err is None else err
+    need = jpeg_ste_workspace_bytes(n, h, w, hs, vs) if n else 0
+    if workspace is None:
+        workspace = _ws_current(x.device).get(need, x.device)
+    have = workspace.numel() * workspace.element_size()
+    _lib.call('nimg_jpeg_ste_fwd', _p(x), _p(qtabs), n, h, w, hs, vs, _p(y), _p(mask), _p(err), _p(workspace), have, _stream())
+    return y, mask, err

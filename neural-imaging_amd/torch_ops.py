@@ -7,6 +7,8 @@ with autograd formulas:
 
     import neural_imaging_amd.torch_ops                     # registers the ops
     y = torch.ops.nimg.djpeg(x, qtab, 'soft')               # models/jpeg.py:91-159, DIFFERENTIABLE (nimg_djpeg_fwd / _bwd)
+    y = torch.ops.nimg.jpeg_ste(x, qtab, 'identity', 2, 2)  # the REAL codec forward (libjpeg's image, bit for bit), the dJPEG adjoint
+                                                            #   backward: a straight-through estimator (nimg_jpeg_ste_fwd)
     y = torch.ops.nimg.djpeg_sub(x, qtab, 'soft', 2, 2)     # the same with chroma sub-sampling, (hs, vs) = (2,1) 4:2:2 | (2,2) 4:2:0,
                                                             #   DIFFERENTIABLE (nimg_djpeg_sub_fwd / _bwd)
     H = torch.ops.nimg.djpeg_entropy(x, qtab, 'sin')        # soft entropy of the quantised DCT coefficients, DIFFERENTIABLE in x
@@ -49,6 +51,8 @@ def _define():
     lib.define('djpeg_sub(Tensor x, Tensor qtab, str rounding, int hs, int vs) -> Tensor')
     lib.define('djpeg_sub_fwd(Tensor x, Tensor qtab, str rounding, int hs, int vs) -> (Tensor, Tensor)')
     lib.define('djpeg_sub_bwd(Tensor x, Tensor gy, Tensor mask, Tensor qtab, str rounding, int hs, int vs) -> Tensor')
+    lib.define('jpeg_ste(Tensor x, Tensor qtab, str rounding, int hs, int vs) -> Tensor')
+    lib.define('jpeg_ste_fwd(Tensor x, Tensor qtab, int hs, int vs) -> (Tensor, Tensor)')
     lib.define('djpeg_entropy(Tensor x, Tensor qtab, str rounding) -> Tensor')
     lib.define('djpeg_entropy_fwd(Tensor x, Tensor qtab, str rounding) -> (Tensor, Tensor)')
     lib.define('djpeg_entropy_bwd(Tensor x, Tensor qtab, Tensor ws, str rounding) -> Tensor')
@@ -115,6 +119,35 @@ class _DJpegSub(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, mask, qtab = ctx.saved_tensors
+        return torch.ops.nimg.djpeg_sub_bwd(x, gy, mask, qtab, ctx.rounding, *ctx.factors), None, None, None, None
+
+
+def _jpeg_ste_fwd(x, qtab, hs, vs):
+    """The real codec at ops.jpeg_tables_from_float(qtab): (the image libjpeg decodes, the clip mask of the dJPEG backward)."""
+    _cuda_only(x, qtab)
+    qtabs, _ = ops.jpeg_tables_from_float(qtab.contiguous().reshape(1, 3, 64))
+    y, mask, _ = ops.jpeg_ste_fwd(x.contiguous(), qtabs, hs, vs, want_mask=True)
+    return y, mask
+
+
+class _JpegSte(torch.autograd.Function):
+    """Straight-through estimator of the real codec: libjpeg's image forward, the differentiable codec's adjoint at the
+    same x, the float tables and the forward's mask backward; gradient to x, none to qtab - as djpeg."""
+
+    @staticmethod
+    def forward(ctx, x, qtab, rounding, hs, vs):
+        if rounding not in ops.ROUNDING:
+            raise ValueError('Unsupported rounding approximation: {}'.format(rounding))
+        y, mask = torch.ops.nimg.jpeg_ste_fwd(x, qtab, hs, vs)
+        ctx.save_for_backward(x, mask, qtab)
+        ctx.rounding, ctx.factors = rounding, (hs, vs)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mask, qtab = ctx.saved_tensors
+        if ctx.factors == (1, 1):
+            return torch.ops.nimg.djpeg_bwd(x, gy, mask, qtab, ctx.rounding), None, None, None, None
         return torch.ops.nimg.djpeg_sub_bwd(x, gy, mask, qtab, ctx.rounding, *ctx.factors), None, None, None, None
 
 
@@ -207,6 +240,7 @@ def _register():
     impl.impl('djpeg_bwd', _djpeg_bwd)
     impl.impl('djpeg_sub_fwd', _djpeg_sub_fwd)
     impl.impl('djpeg_sub_bwd', _djpeg_sub_bwd)
+    impl.impl('jpeg_ste_fwd', _jpeg_ste_fwd)
     impl.impl('djpeg_entropy_fwd', _djpeg_entropy_fwd)
     impl.impl('djpeg_entropy_bwd', _djpeg_entropy_bwd)
     impl.impl('conv2d', _conv2d)
@@ -222,6 +256,8 @@ def _register():
     impl.impl('djpeg', lambda x, qtab, rounding: _djpeg_fwd(x, qtab, rounding)[0])
     auto.impl('djpeg_sub', lambda x, qtab, rounding, hs, vs: _DJpegSub.apply(x, qtab, rounding, hs, vs))
     impl.impl('djpeg_sub', lambda x, qtab, rounding, hs, vs: _djpeg_sub_fwd(x, qtab, rounding, hs, vs)[0])
+    auto.impl('jpeg_ste', lambda x, qtab, rounding, hs, vs: _JpegSte.apply(x, qtab, rounding, hs, vs))
+    impl.impl('jpeg_ste', lambda x, qtab, rounding, hs, vs: _jpeg_ste_fwd(x, qtab, hs, vs)[0])
     auto.impl('djpeg_entropy', lambda x, qtab, rounding: _DJpegEntropy.apply(x, qtab, rounding))
     impl.impl('djpeg_entropy', lambda x, qtab, rounding: _djpeg_entropy_fwd(x, qtab, rounding)[0])
     auto.impl('conv2d', lambda x, w, bias, stride, act: _Conv2D.apply(x, w, bias, stride, act))
@@ -466,3 +502,10 @@ def djpeg_sub(x, qtab, rounding='soft', subsampling='4:2:0'):
     if (hs, vs) == (1, 1):
         return torch.ops.nimg.djpeg(x, qtab, rounding)
     return torch.ops.nimg.djpeg_sub(x, qtab, rounding, hs, vs)
+
+
+def jpeg_ste(x, qtab, rounding='identity', subsampling='4:4:4'):
+    """The real JPEG codec with a surrogate gradient as a dispatcher op: torch.ops.nimg.jpeg_ste.  Forward: the image libjpeg decodes
+    from the file it would write for x at ops.jpeg_tables_from_float(qtab); backward: djpeg_bwd / djpeg_sub_bwd with `rounding`."""
+    hs, vs = ops.jpeg_subsampling(subsampling)
+    return torch.ops.nimg.jpeg_ste(x, qtab, rounding, hs, vs)
