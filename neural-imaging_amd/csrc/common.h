@@ -14,6 +14,8 @@ namespace nimg {
 
 constexpr int WAVE = 64;
 
+typedef __bf16 nimg_bf16x4 __attribute__((ext_vector_type(4)));      // 8-byte bf16 stores (pool.hip, adam.hip)
+
 __device__ __forceinline__ float lrelu(float v, float alpha) { return v > 0.0f ? v : alpha * v; }
 
 // Sign planes (include/nimg.h): the bit of a stored bf16 value is (value > 0) - not -0, +0, a negative or a NaN.  On the bit
@@ -528,11 +530,19 @@ __device__ __forceinline__ int ticket_words_per_tile_dev(int splits, int group) 
 static inline int ticket_words_per_tile(int splits) { const int g = ticket_group(splits); return 1 + (splits + g - 1) / g; }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// workgroups of 256 threads for a grid-stride loop over `items` elements: one element per thread up to the cap of 2048 workgroups
+// (losses.hip sizes the workspaces of its per-workgroup partial sums by this cap)
+static inline int grid_for(long items) {
+    long g = (items + 255) / 256;
+    return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
+}
+// workspace sections start on 256-byte boundaries
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace nimg
 
 // ---- functions that cross translation units without being part of the ABI: declared here once, for definer and callers ----
-// zeroed counter words bound to `stream` by nimg_bind_tickets (pointwise.hip), or null when fewer than `words` are bound
+// zeroed counter words bound to `stream` by nimg_bind_tickets (runtime.hip), or null when fewer than `words` are bound
 extern "C" unsigned* nimg_internal_tickets(hipStream_t stream, size_t words);
 // wgrad5.hip: slabs written (0 = not its shape, -1 = launch error)
 int nimg_internal_wgrad5_alltaps(const void* in, int cin, const void* g, const unsigned char* idx, int cout, float* partial,

@@ -1,5 +1,5 @@
 // ConstrainedConv2D kernel re-normalisation (models/layers.py:45-53), the one copy of its arithmetic: constrained_fwd_kernel
-// (constrained.hip) runs it on the raw kernel in global memory, adam_images_kernel (pointwise.hip) on the values it has just
+// (constrained.hip) runs it on the raw kernel in global memory, adam_images_kernel (adam.hip) on the values it has just
 // updated, in LDS.  Same sums in the same order, same divisions: the same bits.
 #pragma once
 #include "common.h"

@@ -132,7 +132,8 @@ __global__ void gather_rgb_kernel(const uint8_t* __restrict__ rgb, int H, int W,
     }
 }
 
-inline int grid_for(long count) {
+// not common.h grid_for: the gathers cap their grids at 8192 workgroups, not 2048, and keep that launch geometry
+inline int grid_for_8192(long count) {
     long g = (count + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
@@ -177,12 +178,12 @@ int nimg_patch_gather(const uint16_t* raw, const uint8_t* rgb, int n_images, int
     hipStream_t s = (hipStream_t)stream;
     if (x_out) {
         const int ps = patch / 2;
-        hipLaunchKernelGGL(gather_raw_kernel, dim3(grid_for((long)b * ps * ps)), dim3(256), 0, s, raw, h / 2, w / 2,
+        hipLaunchKernelGGL(gather_raw_kernel, dim3(grid_for_8192((long)b * ps * ps)), dim3(256), 0, s, raw, h / 2, w / 2,
                            image_idx, xy, b, ps, x_out);
         NIMG_CHECK_LAUNCH();
     }
     if (y_out) {
-        hipLaunchKernelGGL(gather_rgb_kernel, dim3(grid_for((long)b * patch * ((3 * patch) >> 1))), dim3(256), 0, s, rgb,
+        hipLaunchKernelGGL(gather_rgb_kernel, dim3(grid_for_8192((long)b * patch * ((3 * patch) >> 1))), dim3(256), 0, s, rgb,
                            h, w, image_idx, xy, b, patch, y_out);
         NIMG_CHECK_LAUNCH();
     }

@@ -273,14 +273,11 @@ void launch_bwd(int rounding, int grid, hipStream_t s, A... a) {
 
 extern "C" {
 
-int nimg_abi_version(void) { return NIMG_ABI_VERSION; }
-
 int nimg_djpeg_fwd(const float* x, float* y, const float* qtab, uint8_t* mask, int16_t* idx, float* xdq, int n,
                    int h, int w, int rounding, void* stream) {
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!x || !y || !qtab || n < 0 || h <= 0 || w <= 0 || (h % 8) || (w % 8)) return NIMG_ERR_ARG;
     if (rounding < NIMG_ROUND_ROUND || rounding > NIMG_ROUND_IDENTITY) return NIMG_ERR_ARG;
-    if (n == 0) return NIMG_OK;
     const long tasks = (long)n * (h / 8) * ((w + STRIP_PX - 1) / STRIP_PX);
     const dim3 grid(persistent_grid(tasks)), block(256);
     hipStream_t s = (hipStream_t)stream;
@@ -301,7 +298,6 @@ int nimg_djpeg_bwd(const float* x, const float* gy, const uint8_t* mask, const f
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!x || !gy || !mask || !qtab || !gx || n < 0 || h <= 0 || w <= 0 || (h % 8) || (w % 8)) return NIMG_ERR_ARG;
     if (rounding < NIMG_ROUND_ROUND || rounding > NIMG_ROUND_IDENTITY) return NIMG_ERR_ARG;
-    if (n == 0) return NIMG_OK;
     const long tasks = (long)n * (h / 8) * ((w + STRIP_PX - 1) / STRIP_PX);
     launch_bwd<false>(rounding, persistent_grid(tasks), (hipStream_t)stream, x, gy, mask, qtab, gx, (float*)nullptr, n, h, w);
     NIMG_CHECK_LAUNCH();

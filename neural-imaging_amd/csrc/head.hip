@@ -15,6 +15,9 @@
 // NF = C / 32 fragments of v_mfma_f32_32x32x16_bf16 (128 accumulator registers at C = 256), K in chunks of 64 through LDS
 // (weights: [row][64 + 8] bf16, register-staged one chunk ahead).  C in {64, 128, 256}, HW in {64, 128, 256}; anything else keeps
 // the generic kernels (ops.head_fused_ok).
+//
+// The generic kernels stand behind the fused ones in this file: GAP + Dense + softmax + sparse CE, forward and backward, any shape
+// (gap_*, dense_softmax_ce*, dense_bwd_params*: nimg_fan_head_* and nimg_fan_dense_*, models/forensics.py:80-94).
 #include "common.h"
 
 namespace {
@@ -415,6 +418,261 @@ int dispatch(const HeadParams& p, hipStream_t s) {
     return NIMG_ERR_ARG;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// FAN head.  gap[n][c] = mean_p act[n][p][c]
+__global__ __launch_bounds__(256) void gap_fwd_kernel(const float* __restrict__ act, float* __restrict__ gap, int hw,
+                                                      int c) {
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int cq = c >> 2;
+    if ((c & 3) == 0 && cq <= 256 && 256 % cq == 0) {    // float4 columns x pixel phases, fixed-order LDS finish
+        __shared__ float4 red4[256];
+        const int parts = 256 / cq, col = tid % cq, part = tid / cq;
+        const float4* src = reinterpret_cast<const float4*>(act + (long)n * hw * c) + col;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = part; q < hw; q += parts) {
+            const float4 v = src[(long)q * cq];
+            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        }
+        red4[tid] = a;
+        __syncthreads();
+        if (part == 0) {
+            for (int k = 1; k < parts; ++k) {
+                const float4 v = red4[k * cq + col];
+                a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+            }
+            const float inv = 1.0f / (float)hw;
+            reinterpret_cast<float4*>(gap + (long)n * c)[col] = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+        }
+        return;
+    }
+    for (int ch = tid; ch < c; ch += blockDim.x) {
+        float sacc = 0.f;
+        const float* p = act + (long)n * hw * c + ch;
+        for (int q = 0; q < hw; ++q) sacc += p[(long)q * c];
+        gap[(long)n * c + ch] = sacc / (float)hw;
+    }
+}
+
+// one wave per image: logits = gap W + b (lanes over the features, butterfly sums), softmax, Keras sparse CE on
+// probabilities (clip 1e-7, renormalise), per-image loss and d loss / d logits (already scaled by loss_scale = 1 / batch)
+__global__ __launch_bounds__(64) void dense_softmax_ce_kernel(const float* __restrict__ gap, const float* __restrict__ w,
+                                        const float* __restrict__ b, const int* __restrict__ labels,
+                                        float* __restrict__ probs, float* __restrict__ loss_per,
+                                        float* __restrict__ dlogits, int n, int c, int k, float loss_scale) {
+    const int im = blockIdx.x, lane = threadIdx.x;
+    if (im >= n) return;
+    float z[16], pr[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) z[j] = 0.f;
+    for (int ch = lane; ch < c; ch += 64) {
+        const float g = gap[(long)im * c + ch];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (j < k) z[j] = fmaf(g, w[ch * k + j], z[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (j < k) z[j] = wave_sum(z[j]) + b[j];
+    if (lane != 0) return;
+    float m = z[0];
+    for (int j = 1; j < k; ++j) m = fmaxf(m, z[j]);
+    float s = 0.f;
+    for (int j = 0; j < k; ++j) { pr[j] = expf(z[j] - m); s += pr[j]; }
+    for (int j = 0; j < k; ++j) { pr[j] /= s; probs[(long)im * k + j] = pr[j]; }
+    if (!labels) return;
+    // keras backend sparse_categorical_crossentropy(from_logits=False), eager path: clip, log, softmax-CE of log p
+    const float eps = 1e-7f;
+    const int lab = labels[im];
+    float pc[16], S = 0.f;
+    for (int j = 0; j < k; ++j) { pc[j] = fminf(fmaxf(pr[j], eps), 1.0f - eps); S += pc[j]; }
+    loss_per[im] = -logf(pc[lab]) + logf(S);
+    // dL/dp_j = [p_j inside clip range] * (1/S - delta_jl / pc_l);   dL/dz = p * (g - sum_j g_j p_j)
+    float g[16], dot = 0.f;
+    for (int j = 0; j < k; ++j) {
+        const bool inside = pr[j] >= eps && pr[j] <= 1.0f - eps;
+        g[j] = inside ? (1.0f / S - (j == lab ? 1.0f / pc[lab] : 0.f)) : 0.f;
+        dot += g[j] * pr[j];
+    }
+    for (int j = 0; j < k; ++j) dlogits[(long)im * k + j] = loss_scale * pr[j] * (g[j] - dot);
+}
+
+// The same head for 16 < k <= 256 classes (models/forensics.py:37 allows n_classes up to 256): the lanes of the image's wave own
+// the classes (lane j: classes j, j + 64, ...), the softmax / clip / renormalise sums are wave reductions.
+__global__ __launch_bounds__(64) void dense_softmax_ce_wide_kernel(const float* __restrict__ gap, const float* __restrict__ w,
+                                        const float* __restrict__ b, const int* __restrict__ labels,
+                                        float* __restrict__ probs, float* __restrict__ loss_per,
+                                        float* __restrict__ dlogits, int n, int c, int k, float loss_scale) {
+    const int im = blockIdx.x, lane = threadIdx.x;
+    if (im >= n) return;
+    float z[4], pr[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) z[q] = 0.f;
+    for (int ch = 0; ch < c; ++ch) {
+        const float g = gap[(long)im * c + ch];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = lane + 64 * q;
+            if (j < k) z[q] = fmaf(g, w[ch * k + j], z[q]);
+        }
+    }
+    float m = -3.0e38f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        if (j < k) { z[q] += b[j]; m = fmaxf(m, z[q]); }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        pr[q] = j < k ? expf(z[q] - m) : 0.f;
+        s += pr[q];
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        pr[q] /= s;
+        if (j < k) probs[(long)im * k + j] = pr[q];
+    }
+    if (!labels) return;
+    const float eps = 1e-7f;
+    const int lab = labels[im];
+    float pc[4], S = 0.f, pl = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        pc[q] = j < k ? fminf(fmaxf(pr[q], eps), 1.0f - eps) : 0.f;
+        S += pc[q];
+        if (j == lab) pl = pc[q];
+    }
+    S = wave_sum(S);
+    pl = wave_sum(pl);                         // exactly one lane holds the label's clipped probability
+    if (lane == 0) loss_per[im] = -logf(pl) + logf(S);
+    float g[4], dot = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        const bool inside = j < k && pr[q] >= eps && pr[q] <= 1.0f - eps;
+        g[q] = inside ? (1.0f / S - (j == lab ? 1.0f / pl : 0.f)) : 0.f;
+        dot += g[q] * pr[q];
+    }
+    dot = wave_sum(dot);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        if (j < k) dlogits[(long)im * k + j] = loss_scale * pr[q] * (g[q] - dot);
+    }
+}
+
+// ... and its parameter gradients: one wave per feature channel (block c: bias, block c + 1: the loss), lanes over the classes,
+// the images summed in order
+__global__ __launch_bounds__(64) void dense_bwd_params_wide_kernel(const float* __restrict__ gap,
+                                        const float* __restrict__ dlogits, const float* __restrict__ loss_per,
+                                        float* __restrict__ dw, float* __restrict__ db, float* __restrict__ loss, int n, int c,
+                                        int k, float loss_scale) {
+    const int ch = blockIdx.x, lane = threadIdx.x;
+    if (ch == c + 1) {
+        double sd = 0.0;
+        for (int im = lane; im < n; im += 64) sd += (double)loss_per[im];
+        sd = wave_sum_d(sd);
+        if (lane == 0) loss[0] = (float)(sd * (double)loss_scale);
+        return;
+    }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int im = 0; im < n; ++im) {
+        const float g = ch < c ? gap[(long)im * c + ch] : 1.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = lane + 64 * q;
+            if (j < k) acc[q] = fmaf(g, dlogits[(long)im * k + j], acc[q]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q;
+        if (j < k) {
+            if (ch < c) dw[ch * k + j] = acc[q];
+            else db[j] = acc[q];
+        }
+    }
+}
+
+// dW[c][j] = sum_n gap[n][c] dlogits[n][j];  db[j] = sum_n dlogits[n][j];  loss = scale * sum loss_per
+// one wave per feature channel (block c: bias gradient, block c + 1: the loss); lanes over the images
+__global__ __launch_bounds__(64) void dense_bwd_params_kernel(const float* __restrict__ gap,
+                                        const float* __restrict__ dlogits,
+                                        const float* __restrict__ loss_per, float* __restrict__ dw,
+                                        float* __restrict__ db, float* __restrict__ loss, int n, int c, int k,
+                                        float loss_scale) {
+    const int ch = blockIdx.x, lane = threadIdx.x;
+    if (ch == c + 1) {
+        double sd = 0.0;
+        for (int im = lane; im < n; im += 64) sd += (double)loss_per[im];
+        sd = wave_sum_d(sd);
+        if (lane == 0) loss[0] = (float)(sd * (double)loss_scale);
+        return;
+    }
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    for (int im = lane; im < n; im += 64) {
+        const float g = ch < c ? gap[(long)im * c + ch] : 1.0f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (j < k) acc[j] = fmaf(g, dlogits[(long)im * k + j], acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (j < k) {
+            const float t = wave_sum(acc[j]);
+            if (lane == 0) {
+                if (ch < c) dw[ch * k + j] = t;
+                else db[j] = t;
+            }
+        }
+}
+
+// d act[n][p][ch] = (sum_j dlogits[n][j] W[ch][j]) / hw * lrelu'(act).  Workgroup = one image: a thread owns 4 adjacent
+// channels, computes their k-term dot products ONCE, then streams the image's positions with 16-byte loads / stores (the
+// first version recomputed the dot product - and two 64-bit divisions - for every element: 12 % of the HBM rate).
+__global__ __launch_bounds__(256) void gap_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ w,
+                                                      const float* __restrict__ act, float* __restrict__ dact,
+                                                      int hw, int c, int k, float alpha, int parts) {
+    const int n = blockIdx.x / parts, part = blockIdx.x % parts;
+    const int c4 = c >> 2, tid = threadIdx.x;
+    const float inv = 1.0f / (float)hw;
+    if ((c & 3) == 0 && c4 <= 256 && 256 % c4 == 0) {
+        const int cg = tid % c4, prow = tid / c4, ppi = 256 / c4;             // positions per iteration
+        float g[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float a = 0.f;
+            for (int j = 0; j < k; ++j) a = fmaf(dlogits[(long)n * k + j], w[(cg * 4 + e) * k + j], a);
+            g[e] = a / (float)hw;
+        }
+        const float4* a4 = reinterpret_cast<const float4*>(act + (long)n * hw * c);
+        float4* d4 = reinterpret_cast<float4*>(dact + (long)n * hw * c);
+        for (int p0 = part * ppi + prow; p0 < hw; p0 += parts * ppi) {
+            const float4 a = a4[(long)p0 * c4 + cg];
+            d4[(long)p0 * c4 + cg] = make_float4(g[0] * (a.x > 0.f ? 1.0f : alpha), g[1] * (a.y > 0.f ? 1.0f : alpha),
+                                                 g[2] * (a.z > 0.f ? 1.0f : alpha), g[3] * (a.w > 0.f ? 1.0f : alpha));
+        }
+        return;
+    }
+    (void)inv;
+    for (int i = part * 256 + tid; i < hw * c; i += parts * 256) {           // general shapes: one element per thread
+        const int ch = i % c;
+        float g = 0.f;
+        for (int j = 0; j < k; ++j) g = fmaf(dlogits[(long)n * k + j], w[ch * k + j], g);
+        g /= (float)hw;
+        const long o = (long)n * hw * c + i;
+        dact[o] = g * (act[o] > 0.f ? 1.0f : alpha);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -476,6 +734,75 @@ int nimg_head_dact(const unsigned* mask, const float* dlogits, const float* wden
     const int parts = n >= 1024 ? 1 : (n >= 256 ? 4 : 16);
     hipLaunchKernelGGL(head_dact_kernel, dim3((unsigned)(n * parts)), dim3(256), 0, (hipStream_t)stream, mask, dlogits, wdense,
                        dact, hw, c, k, alpha, parts);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_fan_head_fwd(const float* act, const float* w, const float* b, const int* labels, float* gap, float* probs,
+                      float* loss_per, float* dlogits, int n, int hw, int c, int k, float loss_scale, void* stream) {
+    if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
+    if (!act || !w || !b || !gap || !probs || n < 0 || hw <= 0 || c <= 0 || k <= 0 || k > 256) return NIMG_ERR_ARG;
+    if (labels && (!loss_per || !dlogits)) return NIMG_ERR_ARG;
+    if (n == 0) return NIMG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(gap_fwd_kernel, dim3(n), dim3(256), 0, s, act, gap, hw, c);
+    NIMG_CHECK_LAUNCH();
+    if (k > 16)
+        hipLaunchKernelGGL(dense_softmax_ce_wide_kernel, dim3(n), dim3(64), 0, s, gap, w, b, labels, probs, loss_per, dlogits, n,
+                           c, k, loss_scale);
+    else
+    hipLaunchKernelGGL(dense_softmax_ce_kernel, dim3(n), dim3(64), 0, s, gap, w, b, labels, probs, loss_per, dlogits, n, c,
+                       k, loss_scale);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_fan_head_bwd(const float* act, const float* gap, const float* w, const float* dlogits,
+                      const float* loss_per, float* dact, float* dw, float* db, float* loss, int n, int hw, int c,
+                      int k, float loss_scale, float alpha, void* stream) {
+    if (!act || !gap || !w || !dlogits || !loss_per || !dact || !dw || !db || !loss) return NIMG_ERR_ARG;
+    if (n <= 0 || hw <= 0 || c <= 0 || k <= 0 || k > 256) return NIMG_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (k > 16)
+        hipLaunchKernelGGL(dense_bwd_params_wide_kernel, dim3(c + 2), dim3(64), 0, s, gap, dlogits, loss_per, dw, db, loss, n, c,
+                           k, loss_scale);
+    else
+    hipLaunchKernelGGL(dense_bwd_params_kernel, dim3(c + 2), dim3(64), 0, s, gap, dlogits, loss_per, dw, db, loss, n, c, k,
+                       loss_scale);
+    NIMG_CHECK_LAUNCH();
+    const int parts = n >= 1024 ? 1 : (n >= 256 ? 4 : 16);                   // workgroups per image: enough to fill 256 CUs
+    hipLaunchKernelGGL(gap_bwd_kernel, dim3((unsigned)(n * parts)), dim3(256), 0, s, dlogits, w, act, dact, hw, c, k, alpha,
+                       parts);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_fan_dense_fwd(const float* gap, const float* w, const float* b, const int* labels, float* probs, float* loss_per,
+                       float* dlogits, int n, int c, int k, float loss_scale, void* stream) {
+    if (n == 0) return NIMG_OK;
+    if (!gap || !w || !b || !probs || n < 0 || c <= 0 || k <= 0 || k > 256) return NIMG_ERR_ARG;
+    if (labels && (!loss_per || !dlogits)) return NIMG_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (k > 16)
+        hipLaunchKernelGGL(dense_softmax_ce_wide_kernel, dim3(n), dim3(64), 0, s, gap, w, b, labels, probs, loss_per, dlogits, n,
+                           c, k, loss_scale);
+    else
+        hipLaunchKernelGGL(dense_softmax_ce_kernel, dim3(n), dim3(64), 0, s, gap, w, b, labels, probs, loss_per, dlogits, n, c,
+                           k, loss_scale);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+int nimg_fan_dense_bwd(const float* gap, const float* dlogits, const float* loss_per, float* dw, float* db, float* loss, int n,
+                       int c, int k, float loss_scale, void* stream) {
+    if (!gap || !dlogits || !loss_per || !dw || !db || !loss || n <= 0 || c <= 0 || k <= 0 || k > 256) return NIMG_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (k > 16)
+        hipLaunchKernelGGL(dense_bwd_params_wide_kernel, dim3(c + 2), dim3(64), 0, s, gap, dlogits, loss_per, dw, db, loss, n, c,
+                           k, loss_scale);
+    else
+        hipLaunchKernelGGL(dense_bwd_params_kernel, dim3(c + 2), dim3(64), 0, s, gap, dlogits, loss_per, dw, db, loss, n, c, k,
+                           loss_scale);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }

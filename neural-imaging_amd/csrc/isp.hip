@@ -9,7 +9,8 @@ using namespace nimg;
 
 constexpr int RED_BLOCKS = 1024;
 
-inline int grid_for(long count) {
+// not common.h grid_for: 1024 elements per workgroup and a cap of 8192 workgroups, not 256 and 2048
+inline int grid_for_x4(long count) {
     long g = (count + 1023) / 1024;
     return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
@@ -165,7 +166,7 @@ int nimg_confusion_accumulate(const float* probs, const int* labels, int* pred, 
     if (n < 0 || k < 1) return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
     if (!probs || (!pred && !conf) || (conf && !labels)) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(confusion_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, probs, labels, pred, conf, n, k);
+    hipLaunchKernelGGL(confusion_kernel, dim3(grid_for_x4(n)), dim3(256), 0, (hipStream_t)stream, probs, labels, pred, conf, n, k);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -174,7 +175,7 @@ int nimg_mask_scale(const float* x, const uint8_t* keep, float* y, long count, f
     if (count < 0) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
     if (!x || !keep || !y) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(mask_scale_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, keep, y, count, scale);
+    hipLaunchKernelGGL(mask_scale_kernel, dim3(grid_for_x4(count)), dim3(256), 0, (hipStream_t)stream, x, keep, y, count, scale);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -185,7 +186,7 @@ int nimg_isp_residual_fwd(const float* x, const float* f, const float* alpha, fl
     if (count == 0) return NIMG_OK;
     if (!x || !y || (f && !alpha)) return NIMG_ERR_ARG;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)f) & 15) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(residual_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, f, alpha, y,
+    hipLaunchKernelGGL(residual_fwd_kernel, dim3(grid_for_x4(count)), dim3(256), 0, (hipStream_t)stream, x, f, alpha, y,
                        count, clip);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -215,7 +216,7 @@ int nimg_sigmoid_fwd(const float* x, float* y, long count, void* stream) {
     if (count < 0) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
     if (!x || !y) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(sigmoid_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
+    hipLaunchKernelGGL(sigmoid_fwd_kernel, dim3(grid_for_x4(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -224,7 +225,7 @@ int nimg_sigmoid_bwd(const float* dy, const float* y, float* dx, long count, voi
     if (count < 0) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
     if (!dy || !y || !dx) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, count);
+    hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(grid_for_x4(count)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -234,7 +235,7 @@ int nimg_activation_fwd(const float* x, float* y, long count, int kind, float al
     if (count == 0) return NIMG_OK;
     if (!x || !y || (((uintptr_t)x | (uintptr_t)y) & 15)) return NIMG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int g = grid_for((count + 3) / 4);
+    const int g = grid_for_x4((count + 3) / 4);
     switch (kind) {
         case 0: hipLaunchKernelGGL(activation_fwd_kernel<0>, dim3(g), dim3(256), 0, s, x, y, count, alpha); break;
         case 1: hipLaunchKernelGGL(activation_fwd_kernel<1>, dim3(g), dim3(256), 0, s, x, y, count, alpha); break;
@@ -251,7 +252,7 @@ int nimg_activation_bwd(const float* dy, const float* y, float* dx, long count, 
     if (count == 0) return NIMG_OK;
     if (!dy || !y || !dx || (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dx) & 15)) return NIMG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int g = grid_for((count + 3) / 4);
+    const int g = grid_for_x4((count + 3) / 4);
     switch (kind) {
         case 0: hipLaunchKernelGGL(activation_bwd_kernel<0>, dim3(g), dim3(256), 0, s, dy, y, dx, count, alpha); break;
         case 1: hipLaunchKernelGGL(activation_bwd_kernel<1>, dim3(g), dim3(256), 0, s, dy, y, dx, count, alpha); break;
@@ -267,7 +268,7 @@ int nimg_gamma_ste_fwd(const float* x, float* y, long count, float lo, float hi,
     if (count < 0 || !(lo > 0.f) || !(hi >= lo)) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
     if (!x || !y) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(gamma_ste_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, lo,
+    hipLaunchKernelGGL(gamma_ste_fwd_kernel, dim3(grid_for_x4(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, lo,
                        hi, exponent);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -278,7 +279,7 @@ int nimg_gamma_ste_bwd(const float* x, const float* dy, float* dx, long count, f
     if (count < 0 || !(lo > 0.f) || !(hi >= lo)) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
     if (!x || !dy || !dx) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(gamma_ste_bwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, count,
+    hipLaunchKernelGGL(gamma_ste_bwd_kernel, dim3(grid_for_x4(count)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, count,
                        lo, hi, exponent);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;

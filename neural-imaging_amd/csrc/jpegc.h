@@ -13,7 +13,7 @@ namespace {
 
 constexpr int SCAN_THREADS = 1024;
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+using nimg::align256;
 
 // ---- geometry and workspace ---------------------------------------------------------------------------------------------
 // The longest block with the Annex K tables: DC 9 + 11, 63 x (AC 16 + 10).  JPEGOPT_BLOCK_BITS_MAX, the bound with a caller's tables, is

@@ -74,7 +74,6 @@ __host__ __device__ __forceinline__ int lanes_for(int n_sym) {
 }
 
 inline size_t slot_stride(int n_sym) { return ((size_t)n_sym + 15) / 16 * 16; }
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 // ---- quantise -----------------------------------------------------------------------------------------------------
 // A workgroup takes 64 consecutive pixels of one image with all c features (coalesced NHWC reads) and writes them back

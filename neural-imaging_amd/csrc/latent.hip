@@ -19,7 +19,8 @@ using namespace nimg;
 
 constexpr int MAXK = 256;      // up to 8 bits per feature (models/compression.py:53); the generic kernels keep K-sized arrays per thread
 
-inline int grid_for(long items) {
+// not common.h grid_for: this family caps its grids at 1024 workgroups, not 2048, and keeps that launch geometry
+inline int grid_for_1024(long items) {
     long g = (items + 255) / 256;
     return (int)(g > 1024 ? 1024 : (g < 1 ? 1 : g));
 }
@@ -723,7 +724,7 @@ extern "C" {
 int nimg_affine(const float* x, float* y, long count, float a, float b, void* stream) {
     if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(affine_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, a, b);
+    hipLaunchKernelGGL(affine_kernel, dim3(grid_for_1024(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, a, b);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -731,7 +732,7 @@ int nimg_affine(const float* x, float* y, long count, float a, float b, void* st
 int nimg_lrelu_fwd(const float* x, float* y, long count, float alpha, void* stream) {
     if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(lrelu_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, alpha);
+    hipLaunchKernelGGL(lrelu_fwd_kernel, dim3(grid_for_1024(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, alpha);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -739,7 +740,7 @@ int nimg_lrelu_fwd(const float* x, float* y, long count, float alpha, void* stre
 int nimg_tanh_fwd(const float* x, float* y, long count, void* stream) {
     if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(tanh_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
+    hipLaunchKernelGGL(tanh_fwd_kernel, dim3(grid_for_1024(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -747,7 +748,7 @@ int nimg_tanh_fwd(const float* x, float* y, long count, void* stream) {
 int nimg_tanh_bwd(const float* dy, const float* y, float* dx, long count, void* stream) {
     if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!dy || !y || !dx || count < 0) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(tanh_bwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, count);
+    hipLaunchKernelGGL(tanh_bwd_kernel, dim3(grid_for_1024(count)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -755,7 +756,7 @@ int nimg_tanh_bwd(const float* dy, const float* y, float* dx, long count, void* 
 int nimg_clip01(const float* x, float* y, long count, void* stream) {
     if (count == 0) return NIMG_OK;        /* empty stream: nothing to do (its buffers may be null) */
     if (!x || !y || count < 0) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(clip01_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
+    hipLaunchKernelGGL(clip01_kernel, dim3(grid_for_1024(count)), dim3(256), 0, (hipStream_t)stream, x, y, count);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
@@ -765,7 +766,7 @@ int nimg_pad2d(const float* x, float* y, int n, int h, int w, int c, int pad, in
     if (!x || !y || n < 0 || h <= 0 || w <= 0 || c <= 0 || pad < 0 || pad_mode < 0 || pad_mode > 2) return NIMG_ERR_ARG;
     if ((pad_mode == 1 && (pad > h || pad > w)) || (pad_mode == 2 && (pad >= h || pad >= w))) return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
-    hipLaunchKernelGGL(pad2d_kernel, dim3(grid_for((long)n * (h + 2 * pad) * (w + 2 * pad) * c)), dim3(256), 0,
+    hipLaunchKernelGGL(pad2d_kernel, dim3(grid_for_1024((long)n * (h + 2 * pad) * (w + 2 * pad) * c)), dim3(256), 0,
                        (hipStream_t)stream, x, y, n, h, w, c, pad, pad_mode);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -776,12 +777,12 @@ int nimg_s2d2_affine_bf16(const float* x, void* y, int n, int h, int w, int c, i
     if (!x || !y || n < 0 || h < 2 || w < 2 || (h & 1) || (w & 1) || c < 1 || cp < 4 * c) return NIMG_ERR_ARG;
     if (c == 3 && cp == 16 && (long)n * h * w < (1L << 31)) {
         const int npix = n * (h >> 1) * (w >> 1);
-        hipLaunchKernelGGL(s2d2_affine3_bf16_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, x, (uint4*)y, npix,
+        hipLaunchKernelGGL(s2d2_affine3_bf16_kernel, dim3(grid_for_1024(npix)), dim3(256), 0, (hipStream_t)stream, x, (uint4*)y, npix,
                            h >> 1, w >> 1, a, b);
         NIMG_CHECK_LAUNCH();
         return NIMG_OK;
     }
-    hipLaunchKernelGGL(s2d2_affine_bf16_kernel, dim3(grid_for((long)n * (h / 2) * (w / 2) * cp)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(s2d2_affine_bf16_kernel, dim3(grid_for_1024((long)n * (h / 2) * (w / 2) * cp)), dim3(256), 0, (hipStream_t)stream,
                        x, (__bf16*)y, n, h, w, c, cp, a, b);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -789,7 +790,7 @@ int nimg_s2d2_affine_bf16(const float* x, void* y, int n, int h, int w, int c, i
 
 int nimg_s2d_conv_weights(const float* w5, float* w3, int cin, int cp, int cout, void* stream) {
     if (!w5 || !w3 || cin < 1 || cp < 4 * cin || cout < 1) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(s2d_conv_weights_kernel, dim3(grid_for(9L * cp * cout)), dim3(256), 0, (hipStream_t)stream, w5, w3, cin, cp,
+    hipLaunchKernelGGL(s2d_conv_weights_kernel, dim3(grid_for_1024(9L * cp * cout)), dim3(256), 0, (hipStream_t)stream, w5, w3, cin, cp,
                        cout);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -797,7 +798,7 @@ int nimg_s2d_conv_weights(const float* w5, float* w3, int cin, int cp, int cout,
 
 int nimg_s2d_conv_weights_bwd(const float* dw3, float* dw5, int cin, int cp, int cout, int accumulate, void* stream) {
     if (!dw3 || !dw5 || cin < 1 || cp < 4 * cin || cout < 1) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(s2d_conv_weights_bwd_kernel, dim3(grid_for(25L * cin * cout)), dim3(256), 0, (hipStream_t)stream, dw3, dw5,
+    hipLaunchKernelGGL(s2d_conv_weights_bwd_kernel, dim3(grid_for_1024(25L * cin * cout)), dim3(256), 0, (hipStream_t)stream, dw3, dw5,
                        cin, cp, cout, accumulate);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -808,12 +809,12 @@ int nimg_d2s2_scale(const float* xs, float* x, int n, int h, int w, int c, int c
     if (!xs || !x || n < 0 || h < 2 || w < 2 || (h & 1) || (w & 1) || c < 1 || cp < 4 * c) return NIMG_ERR_ARG;
     if (c == 3 && cp == 16 && (long)n * h * w < (1L << 31)) {
         const int npix = n * (h >> 1) * (w >> 1);
-        hipLaunchKernelGGL(d2s2_scale3_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, (const float4*)xs, x, npix,
+        hipLaunchKernelGGL(d2s2_scale3_kernel, dim3(grid_for_1024(npix)), dim3(256), 0, (hipStream_t)stream, (const float4*)xs, x, npix,
                            h >> 1, w >> 1, scale);
         NIMG_CHECK_LAUNCH();
         return NIMG_OK;
     }
-    hipLaunchKernelGGL(d2s2_scale_kernel, dim3(grid_for((long)n * h * w * c)), dim3(256), 0, (hipStream_t)stream, xs, x, n, h, w, c,
+    hipLaunchKernelGGL(d2s2_scale_kernel, dim3(grid_for_1024((long)n * h * w * c)), dim3(256), 0, (hipStream_t)stream, xs, x, n, h, w, c,
                        cp, scale);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -823,7 +824,7 @@ int nimg_zero_insert2(const float* in, float* out, int n, int h, int w, int c, v
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!in || !out || n < 0 || h <= 0 || w <= 0 || c <= 0) return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
-    hipLaunchKernelGGL(zero_insert2_kernel, dim3(grid_for((long)n * 4 * h * w * c)), dim3(256), 0,
+    hipLaunchKernelGGL(zero_insert2_kernel, dim3(grid_for_1024((long)n * 4 * h * w * c)), dim3(256), 0,
                        (hipStream_t)stream, in, out, n, h, w, c);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -847,7 +848,7 @@ int nimg_latent_fwd(const float* z, const float* scale, const float* codebook, i
         return NIMG_ERR_ARG;
     if (workspace_bytes < nimg_latent_workspace_bytes(codebook_size)) return NIMG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int K = codebook_size, grid = grid_for(count);
+    const int K = codebook_size, grid = grid_for_1024(count);
     double* part = (double*)workspace;
     double* hsum = part + 1024 * (size_t)K;
     double* dH = hsum + K;
@@ -912,7 +913,7 @@ int nimg_latent_bwd(const float* z, const float* scale, const float* latent, con
         return NIMG_ERR_ARG;
     if (workspace_bytes < nimg_latent_workspace_bytes(codebook_size)) return NIMG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int K = codebook_size, grid = grid_for(count);
+    const int K = codebook_size, grid = grid_for_1024(count);
     double* part = (double*)workspace;
     double* dH = part + 1024 * (size_t)K + K;
     double* dsp = dH + K;
@@ -962,7 +963,7 @@ int nimg_l2_loss(const float* target, const float* y, float* loss, float* grad_y
     if (!target || !y || !loss || !workspace || count <= 0) return NIMG_ERR_ARG;
     if (workspace_bytes < nimg_l2_loss_workspace_bytes()) return NIMG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int grid = grid_for(count);
+    const int grid = grid_for_1024(count);
     hipLaunchKernelGGL(l2_loss_kernel, dim3(grid), dim3(256), 0, s, target, y, grad_y, (double*)workspace, count,
                        grad_scale, accumulate);
     NIMG_CHECK_LAUNCH();

@@ -13,7 +13,8 @@ namespace {
 
 using namespace nimg;
 
-inline int grid_for(long items) {
+// not common.h grid_for: this family caps its grids at 4096 workgroups, not 2048, and keeps that launch geometry
+inline int grid_for_4096(long items) {
     long g = (items + 255) / 256;
     return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
 }
@@ -912,7 +913,7 @@ int nimg_gaussian_fwd(const float* x, float* y, uint8_t* mask, const float* gk25
         hipLaunchKernelGGL(gaussian_fwd_tiled_kernel, dim3((unsigned)((long)n * ty * tx)), dim3(256), 0, (hipStream_t)stream,
                            x, y, mask, gk25, n, h, w, clip, ty, tx);
     else
-        hipLaunchKernelGGL(gaussian_fwd_kernel, dim3(grid_for((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, x, y,
+        hipLaunchKernelGGL(gaussian_fwd_kernel, dim3(grid_for_4096((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, x, y,
                            mask, gk25, n, h, w, clip);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -932,7 +933,7 @@ int nimg_gaussian_bwd(const float* dy, const uint8_t* mask, float* dx, const flo
         hipLaunchKernelGGL(gaussian_bwd_tiled_kernel, dim3((unsigned)((long)n * ty * tx)), dim3(256), 0,
                            (hipStream_t)stream, dy, mask, dx, gk25, n, h, w, ty, tx);
     else
-        hipLaunchKernelGGL(gaussian_bwd_kernel, dim3(grid_for((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, dy,
+        hipLaunchKernelGGL(gaussian_bwd_kernel, dim3(grid_for_4096((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, dy,
                            mask, dx, gk25, n, h, w);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -944,7 +945,7 @@ int nimg_dwfilter_fwd(const float* x, float* y, uint8_t* mask, const float* taps
     /* a mirrored border of k/2 pixels needs k/2 (SYMMETRIC) or k/2 + 1 (REFLECT) pixels to mirror */
     if (!x || !y || !taps || n < 0 || k < 1 || k > 31 || !(k & 1) || (pad_mode != 1 && pad_mode != 2)) return NIMG_ERR_ARG;
     if (h < k / 2 + (pad_mode == 2) || w < k / 2 + (pad_mode == 2) || h < 1 || w < 1) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(dwfilter_fwd_kernel, dim3(grid_for((long)n * h * w)), dim3(256), (size_t)k * k * sizeof(float),
+    hipLaunchKernelGGL(dwfilter_fwd_kernel, dim3(grid_for_4096((long)n * h * w)), dim3(256), (size_t)k * k * sizeof(float),
                        (hipStream_t)stream, x, y, mask, taps, k, pad_mode, n, h, w, clip);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -956,7 +957,7 @@ int nimg_dwfilter_bwd(const float* dy, const uint8_t* mask, float* dx, const flo
     if (!dy || !dx || !taps || n < 0 || k < 1 || k > 31 || !(k & 1) || (pad_mode != 1 && pad_mode != 2)) return NIMG_ERR_ARG;
     /* the fold of the padded-domain gradient: each border mirrors a pixel at most once (own + up to two mirrored sources) */
     if (h < 2 * (k / 2) + 1 || w < 2 * (k / 2) + 1) return NIMG_ERR_ARG;
-    hipLaunchKernelGGL(dwfilter_bwd_kernel, dim3(grid_for((long)n * h * w)), dim3(256), (size_t)k * k * sizeof(float),
+    hipLaunchKernelGGL(dwfilter_bwd_kernel, dim3(grid_for_4096((long)n * h * w)), dim3(256), (size_t)k * k * sizeof(float),
                        (hipStream_t)stream, dy, mask, dx, taps, k, pad_mode, n, h, w);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -972,7 +973,7 @@ int nimg_sharpen_fwd(const float* x, float* y, float* aux_hsv, uint8_t* mask, co
         hipLaunchKernelGGL(sharpen_fwd_tiled_kernel, dim3((unsigned)((long)n * ty * tx)), dim3(256), 0, (hipStream_t)stream,
                            x, y, aux_hsv, mask, gk9, n, h, w, ty, tx);
     else
-        hipLaunchKernelGGL(sharpen_fwd_kernel, dim3(grid_for((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, x, y,
+        hipLaunchKernelGGL(sharpen_fwd_kernel, dim3(grid_for_4096((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, x, y,
                            aux_hsv, mask, gk9, n, h, w);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -985,14 +986,14 @@ int nimg_sharpen_bwd(const float* x, const float* dy, float* aux_hsv, const uint
     if (n == 0) return NIMG_OK;
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)n * h * w;
-    hipLaunchKernelGGL(sharpen_bwd_a_kernel, dim3(grid_for(total)), dim3(256), 0, s, dy, mask, aux_hsv, total);
+    hipLaunchKernelGGL(sharpen_bwd_a_kernel, dim3(grid_for_4096(total)), dim3(256), 0, s, dy, mask, aux_hsv, total);
     NIMG_CHECK_LAUNCH();
     const int ty = (h + 15) / 16, tx = (w + 15) / 16;
     if (h >= 16 && w >= 16 && (long)n * ty * tx < (1L << 31))
         hipLaunchKernelGGL(sharpen_bwd_b_tiled_kernel, dim3((unsigned)((long)n * ty * tx)), dim3(256), 0, s, x,
                            (const float*)aux_hsv, dx, gk9, n, h, w, ty, tx);
     else
-        hipLaunchKernelGGL(sharpen_bwd_b_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, (const float*)aux_hsv, dx,
+        hipLaunchKernelGGL(sharpen_bwd_b_kernel, dim3(grid_for_4096(total)), dim3(256), 0, s, x, (const float*)aux_hsv, dx,
                            gk9, n, h, w);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1010,16 +1011,16 @@ int nimg_sparse_axis_apply(const float* in, float* out, const int* rowptr, const
     const bool small = (long)n * hout * wout < (1L << 29) && (long)n * hin * win < (1L << 29);
     if (c == 3 && !scalar_form && small && axis == 0 && win % 4 == 0) {
         const int row4 = win * 3 / 4;
-        hipLaunchKernelGGL(sparse_axis3_rows_kernel, dim3(grid_for((long)n * hout * row4)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(sparse_axis3_rows_kernel, dim3(grid_for_4096((long)n * hout * row4)), dim3(256), 0, (hipStream_t)stream,
                            (const float4*)in, (float4*)out, rowptr, col, val, n, hin, hout, row4);
         NIMG_CHECK_LAUNCH();
         return NIMG_OK;
     }
     if (c == 3 && (long)n * hout * wout < (1L << 31) && (long)n * hin * win < (1L << 31))
-        hipLaunchKernelGGL(sparse_axis3_kernel, dim3(grid_for((long)n * hout * wout)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(sparse_axis3_kernel, dim3(grid_for_4096((long)n * hout * wout)), dim3(256), 0, (hipStream_t)stream,
                            in, out, rowptr, col, val, n, hin, win, hout, wout, axis);
     else
-        hipLaunchKernelGGL(sparse_axis_kernel, dim3(grid_for((long)n * hout * wout * c)), dim3(256), 0,
+        hipLaunchKernelGGL(sparse_axis_kernel, dim3(grid_for_4096((long)n * hout * wout * c)), dim3(256), 0,
                            (hipStream_t)stream, in, out, rowptr, col, val, n, hin, win, hout, wout, c, axis);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1031,10 +1032,10 @@ int nimg_fold_pad(const float* dpad, float* dx, int n, int h, int w, int c, int 
         return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
     if (c == 3 && (long)n * (h + 2 * pad) * (w + 2 * pad) < (1L << 31))
-        hipLaunchKernelGGL(fold_pad3_kernel, dim3(grid_for((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, dpad, dx, n,
+        hipLaunchKernelGGL(fold_pad3_kernel, dim3(grid_for_4096((long)n * h * w)), dim3(256), 0, (hipStream_t)stream, dpad, dx, n,
                            h, w, pad, pad_mode);
     else
-        hipLaunchKernelGGL(fold_pad_kernel, dim3(grid_for((long)n * h * w * c)), dim3(256), 0, (hipStream_t)stream, dpad,
+        hipLaunchKernelGGL(fold_pad_kernel, dim3(grid_for_4096((long)n * h * w * c)), dim3(256), 0, (hipStream_t)stream, dpad,
                            dx, n, h, w, c, pad, pad_mode);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1044,7 +1045,7 @@ int nimg_avgpool_fwd(const float* x, float* y, int n, int h, int w, int c, int f
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!x || !y || n < 0 || h <= 0 || w <= 0 || c <= 0 || factor < 1 || h % factor || w % factor) return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
-    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for((long)n * (h / factor) * (w / factor) * c)), dim3(256), 0,
+    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for_4096((long)n * (h / factor) * (w / factor) * c)), dim3(256), 0,
                        (hipStream_t)stream, x, y, n, h, w, c, factor);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1054,7 +1055,7 @@ int nimg_avgpool_bwd(const float* dy, float* dx, int n, int h, int w, int c, int
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!dy || !dx || n < 0 || h <= 0 || w <= 0 || c <= 0 || factor < 1 || h % factor || w % factor) return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
-    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for((long)n * h * w * c)), dim3(256), 0, (hipStream_t)stream, dy,
+    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for_4096((long)n * h * w * c)), dim3(256), 0, (hipStream_t)stream, dy,
                        dx, n, h, w, c, factor);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1169,7 +1170,7 @@ int nimg_awgn_fwd(const float* x, const float* noise, float* y, uint8_t* mask, l
                   void* stream) {
     if (!x || !noise || !y || count < 0) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
-    hipLaunchKernelGGL(awgn_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, noise, y, mask,
+    hipLaunchKernelGGL(awgn_fwd_kernel, dim3(grid_for_4096(count)), dim3(256), 0, (hipStream_t)stream, x, noise, y, mask,
                        count, strength);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1178,7 +1179,7 @@ int nimg_awgn_bwd(const float* x, const float* noise, const float* dy, const uin
                   float strength, void* stream) {
     if (!x || !noise || !dy || !mask || !dx || count < 0) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
-    hipLaunchKernelGGL(awgn_bwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, noise, dy, mask,
+    hipLaunchKernelGGL(awgn_bwd_kernel, dim3(grid_for_4096(count)), dim3(256), 0, (hipStream_t)stream, x, noise, dy, mask,
                        dx, count, strength);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1186,14 +1187,14 @@ int nimg_awgn_bwd(const float* x, const float* noise, const float* dy, const uin
 int nimg_gamma_fwd(const float* x, float* y, long count, float gamma, void* stream) {
     if (!x || !y || count < 0 || gamma <= 0.f) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
-    hipLaunchKernelGGL(gamma_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, gamma);
+    hipLaunchKernelGGL(gamma_fwd_kernel, dim3(grid_for_4096(count)), dim3(256), 0, (hipStream_t)stream, x, y, count, gamma);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 int nimg_gamma_bwd(const float* x, const float* dy, float* dx, long count, float gamma, void* stream) {
     if (!x || !dy || !dx || count < 0 || gamma <= 0.f) return NIMG_ERR_ARG;
     if (count == 0) return NIMG_OK;
-    hipLaunchKernelGGL(gamma_bwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, count,
+    hipLaunchKernelGGL(gamma_bwd_kernel, dim3(grid_for_4096(count)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, count,
                        gamma);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1203,7 +1204,7 @@ int nimg_median_fwd(const float* x, float* y, uint8_t* sel, int n, int h, int w,
     if (!x || !y || n < 0 || kernel < 1 || kernel > 9 || !(kernel & 1) || h <= kernel / 2 || w <= kernel / 2)
         return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
-    hipLaunchKernelGGL(median_fwd_kernel, dim3(grid_for((long)n * h * w * 3)), dim3(256), 0, (hipStream_t)stream, x, y,
+    hipLaunchKernelGGL(median_fwd_kernel, dim3(grid_for_4096((long)n * h * w * 3)), dim3(256), 0, (hipStream_t)stream, x, y,
                        sel, n, h, w, kernel);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -1213,7 +1214,7 @@ int nimg_median_bwd(const float* dy, const uint8_t* sel, float* dx, int n, int h
     if (n == 0) return NIMG_OK;        /* empty batch: nothing to do (its buffers may be null) */
     if (!dy || !sel || !dx || n < 0 || kernel < 1 || kernel > 9 || !(kernel & 1)) return NIMG_ERR_ARG;
     if (n == 0) return NIMG_OK;
-    hipLaunchKernelGGL(median_bwd_kernel, dim3(grid_for((long)n * h * w * 3)), dim3(256), 0, (hipStream_t)stream, dy,
+    hipLaunchKernelGGL(median_bwd_kernel, dim3(grid_for_4096((long)n * h * w * 3)), dim3(256), 0, (hipStream_t)stream, dy,
                        sel, dx, n, h, w, kernel);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;

@@ -27,7 +27,7 @@ __global__ __launch_bounds__(64) void msssim_images_kernel(const float* __restri
     out[i] = acc / c;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+using nimg::align256;
 
 inline bool size_ok(int n, int h, int w, int c) {
     const int div = 1 << (SCALES - 1);

@@ -144,7 +144,8 @@ def _f32(*ts):
 
 
 D2S_EPILOGUE = os.environ.get('NIMG_NO_D2S_OUT') is None          # A/B switch: depth_to_space as a separate pass
-BF16_IN, BF16_OUT, BF16_MASK, BF16_DZ, D2S_OUT, S2D_OUT, COPY_LRELU, MASK_CONV = 1, 2, 4, 8, 16, 32, 64, 128          # include/nimg.h NIMG_BF16_*, NIMG_D2S_OUT
+BF16_IN, BF16_OUT, BF16_MASK, BF16_DZ, D2S_OUT, S2D_OUT, COPY_LRELU, MASK_CONV = (_lib.CONSTANTS['NIMG_' + _n] for _n in (
+    'BF16_IN', 'BF16_OUT', 'BF16_MASK', 'BF16_DZ', 'D2S_OUT', 'S2D_OUT', 'COPY_LRELU', 'MASK_CONV'))        # plain ints from include/nimg.h
 
 
 def _fb(*ts):
@@ -244,10 +245,9 @@ _ws = Workspace()
 # 1.2 ms for a CU) - with two, every workload is 1 - 4 % faster and the captured two-branch graph replays as fast as eager
 # launches (profiles/r04_side_streams_2_vs_3.txt).  A gradient buffer always goes to the same stream (`key`), so accumulating
 # launches stay ordered; each stream has its own split-K scratch.  NIMG_NO_SIDE_STREAM=1 keeps everything on one stream.
-import os as _os
 
-_SIDE = {'streams': [], 'ws': [Workspace()], 'n': max(1, int(_os.environ.get('NIMG_SIDE_STREAMS', '2'))), 'next': 0, 'keys': {},
-         'enabled': _os.environ.get('NIMG_NO_SIDE_STREAM') is None, 'dirty': set()}
+_SIDE = {'streams': [], 'ws': [Workspace()], 'n': max(1, int(os.environ.get('NIMG_SIDE_STREAMS', '2'))), 'next': 0, 'keys': {},
+         'enabled': os.environ.get('NIMG_NO_SIDE_STREAM') is None, 'dirty': set()}
 _ws_side = _SIDE['ws'][0]       # split-K scratch of the kernels that run on the (first) side stream
 
 
@@ -270,7 +270,7 @@ def _side_index(key):
 # launch - where the separate reduction spreads the same 38 MB over every CU in ~10 us.  Without it every weight gradient keeps its
 # separate reduction launch; the sums differ in the order of the additions only.
 _TICKETS = {}
-TICKETS = _os.environ.get('NIMG_TICKETS') is not None
+TICKETS = os.environ.get('NIMG_TICKETS') is not None
 
 
 def _bind_tickets(device, handle):
@@ -296,7 +296,7 @@ def _ws_current(device):
 
 # NIMG_SIDE_CUS=n: the side streams run on n compute units only (nimg_stream_create_cu_mask) - partitions the chip between the
 # parameter-gradient kernels and the launch stream's kernels instead of interleaving them workgroup by workgroup.
-SIDE_CUS = int(_os.environ.get('NIMG_SIDE_CUS', '0'))
+SIDE_CUS = int(os.environ.get('NIMG_SIDE_CUS', '0'))
 
 
 def _new_side_stream(dev):
@@ -349,7 +349,7 @@ class _on_side_stream(object):
 # side-stream block entered inside waits on it.  Contract: nothing launched inside may depend on launch-stream work queued after
 # the fork - i.e. the body consists of side-stream launches only (parameter gradients deferred by their model, see
 # models/pipelines.py UNet.backward).  NIMG_NO_FORK_GROUPS=1: every block forks for itself, as before round 6.
-FORK_GROUPS = _os.environ.get('NIMG_NO_FORK_GROUPS') is None
+FORK_GROUPS = os.environ.get('NIMG_NO_FORK_GROUPS') is None
 
 
 class one_fork(object):
@@ -415,7 +415,7 @@ class side_stream(object):
 # (profiles/r05_deferred_reduce_ab.txt).  A reduction issued right behind its producer finds the ~38 MB of slabs in the 256 MB
 # Infinity Cache and overlaps with the next layers; the batched one reads ~1 GB of slabs from HBM at the tail of the side stream,
 # on the step's critical path.  The launches were never the cost - VERDICT r04 item 4 is answered by measurement, not by count.
-DEFER_REDUCE = _os.environ.get('NIMG_DEFER_REDUCE') is not None
+DEFER_REDUCE = os.environ.get('NIMG_DEFER_REDUCE') is not None
 _DEFER = {}
 
 
@@ -456,9 +456,9 @@ def _flush_deferred(k, on_its_stream=True):
 # NIMG_CHAIN_REDUCE=0|1: the slab reduction of a side=True weight gradient runs in the PROLOGUE of the next weight-gradient kernel of its
 # side stream (nimg_conv2d_wgrad_bf16_chained; the last one of a chain as a launch of its own at the join): ~25 launches fewer per
 # step on the side queues, which end later than the launch queue in the UNet's backward pass (profiles/r06_fork_markers.txt).
-CHAIN_REDUCE = _os.environ.get('NIMG_CHAIN_REDUCE', '0') == '1'
+CHAIN_REDUCE = os.environ.get('NIMG_CHAIN_REDUCE', '0') == '1'
 _CHAIN = {}                                   # side stream index -> the entry its last chained launch filled (ctypes buffer)
-REDUCE_STREAM = _os.environ.get('NIMG_REDUCE_STREAM', '0') == '1'
+REDUCE_STREAM = os.environ.get('NIMG_REDUCE_STREAM', '0') == '1'
 _RSTREAM = {'streams': {}, 'dirty': set()}
 
 
@@ -537,7 +537,7 @@ def qtables_device(quality, device):
     return torch.from_numpy(q).to(device)
 
 
-ROUNDING = {'round': 0, 'soft': 1, 'sin': 2, 'harmonic': 3, 'identity': 4}
+ROUNDING = {_n: _lib.CONSTANTS['NIMG_ROUND_' + _n.upper()] for _n in ('round', 'soft', 'sin', 'harmonic', 'identity')}
 
 
 def djpeg_fwd(x, qtab, rounding='soft', want_mask=True, want_idx=False, want_xdq=False, out=None):
@@ -826,12 +826,12 @@ def conv2d(x, w, bias=None, x2=None, stride=1, padding='SAME', act=None, pad_mod
 
 # Row-band streaming form of the 3x3 convolutions with 32 output channels over 128-pixel-wide bf16-stored images - the UNet's
 # level-1 layers at the channel's 128 x 128 RAW patches (NIMG_NO_ROWS_CONV=1: the tile kernels, A/B runs)
-ROWS_CONV = _os.environ.get('NIMG_NO_ROWS_CONV') is None
+ROWS_CONV = os.environ.get('NIMG_NO_ROWS_CONV') is None
 # ... and the 64-pixel-wide, 64-channel second level: OPT-IN (NIMG_ROWS_LEVEL2=1).  Stand-alone the streaming form wins there too
 # (32 -> 64: 27 -> 22 us, 64 -> 64: 39 -> 34 us at B = 64) but the UNet step does not move (forward 755 vs 761 us, step 2354 vs 2347 us):
 # these layers are no longer byte-bound (73 KB of weights staged per workgroup, one 143 KB workgroup per CU leaves the side
 # streams' weight gradients no room) - profiles/r05_unet_rows_ab.txt section 6
-ROWS_LEVEL2 = _os.environ.get('NIMG_ROWS_LEVEL2') is not None
+ROWS_LEVEL2 = os.environ.get('NIMG_ROWS_LEVEL2') is not None
 
 
 def rows_conv_ok(x, x2, ks, stride, cout, out_hw, pads, pad_mode, out, out2, act_mask, act, bias=None):
@@ -1066,7 +1066,7 @@ def maxpool2_bwd(dp, yact, add=None, apply_mask=True, out=None, alpha=None):
 # Sign planes of the FAN's bf16-stored pooled activations: (N, H, W, C / 8) uint8, bit e of byte c / 8 = (channel c + e > 0).  The
 # input gradient of the layer behind reads the plane instead of the activation for its LeakyReLU' mask (a sixteenth of the bytes,
 # the same bits).  NIMG_NO_ACT_SIGN=1: no plane is written or read (A/B runs).
-ACT_SIGN = _os.environ.get('NIMG_NO_ACT_SIGN') is None
+ACT_SIGN = os.environ.get('NIMG_NO_ACT_SIGN') is None
 
 
 def conv2d_pool_sign_ok(x, w, out_bf16=True):
@@ -1112,7 +1112,7 @@ def conv2d_pool(x, w, bias=None, act='leaky_relu', want_idx=True, out_bf16=False
 
 # The UNet's encoder levels write the pooled tensor from the second convolution's epilogue (NIMG_NO_POOL_ALSO=1: a separate
 # max-pool pass over the stored activation, A/B runs).
-POOL_ALSO = _os.environ.get('NIMG_NO_POOL_ALSO') is None
+POOL_ALSO = os.environ.get('NIMG_NO_POOL_ALSO') is None
 
 
 _EPI8 = {}
@@ -1158,7 +1158,7 @@ def conv2d_and_pool(x, w, bias=None, act='leaky_relu'):
 
 # ... and their backward: the input gradient of the NEXT level's first convolution written through the max-pool
 # (NIMG_NO_DGRAD_UNPOOL_OUT=1: input gradient, then maxpool2_bwd; A/B runs)
-DGRAD_UNPOOL_OUT = _os.environ.get('NIMG_NO_DGRAD_UNPOOL_OUT') is None
+DGRAD_UNPOOL_OUT = os.environ.get('NIMG_NO_DGRAD_UNPOOL_OUT') is None
 
 
 def conv2d_dgrad_unpool_out_ok(dz, w, act, skip):
@@ -1200,7 +1200,7 @@ def maxpool2_unpool(dp, idx, pooled, apply_mask=True, out=None, out_bf16=False, 
 
 # The FAN's conv2..4 backward reads the pooled gradient directly (un-pooled while staging); NIMG_NO_UNPOOL_FOLD=1 materialises
 # the full-resolution gradient first (A/B runs).
-UNPOOL_FOLD = _os.environ.get('NIMG_NO_UNPOOL_FOLD') is None
+UNPOOL_FOLD = os.environ.get('NIMG_NO_UNPOOL_FOLD') is None
 
 
 def unpool_fold_ok(x, g, cin, cout, ks):
@@ -1210,7 +1210,7 @@ def unpool_fold_ok(x, g, cin, cout, ks):
     small = max(x.numel(), g.numel()) * 2 < (1 << 31) - 65536 and 25 * cin * cout * 2 < (1 << 31) - 65536
     return UNPOOL_FOLD and COMPUTE == 'bf16' and ks == 5 and _is_bf16(x) and _is_bf16(g) and cin % 32 == 0 and \
         cout % 64 == 0 and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0 and small and \
-        _os.environ.get('NIMG_NO_BUFFER_LOADS') is None
+        os.environ.get('NIMG_NO_BUFFER_LOADS') is None
 
 
 def conv2d_dgrad_unpool(g, idx, w, act_mask=None, out_bf16=False, act_sign=None):
@@ -1403,7 +1403,7 @@ def mse255(a, b, grad_scale=None, grad_out=None, accumulate=False):
 
 # The workflow hands the UNet its output gradient as (manipulation gradients..., L2 term): one pass that sums them and writes
 # the gradient behind depth_to_space + clip (NIMG_NO_FUSED_HEAD_GRAD=1: the three separate passes, A/B runs).
-FUSED_HEAD_GRAD = _os.environ.get('NIMG_NO_FUSED_HEAD_GRAD') is None
+FUSED_HEAD_GRAD = os.environ.get('NIMG_NO_FUSED_HEAD_GRAD') is None
 
 
 def mse255_sum_s2d3(parts, y, target, grad_scale):
@@ -1459,7 +1459,7 @@ def fan_head_bwd(act, gap, w, dlogits, loss_per, loss_scale, dw, db, alpha=None)
 # ---- fused FAN head, throughput mode (csrc/head.hip): 1x1 conv + LeakyReLU + global average pooling in one pass; the backward
 # pass builds the pooled gradient's spread-out form inside the 1x1 layer's input-gradient kernel from one bit per activation.
 # NIMG_NO_HEAD_FUSED=1 keeps the generic 1x1 / pooling kernels (A/B switch).
-HEAD_FUSED = _os.environ.get('NIMG_NO_HEAD_FUSED') is None
+HEAD_FUSED = os.environ.get('NIMG_NO_HEAD_FUSED') is None
 
 
 def head_fused_ok(x, cout):
@@ -1569,10 +1569,10 @@ def adam_step(params, grads, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, g
 
 # The Adam launch also writes the bf16 weight images from the updated values, so that the forward passes need not rebuild them
 # (NIMG_NO_ADAM_IMAGES=1: plain Adam, one image launch at the head of every forward; the same bits, A/B runs)
-ADAM_IMAGES = _os.environ.get('NIMG_NO_ADAM_IMAGES') is None
+ADAM_IMAGES = os.environ.get('NIMG_NO_ADAM_IMAGES') is None
 # ... and the normalised ConstrainedConv2D filter with its flipped form (NIMG_NO_ADAM_CCONV=1: made at the head of every forward
 # pass and input gradient, by launches of their own; the same with NIMG_NO_ADAM_IMAGES=1, whose Adam launch makes neither)
-ADAM_CCONV = _os.environ.get('NIMG_NO_ADAM_CCONV') is None
+ADAM_CCONV = os.environ.get('NIMG_NO_ADAM_CCONV') is None
 
 
 def adam_step_images(params, grads, m, v, images, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, skip_flag=None,
@@ -1663,13 +1663,13 @@ def cconv3(x, w, pad_mode=1, out=None, want_f32=True, want_c4=False):
 
 # The row-band front-end kernels (csrc/frontend.hip) serve the FAN's standard first layer in throughput mode; NIMG_OLD_FRONTEND=1
 # keeps the generic small-channel kernels (A/B runs).
-FRONT_END = _os.environ.get('NIMG_OLD_FRONTEND') is None
-CCONV_DGRAD_MFMA = _os.environ.get('NIMG_NO_CCONV_DGRAD_MFMA') is None       # A/B switch
+FRONT_END = os.environ.get('NIMG_OLD_FRONTEND') is None
+CCONV_DGRAD_MFMA = os.environ.get('NIMG_NO_CCONV_DGRAD_MFMA') is None       # A/B switch
 # 5x5 stride-2 layers as 3x3 stride-1 layers over the space-to-depth image (throughput mode); NIMG_NO_S2D_CONV=1: the strided kernels
-S2D_CONV = _os.environ.get('NIMG_NO_S2D_CONV') is None
+S2D_CONV = os.environ.get('NIMG_NO_S2D_CONV') is None
 # 5x5 input gradients of the fused conv + pool layers on the sparse matrix instruction (csrc/dgrad5s.hip): correct, but at
 # parity with the ring kernels (its dense operand is twice the LDS bytes per matrix cycle) - off unless NIMG_SPARSE_DGRAD=1
-SPARSE_DGRAD = _os.environ.get('NIMG_SPARSE_DGRAD') is not None
+SPARSE_DGRAD = os.environ.get('NIMG_SPARSE_DGRAD') is not None
 
 
 def front_end_ok(cin, cout, ks, h, w, n=None):
@@ -1757,7 +1757,7 @@ def cconv3_dgrad(dy, nf, nf_flip=None):
 
 # The mirror terms of the constrained filter's input gradient from LDS-staged strips (NIMG_NO_BORDER_STRIPS=1: one thread per border
 # pixel reading L2 tap by tap; the same bits, A/B runs)
-BORDER_STRIPS = _os.environ.get('NIMG_NO_BORDER_STRIPS') is None
+BORDER_STRIPS = os.environ.get('NIMG_NO_BORDER_STRIPS') is None
 
 
 def cconv3_dgrad_border(dy, nf, dx, strips=None):

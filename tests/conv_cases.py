@@ -76,7 +76,7 @@ SWITCHES = {
     'NIMG_ROWS_BH': 'group:splits',
     'NIMG_ROWS_NCW': 'group:splits,optin_b',
     'NIMG_ROWS_PFD': 'group:optin_b',
-    # pointwise.hip
+    # runtime.hip
     'NIMG_NO_TICKETS': 'group:no_tickets',
     # other kernel families
     'NIMG_NO_S2D3_ROWS': 'covered_elsewhere:test_gpu_tail_exact',

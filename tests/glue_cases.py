@@ -22,7 +22,7 @@ from util import (EXACT_SUM_LIMIT, assert_exact_conditions, assert_no_denormals,
 
 F32 = np.float32
 ALPHA = 0.25                        # LeakyReLU slope of the exact cases (the library's default 0.2 is not dyadic)
-CAP = 2048 * 256                    # grid cap of csrc/pointwise.hip and csrc/losses.hip: 2048 workgroups of 256 threads
+CAP = 2048 * 256                    # grid cap of csrc/common.h grid_for (pointwise, pool, adam, losses): 2048 workgroups of 256 threads
 LATENT_CAP = 1024 * 256             # ... of csrc/latent.hip (affine, lrelu, tanh, clip01, zero_insert2, d2s2_scale)
 ISP_BIG = 8192 * 256 * 4 + 3        # above the 8192 workgroups of csrc/isp.hip, float4 items
 PW_BIG = CAP + 3

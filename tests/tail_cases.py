@@ -27,7 +27,7 @@ from util import (EXACT_SUM_LIMIT, F32_MIN_NORMAL, F32_UNIT_ROUNDOFF, PIXEL_GRID
                   bf16_rne, depth_to_space2, is_f32, mask_f32, odd_part, pack_bits, pixel_pairs, small_ints, space_to_depth2,
                   ternary, to64)
 
-CAP = 2048 * 256                    # grid cap of csrc/pointwise.hip and csrc/losses.hip (grid_for): 2048 workgroups of 256
+CAP = 2048 * 256                    # grid cap of csrc/common.h grid_for (pointwise, pool, adam, losses): 2048 workgroups of 256
 L2CAP = 1024 * 256                  # ... of csrc/latent.hip
 BENCH = 64 * 256 * 256 * 3          # the developed batch of the bench's default configuration
 F32 = np.float32
