@@ -119,8 +119,9 @@ int nimg_djpeg_sub_bwd(const float* x, const float* gy, const uint8_t* mask, con
  * The transform is recomputed from x; nothing of size N x 512 exists.  Values inside [-255.5, 256.5] see the five centres around
  * the nearest one (every other centre weighs < 2e-33 of it), values outside all 512.
  * workspace: nimg_djpeg_entropy_workspace_bytes(n, h, w) device bytes, 16-byte aligned (0 for an empty or refused shape); a shorter
- * one is NIMG_ERR_WORKSPACE.  _fwd leaves dH / d mean_k there for _bwd: the workspace must stay untouched between the two (several
- * _bwd calls may follow one _fwd).  h % 8, w % 8, a null pointer, a rounding mode out of range: NIMG_ERR_ARG.  The workgroups'
+ * one is NIMG_ERR_WORKSPACE.  _fwd leaves dH / d mean_k there for _bwd - the first 512 float64 of the workspace, centre -255 first,
+ * exactly 0 where the 1e-9 clip is active: the workspace must stay untouched between the two (several _bwd calls may follow one
+ * _fwd).  h % 8, w % 8, a null pointer, a rounding mode out of range: NIMG_ERR_ARG.  The workgroups'
  * partial histograms are summed in a fixed order; inside a workgroup the float64 LDS atomics arrive in any order, so two runs agree
  * to the last bits of float64, not bit for bit.  Asynchronous on `stream`, capturable, no allocation, no synchronisation; n == 0 is
  * a no-op. */

@@ -49,9 +49,10 @@ static const float COLOR_I[3][4] = {
  * xd  (optional): same shape float32 dequantised coefficients (second output of the reference model).
  * pre (optional): (n,h,w,3) float32, the value before the clamp.  mask (optional): (n,h,w) uint8, bit c set iff
  * 0 <= pre_c <= 1 - the CLOSED interval on which the clamp passes the gradient (the kernel's clip mask).
+ * z (optional): shape of idx, float32, the quotient X / Q before the rounding (the input of the rate term's quantiser).
  * returns 0, or -1 on bad shape. */
 static int forward_body(const float *x, float *y, const float *q, int16_t *idx, float *xd, float *pre, uint8_t *mask,
-                        int n, int h, int w)
+                        float *z, int n, int h, int w)
 {
     if (h % 8 || w % 8 || n < 0) return -1;
     const int hb = h / 8, wb = w / 8;
@@ -84,9 +85,11 @@ static int forward_body(const float *x, float *y, const float *q, int16_t *idx, 
                             float acc = 0.0f;
                             for (int i = 0; i < 8; ++i) acc = fmaf(t[i][v], DCT_F[u][i], acc);
                             const float qq = q[c * 64 + u * 8 + v];
-                            const float r = rintf(acc / qq);       /* half-to-even in the default rounding mode */
+                            const float zz = acc / qq;
+                            const float r = rintf(zz);             /* half-to-even in the default rounding mode */
                             X[u][v] = r * qq;
                             const size_t o = ((((size_t)im * 3 + c) * hb + by) * wb + bx) * 64 + u * 8 + v;
+                            if (z) z[o] = zz;
                             if (idx) idx[o] = (int16_t)r;
                             if (xd) xd[o] = X[u][v];
                         }
@@ -126,14 +129,20 @@ static int forward_body(const float *x, float *y, const float *q, int16_t *idx, 
 
 int djpeg_ref_forward(const float *x, float *y, const float *q, int16_t *idx, float *xd, int n, int h, int w)
 {
-    return forward_body(x, y, q, idx, xd, NULL, NULL, n, h, w);
+    return forward_body(x, y, q, idx, xd, NULL, NULL, NULL, n, h, w);
 }
 
 /* The same forward pass, also returning the pre-clip value and the clip mask (tests/djpeg_cases.py). */
 int djpeg_ref_forward_ex(const float *x, float *y, const float *q, int16_t *idx, float *xd, float *pre, uint8_t *mask,
                          int n, int h, int w)
 {
-    return forward_body(x, y, q, idx, xd, pre, mask, n, h, w);
+    return forward_body(x, y, q, idx, xd, pre, mask, NULL, n, h, w);
+}
+
+/* The same forward pass, also returning z = X / Q in float32 (tests/djpeg_rate_cases.py: the rate term's references start here). */
+int djpeg_ref_forward_z(const float *x, float *y, const float *q, int16_t *idx, float *xd, float *z, int n, int h, int w)
+{
+    return forward_body(x, y, q, idx, xd, NULL, NULL, z, n, h, w);
 }
 
 /* IJG quality scaling, compression/jpeg_helpers.py:264-305 (float32 arithmetic like the numpy reference). */

@@ -172,6 +172,17 @@ def c_forward_ex(x, q):
     return out
 
 
+def c_forward_z(x, q):
+    """djpeg_ref_forward_z: dict(y, idx, xd, z), z = X / Q in float32 before the rounding, (n, 3, h/8, w/8, 8, 8)."""
+    x = np.ascontiguousarray(x, np.float32)
+    q = np.ascontiguousarray(q, np.float32)
+    n, h, w, _ = x.shape
+    out = dict(y=np.zeros_like(x), idx=np.zeros((n, 3, h // 8, w // 8, 8, 8), np.int16),
+               xd=np.zeros((n, 3, h // 8, w // 8, 8, 8), np.float32), z=np.full((n, 3, h // 8, w // 8, 8, 8), np.nan, np.float32))
+    assert clib().djpeg_ref_forward_z(_vp(x), _vp(out['y']), _vp(q), _vp(out['idx']), _vp(out['xd']), _vp(out['z']), n, h, w) == 0
+    return out
+
+
 _HARD = {}
 
 
