@@ -970,6 +970,53 @@ int nimg_jpeg_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, co
                                  int n, int h, int w, int hs, int vs, int restart_interval, int subseq_bits, int16_t* coef,
                                  uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Grey-scale files: a frame of ONE component, which imageio.imsave / imread (jpeg_helpers.py:97-101) write
+ * and read for a mode 'L' image.  One entry per operation over the launchers of the colour entry points above, with
+ *   no sampling factors   a one-component scan is never interleaved: one block is one MCU, the blocks stand in raster order over
+ *                         ceil(h / 8) x ceil(w / 8), the right and bottom edges replicated; a restart interval counts blocks
+ *   restart_interval      0..65535 on every coding entry, 0 = none (there is no _restart twin)
+ *   x, y                  (n,h,w,1): the sample is the byte - no colour conversion, no up-sampling; float input through the same
+ *                         conversion and batch-wide "any value above 1" flag as nimg_jpeg_transform
+ *   coef                  int16 [image][block row][block col][64 zig-zag]
+ *   qtabs                 (device) [.][1][64] uint16, natural order: the one table of the frame
+ *   hist, tables          [n][2][257] and [n][2][272]: DC then AC (the DHT ids 00 10)
+ *   huffman (decode)      [n][2][272]: DC, AC; (decode_progressive) [n][n_scans][3][272] with slot 0 alone in use, every scan's mask 1
+ * Everything else - arguments, limits, status bits, rounds, what is clamped, the bounds of a segment - is that of the entry point named:
+ *   grey_workspace_bytes                      nimg_jpeg_encode_restart_workspace_bytes (serves transform*, encode, reconstruct_tables)
+ *   grey_transform                            nimg_jpeg_transform
+ *   grey_transform_tables                     nimg_jpeg_transform_tables
+ *   grey_encode                               nimg_jpeg_encode_restart (Annex K luma tables)
+ *   grey_histogram                            nimg_jpeg_histogram_restart; nimg_jpeg_optimal_tables takes its 2 n histograms as they are
+ *   grey_encode_tables (_workspace_bytes)     nimg_jpeg_encode_tables_restart (_workspace_bytes)
+ *   grey_decode (_workspace_bytes)            nimg_jpeg_decode_restart (_workspace_bytes)
+ *   grey_reconstruct_tables                   nimg_jpeg_reconstruct_tables
+ *   grey_decode_progressive (_workspace_bytes)  nimg_jpeg_decode_progressive (_workspace_bytes)
+ * No allocation, no synchronisation, capturable; n == 0 (n_src == n_items == 0) is a no-op; NIMG_ERR_ARG and NIMG_ERR_WORKSPACE come
+ * before any launch.  Purely added: NIMG_ABI_VERSION stays, and every entry point above answers every argument as before. */
+size_t nimg_jpeg_grey_workspace_bytes(int n, int h, int w, int restart_interval);
+int nimg_jpeg_grey_transform(const void* x, int is_u8, int n, int h, int w, int quality, int16_t* coef, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int nimg_jpeg_grey_transform_tables(const void* x, int is_u8, int n_src, int h, int w, const uint16_t* qtabs, int n_items, int16_t* coef,
+                                    int* err, void* workspace, size_t workspace_bytes, void* stream);
+int nimg_jpeg_grey_encode(const int16_t* coef, int n, int h, int w, int restart_interval, uint8_t* out, size_t out_capacity,
+                          uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream);
+int nimg_jpeg_grey_histogram(const int16_t* coef, int n, int h, int w, int restart_interval, uint32_t* hist, void* stream);
+size_t nimg_jpeg_grey_encode_tables_workspace_bytes(int n, int h, int w, int restart_interval);
+int nimg_jpeg_grey_encode_tables(const int16_t* coef, int n, int h, int w, int restart_interval, const uint8_t* tables, uint8_t* out,
+                                 size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+size_t nimg_jpeg_grey_decode_workspace_bytes(int n, int h, int w, int restart_interval, size_t ecd_bytes, int subseq_bits);
+int nimg_jpeg_grey_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int restart_interval,
+                          int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int nimg_jpeg_grey_reconstruct_tables(const int16_t* coef, int n, int h, int w, const uint16_t* qtabs, void* y, int out_u8, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+size_t nimg_jpeg_grey_decode_progressive_workspace_bytes(int n, int h, int w, int restart_interval, int n_scans, size_t ecd_bytes,
+                                                         int subseq_bits);
+int nimg_jpeg_grey_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans, const uint8_t* huffman,
+                                      int n, int h, int w, int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status,
+                                      uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Sign planes of the FAN's bf16-stored pooled activations: all that a layer's input gradient reads of the
  * activation in front of it is LeakyReLU', one bit per value.  A plane is (n, h, w, c / 8) bytes next to a bf16 tensor (n, h, w, c),
  * c % 8 == 0: bit e of byte c' / 8 is 1 iff the STORED bf16 value of channel c' + e is > 0 (-0, +0 and NaN give 0) - the predicate of

@@ -25,6 +25,10 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
   progressive= (jpeg_header, device_codec,              new: progressive files (SOF2), the ten scans of libjpeg's simple progression
   encode_batch, compress_batch, transcode_batch),       byte for byte, every scan with a Huffman table of its own (DESIGN.md section 4l);
   jpeg_progressive_pieces                               written only - parse_header refuses them as before
+  (n,h,w,1) input (jpeg_header 'grey', device_codec,    new: grey-scale files - one component, what libjpeg writes for a mode 'L' image byte
+  encode_batch, compress_batch), allow_grey=            for byte - written as baseline files and, asked for with allow_grey, read back,
+  (parse_header, decode_batch, decode_coefficients,     baseline or progressive, next to colour files in one call
+  transcode_batch)
   JPEGMarkerStats (:133-250)                            host parsing of a file's segments
 
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
@@ -98,10 +102,11 @@ def libjpeg_qtable(quality, channel=0):
     return np.clip(t, 1, 255).reshape(8, 8)
 
 
-def check_qtables(qtables):
+def check_qtables(qtables, grey=False):
     """Quantisation tables as a baseline file carries them: two (luma, chroma) or three (Y, Cb, Cr) tables of 64 integers 1..255 in
     natural (row-major) order, given as (T, 64) or (T, 8, 8) -> (T, 64) uint16.  Everything else is a ValueError that names the
-    table and the entry.  (Larger entries would need 16-bit DQT segments and an SOF1 frame: not written here.)"""
+    table and the entry.  (Larger entries would need 16-bit DQT segments and an SOF1 frame: not written here.)  `grey`: the tables of
+    a grey-scale file - one, or two or three of which the first alone is used and written, as libjpeg does -> (1, 64)."""
     try:
         t = np.asarray(qtables)
         numeric = np.issubdtype(t.dtype, np.number) or t.dtype == np.bool_
@@ -113,7 +118,11 @@ def check_qtables(qtables):
         t = t.reshape(t.shape[0], 64)
     if t.ndim != 2 or t.shape[1] != 64:
         raise ValueError('qtables: shape (T, 64) or (T, 8, 8) needed, got {}'.format(tuple(np.shape(qtables))))
-    if t.shape[0] not in (2, 3):
+    if grey:
+        if t.shape[0] not in (1, 2, 3):
+            raise ValueError('qtables: 1 table needed for a grey-scale file (of 2 or 3 the first is used), got {}'.format(t.shape[0]))
+        t = t[:1]
+    elif t.shape[0] not in (2, 3):
         raise ValueError('qtables: 2 tables (luma, chroma) or 3 (Y, Cb, Cr) needed, got {}'.format(t.shape[0]))
     t = t.astype(np.float64)
     with np.errstate(invalid='ignore'):
@@ -125,13 +134,14 @@ def check_qtables(qtables):
     return t.astype(np.uint16)
 
 
-def _quality_or_tables(quality, qtables, clamp=False):
+def _quality_or_tables(quality, qtables, clamp=False, grey=False):
     """Exactly one of the two says what a file is quantised with -> (quality 1..100 or None, (T, 64) uint16 or None); checked on the
-    host, before anything is uploaded.  A quality outside 1..100 is refused, or with `clamp` left to libjpeg_qtable's clamp."""
+    host, before anything is uploaded.  A quality outside 1..100 is refused, or with `clamp` left to libjpeg_qtable's clamp.
+    `grey`: the tables are those of a grey-scale file (check_qtables)."""
     if (quality is None) == (qtables is None):
         raise ValueError('either a quality or qtables= is needed, {} were given'.format('both' if qtables is not None else 'neither'))
     if qtables is not None:
-        return None, check_qtables(qtables)
+        return None, check_qtables(qtables, grey)
     if clamp:
         return quality, None
     q = int(quality)
@@ -140,10 +150,16 @@ def _quality_or_tables(quality, qtables, clamp=False):
     return q, None
 
 
-def _header_bytes(tables, restart_interval=0):
+JPEG_GREY_HEADER_BYTES = 328      # SOI .. SOS of a grey-scale file: one DQT, an SOF0 and an SOS of one component, the two luma DHT
+_GREY_DHT_OFFSET = 102
+
+
+def _header_bytes(tables, restart_interval=0, grey=False):
     """(bytes from SOI to the end of SOS with the Annex K Huffman tables, offset of the first DHT segment) of a file with
     `tables` = None or (2, 64): 623 and 177; (3, 64): one DQT segment more.  A restart interval adds its DRI segment's 6 bytes behind
-    the Huffman tables."""
+    the Huffman tables.  `grey`: 328 and 102, whatever the tables."""
+    if grey:
+        return JPEG_GREY_HEADER_BYTES + (_DRI_BYTES if restart_interval else 0), _GREY_DHT_OFFSET
     extra = _DQT_BYTES if tables is not None and len(tables) == 3 else 0
     return JPEG_HEADER_BYTES + extra + (_DRI_BYTES if restart_interval else 0), _DHT_OFFSET + extra
 
@@ -155,6 +171,8 @@ def jpeg_header(h, w, quality, subsampling='4:4:4', huffman=None, qtables=None, 
     see check_qtables): these tables instead of a quality's, as libjpeg writes a caller's - zig-zag, one DQT segment each; a third
     table goes to Cr (selector 2 in SOF0) and moves everything behind it by 69 bytes: 692 in all, the first DHT at 246.
     restart_interval (MCUs, 0..65535): above 0 the DRI segment FFDD 0004 RRRR between the last DHT segment and SOS, 6 bytes more.
+    subsampling 'grey': the header of a grey-scale file - one DQT segment (table 0: the quality's luma table, or
+    the first of qtables), SOF0 and SOS of one component (id 1, sampling 1x1), the DC and AC table 0 - Annex K's, or huffman (2, 272).
     progressive: the bytes in front of the FIRST scan of a progressive file - SOF2 in place of SOF0, the two DC tables of huffman
     (10, 272) (which is needed: a progressive file has no default tables), the DRI segment, the first SOS; jpeg_progressive_pieces
     gives what stands in front of every scan."""
@@ -175,6 +193,26 @@ def _dht_segment(ident, table):
 
 
 _ANNEX_K_DHT = b''.join(_dht_segment(t[0], np.frombuffer(t, np.uint8, offset=1)) for t in _DHT)
+_GREY_DHT_BYTES = 33 + 183        # the first two of them, the luma tables: all a grey-scale file carries
+_ANNEX_K_SYMBOLS, _GREY_ANNEX_K_SYMBOLS = 348, 174       # the symbols of the four tables, and of the two
+
+
+def _colour_only(what, grey):
+    """What DESIGN.md section 8 lists as out for grey-scale (one-component) input says so."""
+    if grey:
+        raise ValueError('grey-scale (one-component) images: {} is not supported'.format(what))
+
+
+def _grey_input(shape, subsampling, name):
+    """The sub-sampling a batch of `shape` is coded with: 'grey' for (..., 1) - which takes no other than the default or 'grey' itself,
+    there being no chroma to sub-sample -, else `subsampling`, which is then not 'grey'."""
+    if len(shape) in (3, 4) and shape[-1] == 1:
+        if subsampling not in ('4:4:4', 'grey'):
+            raise ValueError('{}: grey-scale input {} takes no chroma sub-sampling, got {!r}'.format(name, tuple(shape), subsampling))
+        return 'grey'
+    if subsampling == 'grey':
+        raise ValueError("{}: subsampling 'grey' needs (n,h,w,1) or (h,w,1) input, got {}".format(name, tuple(shape)))
+    return subsampling
 
 
 def _dri_segment(ri):
@@ -192,6 +230,7 @@ def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qt
         raise ValueError('huffman: the (10, 272) uint8 tables of a progressive file are needed, got {}'.format(
             None if huffman is None else (huffman.dtype, huffman.shape)))
     ri = ops.jpeg_restart_interval(restart_interval)
+    _colour_only('progressive=True (writing the six scans libjpeg writes for one component)', subsampling == 'grey')
     base = _jpeg_header(h, w, quality, subsampling, None, qtables, 0)
     dht = _header_bytes(None if qtables is None else check_qtables(qtables))[1]
     sof = dht - 19
@@ -211,14 +250,24 @@ def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qt
 
 def _jpeg_header(h, w, quality, subsampling, huffman, qtables, restart_interval):
     hs, vs = ops.jpeg_subsampling(subsampling)
+    grey = ops.jpeg_is_grey(hs, vs)
     ri = ops.jpeg_restart_interval(restart_interval)
-    quality, qtables = _quality_or_tables(quality, qtables, clamp=True)
+    quality, qtables = _quality_or_tables(quality, qtables, clamp=True, grey=grey)
     if qtables is None:
-        qtables = np.stack([libjpeg_qtable(quality, t).ravel() for t in (0, 1)])
+        qtables = np.stack([libjpeg_qtable(quality, t).ravel() for t in ((0,) if grey else (0, 1))])
     order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
     out = bytes.fromhex('ffd8' 'ffe00010' '4a46494600' '0101' '00' '0001' '0001' '0000')
     for t, table in enumerate(qtables):
         out += bytes.fromhex('ffdb0043') + bytes([t]) + table[order].astype(np.uint8).tobytes()
+    if grey:
+        dht = _ANNEX_K_DHT[:_GREY_DHT_BYTES]
+        if huffman is not None:
+            huffman = np.asarray(huffman)
+            if huffman.dtype != np.uint8 or huffman.shape != (2, 272):
+                raise ValueError('huffman: (2, 272) uint8 needed for a grey-scale file, got {} {}'.format(huffman.dtype, huffman.shape))
+            dht = b''.join(_dht_segment(ident, t) for ident, t in zip((0x00, 0x10), huffman))
+        return out + bytes.fromhex('ffc0000b' '08') + struct.pack('>HH', h, w) + bytes([1, 1, 0x11, 0]) + dht + _dri_segment(ri) + \
+            bytes.fromhex('ffda0008' '01' '0100' '00' '3f' '00')
     out += bytes.fromhex('ffc00011' '08') + struct.pack('>HH', h, w) + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, len(qtables) - 1])
     dht = _ANNEX_K_DHT
     if huffman is not None:
@@ -305,7 +354,8 @@ def _device_segments(coding, coef, n, h, w, hs, vs, ws=None, restart_interval=0)
 
 def _device_tables(tables, items, device):
     """Table sets (K, T, 64) uint16 of check_qtables -> the (K * items, 3, 64) device tensor the table kernels read, set-major: every
-    set repeated for `items` consecutive items; with two tables Cr takes the chroma table."""
+    set repeated for `items` consecutive items; with two tables Cr takes the chroma table.  The one table of a grey-scale file stays
+    one: (K * items, 1, 64)."""
     t = np.asarray(tables)
     t = t[:, [0, 1, 1]] if t.shape[1] == 2 else t
     return torch.from_numpy(np.repeat(t, items, axis=0).view(np.int16)).to(device)
@@ -321,9 +371,14 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
     (ops.jpeg_transform_tables, ops.jpeg_reconstruct_tables).  restart_interval (MCUs, 0..65535): the segments carry a restart marker
     behind every so many MCUs; the image is the same.  progressive: the ten scans of a progressive file
      - `segments` is then a list of ten bytes objects per image and the tables, (n, 10, 272), are always
-    returned as the third value: a progressive file has optimised tables with `optimize` or without."""
+    returned as the third value: a progressive file has optimised tables with `optimize` or without.
+    x (n,h,w,1): a grey-scale batch - subsampling left at its default or 'grey', the image (n,h,w,1), the tables
+    (n, 2, 272), qtables one table (or the first of two or three); not with `progressive`."""
+    subsampling = _grey_input(x.shape, subsampling, 'device_codec')
     hs, vs = ops.jpeg_subsampling(subsampling)
-    quality, qtables = _quality_or_tables(quality, qtables)
+    grey = ops.jpeg_is_grey(hs, vs)
+    _colour_only('progressive=True (writing the six scans libjpeg writes for one component)', grey and progressive)
+    quality, qtables = _quality_or_tables(quality, qtables, grey=grey)
     ri = ops.jpeg_restart_interval(restart_interval)
     n, h, w, _ = x.shape
     ws = torch.empty(ops.jpeg_workspace_bytes(n, h, w, hs, vs, ri) or 1, dtype=torch.uint8, device=x.device)
@@ -336,7 +391,10 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
     if want_bytes:
         segments, tables = _device_segments(_coding(optimize, progressive), coef, n, h, w, hs, vs, ws, ri)
     image = None
-    if want_image:
+    if want_image and grey and qtables is None:          # the one reconstruction of a grey-scale batch takes the table itself
+        qt = _device_tables(libjpeg_qtable(quality, 0).reshape(1, 1, 64).astype(np.uint16), n, x.device)
+        image = ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, workspace=ws)
+    elif want_image:
         image = ops.jpeg_reconstruct(coef, h, w, quality, hs, vs, workspace=ws) if qtables is None else \
             ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, workspace=ws)
     return (image, segments, tables) if optimize or progressive else (image, segments)
@@ -351,8 +409,10 @@ def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtabl
     marker FFD0..FFD7 behind every so many MCUs that another follows; a whole number of MCU rows is rows * MCUs per row.
     progressive: the files libjpeg writes with jpeg_simple_progression (Pillow: progressive=True) - SOF2 and ten scans, each with an
     optimal table of its own, the same bytes with `optimize` or without; in a single-component scan the restart interval counts
-    blocks."""
-    quality, qtables = _quality_or_tables(quality, qtables)
+    blocks.  (n,h,w,1) or (h,w,1): grey-scale files, the ones libjpeg writes for a mode 'L' image - subsampling
+    left at its default or 'grey', qtables one table (or the first of two or three), not with `progressive`."""
+    subsampling = _grey_input(np.shape(unwrap(batch_x)), subsampling, 'encode_batch')           # (host checks first: nothing is uploaded
+    quality, qtables = _quality_or_tables(quality, qtables, grey=subsampling == 'grey')         # for a call that is refused)
     ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=True)
     if x.dim() == 3:
@@ -380,8 +440,10 @@ def _header_lengths(h, w, quality, subsampling, n, tables, qtables, ri, progress
     if progressive:
         pieces = (jpeg_progressive_pieces(h, w, quality, subsampling, t, qtables=qtables, restart_interval=ri) for t in tables)
         return [sum(len(p) for p in front) for front in pieces]
-    head = _header_bytes(qtables, ri)[0]
-    return [head] * n if tables is None else (head - 348 + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)).tolist()
+    grey = subsampling == 'grey'
+    head = _header_bytes(qtables, ri, grey)[0]
+    annex_k = _GREY_ANNEX_K_SYMBOLS if grey else _ANNEX_K_SYMBOLS
+    return [head] * n if tables is None else (head - annex_k + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)).tolist()
 
 
 def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', optimize=False, *, qtables=None, restart_interval=0,
@@ -396,8 +458,12 @@ def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', 
     restart_interval: the sizes are those of encode_batch(restart_interval=), the DRI segment and the markers counted (both lie
     behind the first Huffman table, so `effective` counts them too); the image is the same.
     progressive: the sizes are those of encode_batch(progressive=True), `effective` again from the first Huffman table on (offset 177
-    with two quantisation tables); the image is the same."""
-    jpeg_quality, qtables = _quality_or_tables(jpeg_quality, qtables)
+    with two quantisation tables); the image is the same.
+    (h,w,1) or (n,h,w,1): the grey-scale codec - the image comes back with its one channel, the sizes are those of
+    encode_batch's grey-scale files, `effective` from the first Huffman table on (offset 102); subsampling left at its default or
+    'grey', not with `progressive`."""
+    subsampling = _grey_input(np.shape(unwrap(batch_x)), subsampling, 'compress_batch')
+    jpeg_quality, qtables = _quality_or_tables(jpeg_quality, qtables, grey=subsampling == 'grey')
     ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=False)
     if x.dim() not in (3, 4):
@@ -406,7 +472,7 @@ def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', 
     image, segments, tables = (device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=optimize, qtables=qtables,
                                             restart_interval=ri, progressive=progressive) + (None,))[:3]
     heads = _header_lengths(x.shape[-3], x.shape[-2], jpeg_quality, subsampling, len(segments), tables, qtables, ri, progressive)
-    dht = _header_bytes(qtables, ri)[1] if effective else 0
+    dht = _header_bytes(qtables, ri, subsampling == 'grey')[1] if effective else 0
     sizes = [head + (sum(len(scan) for scan in s) if progressive else len(s)) + 2 - dht for head, s in zip(heads, segments)]
     image = image.cpu().numpy()
     if single:
@@ -419,6 +485,7 @@ def match_quality(image, target=0.95, match='ssim', subsampling='4:4:4', optimiz
     `optimize` the bpp is that of the file with optimised Huffman tables."""
     from ..helpers import metrics
     assert image.ndim == 3, 'Only RGB images supported'
+    _colour_only('match_quality', image.shape[-1] == 1)
 
     def ssim_gap(q):
         return metrics.ssim(image, compress_batch(image, q, subsampling=subsampling, optimize=optimize)[0].squeeze()) - target
@@ -504,6 +571,7 @@ def rate_distortion(batch_x, qualities, subsampling='4:4:4', effective=True, wan
     q = _check_qualities(qualities)
     hs, vs = ops.jpeg_subsampling(subsampling)
     x = _device_batch(batch_x, keep_bytes=False)
+    _colour_only('rate_distortion', x.dim() == 4 and x.shape[3] == 1)
     if x.dim() != 4 or x.shape[3] != 3:
         raise ValueError('rate_distortion needs an (n,h,w,3) batch')
     n = x.shape[0]
@@ -556,6 +624,7 @@ def rate_distortion_tables(batch_x, tables, subsampling='4:4:4', effective=True,
     sets = np.stack([check_qtables(t) for t in tables])
     hs, vs = ops.jpeg_subsampling(subsampling)
     x = _device_batch(batch_x, keep_bytes=False)
+    _colour_only('rate_distortion_tables', x.dim() == 4 and x.shape[3] == 1)
     if x.dim() != 4 or x.shape[3] != 3:
         raise ValueError('rate_distortion_tables needs an (n,h,w,3) batch')
     n = x.shape[0]
@@ -573,6 +642,7 @@ def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4',
     if match not in ('ssim', 'bpp'):
         raise ValueError('Invalid argument: match')
     shape = tuple(unwrap(batch_x).shape)
+    _colour_only('match_quality_batch', len(shape) == 4 and shape[3] == 1)
     if len(shape) != 4 or shape[3] != 3:
         raise ValueError('match_quality_batch needs an (n,h,w,3) batch')
     n, h, w, _ = shape
@@ -620,12 +690,19 @@ def match_quality_batch(batch_x, target=0.95, match='ssim', subsampling='4:4:4',
 class JPEGHeader(namedtuple('JPEGHeader', 'h w hs vs qtables huffman ecd_offset ecd_end restart_interval', defaults=(0,))):
     """parse_header's result.  The tuple keeps the nine fields it had before progressive files were read (callers unpack it and count
     on restart_interval as its last); `scans` - a JPEGScan per scan of a progressive file, () for a baseline file - is an attribute
-    next to them, set by with_scans."""
+    next to them, set by with_scans.  So is `ncomp`, the components of the frame: 3, or 1 for a grey-scale file (allow_grey), whose
+    qtables are (1, 64) and whose huffman holds two pairs."""
     scans = ()
+    ncomp = 3
 
     def with_scans(self, scans):
         out = self._replace()
-        out.scans = tuple(scans)
+        out.scans, out.ncomp = tuple(scans), self.ncomp
+        return out
+
+    def with_ncomp(self, ncomp):
+        out = self._replace()
+        out.scans, out.ncomp = self.scans, int(ncomp)
         return out
 
 
@@ -647,7 +724,7 @@ _SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless'
               0xce: 'arithmetic-coded differential progressive', 0xcf: 'arithmetic-coded differential lossless'}
 
 
-def parse_header(data, allow_restart=False, allow_progressive=False):
+def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=False):
     """The header of a baseline JPEG file, read on the host without decoding: JPEGHeader(h, w, hs, vs, qtables (3, 64) uint16 in
     natural order per component, huffman = six (16 counts, symbols) pairs of bytes in the order Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC
     as the DHT bodies have them, ecd_offset, ecd_end = the offset of the final FFD9, restart_interval).  Accepted: SOF0 with 8-bit
@@ -661,7 +738,10 @@ def parse_header(data, allow_restart=False, allow_progressive=False):
     section 4n).  All its scans are walked: `scans` holds one JPEGScan per scan with the tables in force at its SOS, `huffman` is (),
     ecd_offset / ecd_end span the first scan to the final FFD9.  Refused by name: a script that breaks T.81's rules or leaves a
     coefficient short of Al = 0, a restart interval that changes between scans, more than 64 scans, a DNL marker, a missing table,
-    any marker between scans but DHT, DRI, COM and APPn."""
+    any marker between scans but DHT, DRI, COM and APPn.  allow_grey: a grey-scale file - a frame of one
+    component, SOF0 or with allow_progressive SOF2, 8-bit samples, every scan of that component, any Huffman table ids, with
+    allow_restart a DRI - is accepted too.  Its sampling factors may be any of 1..4: a one-component scan is never interleaved, so they
+    change nothing, and hs = vs = 1 is reported.  Its qtables are (1, 64), its huffman two pairs (DC, AC), its `ncomp` 1."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise ValueError('JPEG data: bytes needed, got {}'.format(type(data).__name__))
     data = bytes(data)
@@ -708,14 +788,17 @@ def parse_header(data, allow_restart=False, allow_progressive=False):
             if body[0] != 8:
                 raise ValueError('{}-bit samples (only 8-bit baseline files are read)'.format(body[0]))
             h, w, ncomp = struct.unpack_from('>HH', body, 1) + (body[5],)
-            if ncomp != 3:
+            if ncomp != 3 and not (ncomp == 1 and allow_grey):
                 raise ValueError('{} (3 components needed, the file has {})'.format(
                     {1: 'grey-scale file', 4: 'CMYK / four-component file'}.get(ncomp, 'unsupported number of components'), ncomp))
             if h < 1 or w < 1 or h > _MAX_SIDE or w > _MAX_SIDE:
                 raise ValueError('unsupported size {}x{} (1..{} per side)'.format(h, w, _MAX_SIDE))
-            comps = [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(3)]
+            comps = [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(ncomp)]
             sampling = tuple(c[1:3] for c in comps)
-            if sampling[0] not in ((1, 1), (2, 1), (2, 2)) or sampling[1:] != ((1, 1), (1, 1)):
+            if ncomp == 1:
+                if not (1 <= sampling[0][0] <= 4 and 1 <= sampling[0][1] <= 4):
+                    raise ValueError('illegal sampling factors {}x{} of the one component (1..4 each)'.format(*sampling[0]))
+            elif sampling[0] not in ((1, 1), (2, 1), (2, 2)) or sampling[1:] != ((1, 1), (1, 1)):
                 raise ValueError('unsupported sampling factors {} (luma 1x1, 2x1 or 2x2 over 1x1 chroma)'.format(
                     ' '.join('{}x{}'.format(*f) for f in sampling)))
             frame = (h, w, comps)
@@ -745,15 +828,18 @@ def parse_header(data, allow_restart=False, allow_progressive=False):
         return _parse_scans(data, pos, frame, qt, huff, restart or 0, allow_restart)
     if len(body) < 1 or len(body) != 4 + 2 * body[0]:
         raise ValueError('malformed SOS segment')
-    if body[0] != 3:
+    nc = len(comps)
+    if nc == 1 and body[0] != 1:
+        raise ValueError('the scan holds {} components, the frame of a grey-scale file one'.format(body[0]))
+    if body[0] != nc:
         raise ValueError('non-interleaved file: the scan holds {} of 3 components'.format(body[0]))
-    if [body[1 + 2 * c] for c in range(3)] != [c[0] for c in comps]:
+    if [body[1 + 2 * c] for c in range(nc)] != [c[0] for c in comps]:
         raise ValueError('the scan does not list the components in frame order')
-    ss, se, ahal = body[7], body[8], body[9]
+    ss, se, ahal = body[1 + 2 * nc], body[2 + 2 * nc], body[3 + 2 * nc]
     if (ss, se, ahal) != (0, 63, 0):
         raise ValueError('not a baseline scan: Ss={} Se={} Ah/Al={:02x} (0, 63, 00 needed)'.format(ss, se, ahal))
-    tables, qtables = [], np.zeros((3, 64), np.uint16)
-    for c in range(3):
+    tables, qtables = [], np.zeros((nc, 64), np.uint16)
+    for c in range(nc):
         sel = body[2 + 2 * c]
         if (sel >> 4) > 3 or (sel & 15) > 3:
             raise ValueError('malformed SOS segment')
@@ -786,6 +872,8 @@ def parse_header(data, allow_restart=False, allow_progressive=False):
         if nxt in (0xda, 0xc4, 0xdb, 0xdd):
             raise ValueError('several scans: marker FF{:02X} behind the first entropy-coded segment'.format(nxt))
         raise ValueError('unexpected marker FF{:02X} in the entropy-coded segment'.format(nxt))
+    if nc == 1:
+        return JPEGHeader(h, w, 1, 1, qtables, tuple(tables), ecd_offset, k, restart or 0).with_ncomp(1)
     return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, tuple(tables), ecd_offset, k, restart or 0)
 
 
@@ -810,18 +898,21 @@ def _segment_end(data, k, restart, allow_restart):
             return k
 
 
-def jpeg_script_check(script):
+def jpeg_script_check(script, ncomp=3):
     """script: [(components, Ss, Se, Ah, Al)] -> the level of every scan (1 + the highest level of an earlier
-    scan of a shared component whose band overlaps); ValueError names the rule of T.81 G.1.1.1 a script breaks."""
+    scan of a shared component whose band overlaps); ValueError names the rule of T.81 G.1.1.1 a script breaks.  ncomp: the components
+    of the frame, 3 or 1 - every scan of a grey-scale file holds its one component."""
     if len(script) > JPEG_SCANS_MAX:
         raise ValueError('progressive file with {} scans (at most {} are read)'.format(len(script), JPEG_SCANS_MAX))
-    al_of, levels = [[None] * 64 for _ in range(3)], []
+    al_of, levels = [[None] * 64 for _ in range(ncomp)], []
     for i, (cs, ss, se, ah, al) in enumerate(script):
         where = 'scan {} (components {} Ss={} Se={} Ah={} Al={})'.format(i, list(cs), ss, se, ah, al)
         if ss == 0 and se != 0:
             raise ValueError('illegal progressive script: {} mixes DC and AC coefficients'.format(where))
         if ss > se or se > 63 or ah > 13 or al > 13:
             raise ValueError('illegal progressive script: {} has a band or bit position out of range'.format(where))
+        if ncomp == 1 and tuple(cs) != (0,):
+            raise ValueError('illegal progressive script: {} - every scan of a one-component frame holds that component, once'.format(where))
         if tuple(cs) not in ((0,), (1,), (2,), (0, 1, 2)) or (ss > 0 and len(cs) != 1):
             raise ValueError('illegal progressive script: {} - a DC scan holds one component or all three in frame order, an AC scan '
                              'exactly one'.format(where))
@@ -835,7 +926,7 @@ def jpeg_script_check(script):
                 al_of[c][k] = al
         levels.append(1 + max([lv for lv, (ce, se0, se1, _, _) in zip(levels, script) if set(ce) & set(cs) and se0 <= se and ss <= se1]
                               or [0]))
-    short = [(c, k) for c in range(3) for k in range(64) if al_of[c][k] != 0]
+    short = [(c, k) for c in range(ncomp) for k in range(64) if al_of[c][k] != 0]
     if short:
         raise ValueError('incomplete progression: coefficient {} of component {} never reaches Al = 0 ({} such coefficients; libjpeg '
                          'smooths such files)'.format(short[0][1], short[0][0], len(short)))
@@ -909,12 +1000,15 @@ def _parse_scans(data, pos, frame, qt, huff, restart, allow_restart):
                 raise ValueError('no marker at offset {}'.format(pos))
         if data[pos + 1] == 0xd9:
             break
-    jpeg_script_check([s[:5] for s in scans])
-    qtables = np.zeros((3, 64), np.uint16)
-    for c in range(3):
+    nc = len(comps)
+    jpeg_script_check([s[:5] for s in scans], nc)
+    qtables = np.zeros((nc, 64), np.uint16)
+    for c in range(nc):
         if comps[c][3] not in qt:
             raise ValueError('missing quantisation table {} of component {}'.format(comps[c][3], c))
         qtables[c] = qt[comps[c][3]]
+    if nc == 1:
+        return JPEGHeader(h, w, 1, 1, qtables, (), scans[0].ecd_offset, pos, restart).with_ncomp(1).with_scans(scans)
     return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, (), scans[0].ecd_offset, pos, restart).with_scans(scans)
 
 
@@ -936,21 +1030,23 @@ def _status_text(status):
     return ' | '.join(text for bit, text in JPEG_STATUS_BITS.items() if status & bit)
 
 
-def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progressive=False):
+def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progressive=False, allow_grey=False):
     """Headers parsed, one upload, one nimg_jpeg_decode[_restart] per group of equal (h, w, hs, vs, restart interval) - for progressive
     files (allow_progressive) one nimg_jpeg_decode_progressive per group of equal geometry, interval and scan script.  Returns
-    (headers, groups) with groups = [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back."""
-    headers = [parse_header(f, allow_restart, allow_progressive) for f in files]
+    (headers, groups) with groups = [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back.  The
+    (hs, vs) of a group of grey-scale files (allow_grey) is ops.JPEG_GREY: another geometry, so never in a group with colour files."""
+    headers = [parse_header(f, allow_restart, allow_progressive, allow_grey) for f in files]
     if not headers:
         raise ValueError('no files to decode')
     keys = OrderedDict()
     for i, hd in enumerate(headers):
-        keys.setdefault((hd.h, hd.w, hd.hs, hd.vs, hd.restart_interval, tuple(s[:5] for s in hd.scans)), []).append(i)
+        hs, vs = ops.JPEG_GREY if hd.ncomp == 1 else (hd.hs, hd.vs)
+        keys.setdefault((hd.h, hd.w, hs, vs, hd.restart_interval, tuple(s[:5] for s in hd.scans)), []).append(i)
     dev = device if device is not None else default_device()
     order = [i for idx in keys.values() for i in idx]                    # the segments back to back, group after group
     spans = [[(s.ecd_offset, s.ecd_end) for s in headers[i].scans] or [(headers[i].ecd_offset, headers[i].ecd_end)] for i in order]
     blob = b''.join(files[i][lo:hi] for i, sp in zip(order, spans) for lo, hi in sp)
-    tables = []                                                          # baseline: six per file; progressive: three per scan
+    tables = []                                                          # baseline: six per file (grey: two); progressive: three per scan
     for i in order:
         per = [headers[i].huffman] if not headers[i].scans else [s.huffman + ((bytes(16), b''),) * (3 - len(s.huffman))
                                                                  for s in headers[i].scans]
@@ -959,26 +1055,27 @@ def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progre
     for j, (counts, symbols) in enumerate(tables):
         huff[j, :16] = np.frombuffer(counts, np.uint8)
         huff[j, 16:16 + len(symbols)] = np.frombuffer(symbols, np.uint8)
-    qt = np.stack([headers[i].qtables for i in order]).view(np.int16)
+    qt = np.concatenate([headers[i].qtables.reshape(-1) for i in order]).view(np.int16)        # three tables per file, or one
     ecd = torch.from_numpy(np.frombuffer(blob if blob else b'\0', np.uint8).copy()).to(dev)
     huff, qt = torch.from_numpy(huff).to(dev), torch.from_numpy(qt).to(dev)
-    groups, j0, b0, t0 = [], 0, 0, 0
+    groups, j0, b0, t0, q0 = [], 0, 0, 0, 0
     for (h, w, hs, vs, ri, script), idx in keys.items():
+        nc = 1 if ops.jpeg_is_grey(hs, vs) else 3
         lengths = [hi - lo for sp in spans[j0:j0 + len(idx)] for lo, hi in sp]
         off = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
         part = ecd[b0:b0 + max(sum(lengths), 1)]
         if script:
             rows = np.array([[sum(1 << c for c in cs), ss, se, ah, al, lv]
-                             for (cs, ss, se, ah, al), lv in zip(script, jpeg_script_check(script))], np.int32)
+                             for (cs, ss, se, ah, al), lv in zip(script, jpeg_script_check(script, nc))], np.int32)
             count = len(idx) * len(script) * 3
             coef, status, rounds = ops.jpeg_decode_progressive(part, off, huff[t0:t0 + count].view(len(idx), len(script), 3, 272), rows, h, w,
                                                                hs, vs, subseq_bits=subseq_bits, restart_interval=ri)
         else:
-            count = len(idx) * 6
-            coef, status, rounds = ops.jpeg_decode(part, off, huff[t0:t0 + count].view(len(idx), 6, 272), h, w, hs, vs,
+            count = len(idx) * 2 * nc
+            coef, status, rounds = ops.jpeg_decode(part, off, huff[t0:t0 + count].view(len(idx), 2 * nc, 272), h, w, hs, vs,
                                                    subseq_bits=subseq_bits, restart_interval=ri)
-        groups.append((idx, (h, w, hs, vs), coef, status, rounds, qt[j0:j0 + len(idx)]))
-        j0, b0, t0 = j0 + len(idx), b0 + sum(lengths), t0 + count
+        groups.append((idx, (h, w, hs, vs), coef, status, rounds, qt[q0:q0 + len(idx) * nc * 64].view(len(idx), nc, 64)))
+        j0, b0, t0, q0 = j0 + len(idx), b0 + sum(lengths), t0 + count, q0 + len(idx) * nc * 64
     return headers, groups
 
 
@@ -995,7 +1092,8 @@ def _as_files(files):
     return [bytes(files)] if isinstance(files, (bytes, bytearray, memoryview)) else [bytes(f) for f in files]
 
 
-def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False):
+def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False,
+                 allow_grey=False):
     """Decode baseline JPEG files on the GPU: a list of bytes (or one bytes) -> (n,h,w,3) uint8, the array imageio.imread returns for
     each (libjpeg's islow inverse DCT and fancy up-sampling, bit for bit), or float32(byte) / 255 with as_float.  Files of different
     geometry give a list of (h,w,3) arrays in input order.  Any 8-bit quantisation and Huffman tables are read from each file
@@ -1004,9 +1102,11 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     ValueError naming the indices and the status bits (JPEG_STATUS_BITS).  allow_restart: files with a restart interval are read
     too (parse_header); a group is then the files of equal geometry and interval, and every interval is decoded from its own start.
     allow_progressive: progressive files of any legal scan script are read too (parse_header), next to baseline
-    ones in the same call; a group is then the files of equal geometry, interval and script (nimg_jpeg_decode_progressive)."""
+    ones in the same call; a group is then the files of equal geometry, interval and script (nimg_jpeg_decode_progressive).
+    allow_grey: grey-scale files are read too (parse_header) and decode to (n,h,w,1) - the array imageio.imread
+    returns for them with a last axis added; next to colour files they are another geometry, so the result is then a list."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey)
     images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
               for _, (h, w, hs, vs), coef, _, _, qt in groups]
     words = [len(g[0]) for g in groups]
@@ -1031,14 +1131,16 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     return result
 
 
-def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False):
+def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False,
+                        allow_grey=False):
     """The quantised coefficients of baseline files of ONE geometry, as stored in the files: ((n, real blocks, 64) int16 in the layout
     of DESIGN.md section 4c - [Y | Cb | Cr][block row][block col][zig-zag] - and the (n, 3, 64) uint16 quantisation tables per
     component in natural order; jpeg_qf_estimation(tables[i, c].reshape(8, 8), c) names the quality they came from).
     allow_restart: as decode_batch's; the files must then share their restart interval too.  allow_progressive: as decode_batch's;
-    the files must then share their scan script too (baseline files count as one script)."""
+    the files must then share their scan script too (baseline files count as one script).  allow_grey: grey-scale files are read too
+    - (n, blocks, 64) coefficients in raster order and (n, 1, 64) tables -, never in one call with colour files."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey)
     if len(groups) != 1:
         raise ValueError('decode_coefficients needs files of one geometry{}, got {}'.format(
             (' and restart interval' if allow_restart else '') + (' and scan script' if allow_progressive else ''), [g[1] for g in groups]))
@@ -1047,7 +1149,7 @@ def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, 
     return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
 
 
-def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False, allow_progressive=False):
+def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False, allow_progressive=False, allow_grey=False):
     """Baseline files written again with their coefficients and their quantisation tables untouched - a list of bytes in input order.
     The Huffman tables are the optimal ones of each image (what jpegtran -optimize does) or, with optimize=False, Annex K's.  Every
     file parse_header accepts is read; the header written is the one of encode_batch - JFIF APP0, two DQT segments where the file's Cb
@@ -1057,18 +1159,22 @@ def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=Fa
     markers are written again.  progressive: baseline files in, progressive files out (the lossless jpegtran -progressive); their
     tables are optimal whatever `optimize` says.  allow_progressive: progressive files of any legal scan script are read too
     (parse_header) and written as baseline files - jpegtran -optimize of a progressive file - or, with progressive, as libjpeg's simple
-    progression whatever script came in."""
+    progression whatever script came in.  allow_grey: grey-scale files, baseline or with allow_progressive progressive, are read too and
+    written again as grey-scale baseline files (one DQT segment, the DC and AC table 0) - not with `progressive`."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, 0, None, allow_restart, allow_progressive)
+    headers, groups = _decode_groups(files, 0, None, allow_restart, allow_progressive, allow_grey)
+    _colour_only('progressive=True (writing the six scans libjpeg writes for one component)',
+                 progressive and any(hd.ncomp == 1 for hd in headers))
     _raise_on_status(groups, np.split(torch.cat([g[3] for g in groups]).cpu().numpy(), np.cumsum([len(g[0]) for g in groups])[:-1]))
     names = {v: k for k, v in ops.JPEG_SUBSAMPLING.items()}
+    names[ops.JPEG_GREY] = 'grey'
     result = [None] * len(files)
     for idx, (h, w, hs, vs), coef, _, _, _ in groups:
         ri = headers[idx[0]].restart_interval                               # the group's: files are grouped by it
         segments, tables = _device_segments(_coding(optimize, progressive), coef, len(idx), h, w, hs, vs, restart_interval=ri)
         for j, i in enumerate(idx):                                         # a file at a time: each keeps its quantisation tables
             qt = headers[i].qtables
-            qt = qt[:2] if np.array_equal(qt[1], qt[2]) else qt
+            qt = qt if len(qt) == 1 else (qt[:2] if np.array_equal(qt[1], qt[2]) else qt)
             result[i], = _jpeg_files(h, w, None, names[(hs, vs)], segments[j:j + 1], None if tables is None else tables[j:j + 1], qt, ri,
                                      progressive)
     return result

@@ -159,6 +159,13 @@ __device__ __forceinline__ void load_rgb(const void* img, int w, int y, int x, b
     }
 }
 
+// the one sample of a pixel of a grey-scale image: the byte itself, no colour conversion
+template <bool U8>
+__device__ __forceinline__ int load_grey(const void* img, int w, int y, int x, bool div) {
+    const long i = (long)y * w + x;
+    return U8 ? (int)((const uint8_t*)img)[i] : byte_of(((const float*)img)[i], div);
+}
+
 // libjpeg's fixed-point RGB -> YCbCr (jccolor.c), one sample: the luma, and Cb (comp = 1) or Cr (comp = 2)
 __device__ __forceinline__ int luma_of(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
 __device__ __forceinline__ int chroma_of(int comp, int r, int g, int b) {
@@ -171,10 +178,12 @@ __device__ __forceinline__ int chroma_of(int comp, int r, int g, int b) {
 __device__ __forceinline__ int downsample_of(int sum, int vs, int x) { return vs == 2 ? (sum + 1 + (x & 1)) >> 2 : (sum + (x & 1)) >> 1; }
 
 // sample (y, x) of component `comp` as the forward DCT sees it: the right edge replicated at full resolution, the bottom row up
-// to a multiple of the vertical factor, chroma down-sampled, then the component's last row replicated downwards
-template <bool U8>
+// to a multiple of the vertical factor, chroma down-sampled, then the component's last row replicated downwards.  GREY: the one
+// component of a grey-scale image - its edges replicated, nothing else
+template <bool U8, bool GREY>
 __device__ __forceinline__ int sample(const void* img, const JpegGeo& g, int comp, int y, int x, bool div) {
     int r, gg, b;
+    if (GREY) return load_grey<U8>(img, g.w, min(y, g.h - 1), min(x, g.w - 1), div);
     if (comp == 0) {
         load_rgb<U8>(img, g.w, min(y, g.h - 1), min(x, g.w - 1), div, r, gg, b);
         return luma_of(r, gg, b);
@@ -260,8 +269,9 @@ __device__ __forceinline__ void locate(const JpegGeo& g, long t, int& img, int& 
     }
 }
 
-// one thread per real block
-template <bool U8, class Tables>
+// one thread per real block.  GREY (g.nc == 1): x is (n,h,w,1) - a compile-time choice, so that the colour instantiations are the
+// code they were before grey-scale files were written
+template <bool U8, class Tables, bool GREY = false>
 __global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restrict__ x, int16_t* __restrict__ coef, JpegGeo g, Tables tabs,
                                                              const uint32_t* __restrict__ flag) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -270,14 +280,15 @@ __global__ void __launch_bounds__(256) jpeg_transform_kernel(const void* __restr
     locate(g, t, item, comp, br, bc);
     const bool div = !U8 && *flag != 0;
     const int img = tabs.source(item);
-    const void* base = U8 ? (const void*)((const uint8_t*)x + (long)img * g.h * g.w * 3)
-                          : (const void*)((const float*)x + (long)img * g.h * g.w * 3);
+    constexpr int NC = GREY ? 1 : 3;
+    const void* base = U8 ? (const void*)((const uint8_t*)x + (long)img * g.h * g.w * NC)
+                          : (const void*)((const float*)x + (long)img * g.h * g.w * NC);
     const uint16_t* q = tabs.table(g, t, item, comp);
     int d[64];
 #pragma unroll
     for (int r = 0; r < 8; ++r)
 #pragma unroll
-        for (int c = 0; c < 8; ++c) d[8 * r + c] = sample<U8>(base, g, comp, 8 * br + r, 8 * bc + c, div) - 128;
+        for (int c = 0; c < 8; ++c) d[8 * r + c] = sample<U8, GREY>(base, g, comp, 8 * br + r, 8 * bc + c, div) - 128;
 #pragma unroll
     for (int r = 0; r < 8; ++r) fdct8<1, true>(d + 8 * r);
 #pragma unroll
@@ -420,7 +431,7 @@ inline bool grid_ok(long items, int per_block) { return (items + per_block - 1) 
 #define NIMG_HIDDEN __attribute__((visibility("hidden")))
 // *flag |= 1 if any of the `count` floats at x exceeds 1 (flag zeroed here); 0 or NIMG_ERR_LAUNCH
 NIMG_HIDDEN int nimg_internal_jpeg_above_one(const float* x, long count, uint32_t* flag, hipStream_t stream);
-// the sample planes of g.n images (as the inverse DCT leaves them) -> y (n,h,w,3): float32 k / 255, or the bytes themselves if u8
+// the sample planes of g.n images (as the inverse DCT leaves them) -> y (n,h,w,g.nc): float32 k / 255, or the bytes themselves if u8
 NIMG_HIDDEN int nimg_internal_jpeg_colour(uint8_t* planes, void* y, bool u8, const JpegGeo& g, hipStream_t stream);
 // the coder's passes around its bit-length and its emit pass (a raw buffer of raw_words words per image):
 // off[n][SB] bit lengths -> offsets in place, total[n]; the words of raw the bits will be OR-ed into zeroed.  With g.ri the end of an

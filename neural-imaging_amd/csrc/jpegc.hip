@@ -213,6 +213,11 @@ __global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ 
     if (t >= (long)g.n * g.h * g.w) return;
     const int img = (int)(t / ((long)g.h * g.w)), r = (int)(t - (long)img * g.h * g.w), y = r / g.w, x = r - y * g.w;
     const int yy = plane_of(planes, g, img, 0)[(size_t)y * 8 * g.bwY + x];
+    if (g.nc == 1) {                                     // grey-scale: the range-limited sample is the pixel
+        if (U8) ((uint8_t*)out)[t] = (uint8_t)yy;
+        else ((float*)out)[t] = __fdiv_rn((float)yy, 255.0f);
+        return;
+    }
     const int cb = chroma_at(plane_of(planes, g, img, 1), g, y, x) - 128;
     const int cr = chroma_at(plane_of(planes, g, img, 2), g, y, x) - 128;
     const int R = min(max(red_of(yy, cr), 0), 255);
@@ -229,20 +234,11 @@ __global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ 
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t nimg_jpeg_workspace_bytes(int n, int h, int w, int hs, int vs) {
+// ---- the launchers: one per operation, for files of three components (nc = 3) and of one (nc = 1, section 4p) -------------------
+int transform_launch(const void* x, int is_u8, int n, int h, int w, int hs, int vs, int nc, int quality, int16_t* coef, void* workspace,
+                     size_t workspace_bytes, void* stream) {
     JpegGeo g;
-    if (!make_geo(&g, n, h, w, hs, vs)) return 0;
-    return carve(g, nullptr).bytes;
-}
-
-int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, int vs, int quality, int16_t* coef, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-    JpegGeo g;
-    if (!x || !coef || !workspace || quality < 1 || quality > 100 || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
+    if (!x || !coef || !workspace || quality < 1 || quality > 100 || !make_geo(&g, n, h, w, hs, vs, nc)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     const long blocks = (long)n * g.NB;
@@ -250,27 +246,33 @@ int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, i
     hipStream_t st = (hipStream_t)stream;
     const BatchTables tabs{make_qtabs(quality)};
     const unsigned grid = (unsigned)((blocks + 255) / 256);
-    if (is_u8) {
-        hipLaunchKernelGGL((jpeg_transform_kernel<true, BatchTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, (const uint32_t*)ws.flag);
-    } else {
-        const int rc = nimg_internal_jpeg_above_one((const float*)x, (long)n * h * w * 3, ws.flag, st);
+    const uint32_t* flag = ws.flag;
+    if (!is_u8) {
+        const int rc = nimg_internal_jpeg_above_one((const float*)x, (long)n * h * w * nc, ws.flag, st);
         if (rc != NIMG_OK) return rc;
-        hipLaunchKernelGGL((jpeg_transform_kernel<false, BatchTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, (const uint32_t*)ws.flag);
+    }
+    if (nc == 1) {
+        if (is_u8) hipLaunchKernelGGL((jpeg_transform_kernel<true, BatchTables, true>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
+        else hipLaunchKernelGGL((jpeg_transform_kernel<false, BatchTables, true>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
+    } else {
+        if (is_u8) hipLaunchKernelGGL((jpeg_transform_kernel<true, BatchTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
+        else hipLaunchKernelGGL((jpeg_transform_kernel<false, BatchTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
     }
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
 }
 
-size_t nimg_jpeg_encode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval) {
+size_t workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval) {
     JpegGeo g;
-    if (!make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return 0;
+    if (!make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval)) return 0;
     return carve(g, nullptr).bytes;
 }
 
-int nimg_jpeg_encode_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint8_t* out,
-                             size_t out_capacity, uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream) {
+int encode_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, int restart_interval, uint8_t* out,
+                  size_t out_capacity, uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream) {
     JpegGeo g;
-    if (!coef || !out || !lengths || !workspace || !make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return NIMG_ERR_ARG;
+    if (!coef || !out || !lengths || !workspace || !make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval))
+        return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -283,6 +285,42 @@ int nimg_jpeg_encode_restart(const int16_t* coef, int n, int h, int w, int hs, i
     hipLaunchKernelGGL(jpeg_emit_kernel, dim3(grid), dim3(256), 0, st, coef, (const uint32_t*)ws.off, ws.raw, g, ws.raw_words);
     NIMG_CHECK_LAUNCH();
     return nimg_internal_jpeg_pack(ws.raw, ws.total, ws.off, lengths, ws.dst, out, out_capacity, g, ws.raw_words, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nimg_jpeg_workspace_bytes(int n, int h, int w, int hs, int vs) { return workspace_size(n, h, w, hs, vs, 3, 0); }
+
+int nimg_jpeg_transform(const void* x, int is_u8, int n, int h, int w, int hs, int vs, int quality, int16_t* coef, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    return transform_launch(x, is_u8, n, h, w, hs, vs, 3, quality, coef, workspace, workspace_bytes, stream);
+}
+
+size_t nimg_jpeg_encode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval) {
+    return workspace_size(n, h, w, hs, vs, 3, restart_interval);
+}
+
+int nimg_jpeg_encode_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint8_t* out,
+                             size_t out_capacity, uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream) {
+    return encode_launch(coef, n, h, w, hs, vs, 3, restart_interval, out, out_capacity, lengths, workspace, workspace_bytes, stream);
+}
+
+size_t nimg_jpeg_grey_workspace_bytes(int n, int h, int w, int restart_interval) {
+    return workspace_size(n, h, w, 1, 1, 1, restart_interval);
+}
+
+int nimg_jpeg_grey_transform(const void* x, int is_u8, int n, int h, int w, int quality, int16_t* coef, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    if (n == 0) return NIMG_OK;
+    return transform_launch(x, is_u8, n, h, w, 1, 1, 1, quality, coef, workspace, workspace_bytes, stream);
+}
+
+int nimg_jpeg_grey_encode(const int16_t* coef, int n, int h, int w, int restart_interval, uint8_t* out, size_t out_capacity,
+                          uint32_t* lengths, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n == 0) return NIMG_OK;
+    return encode_launch(coef, n, h, w, 1, 1, 1, restart_interval, out, out_capacity, lengths, workspace, workspace_bytes, stream);
 }
 
 int nimg_jpeg_encode(const int16_t* coef, int n, int h, int w, int hs, int vs, uint8_t* out, size_t out_capacity, uint32_t* lengths,

@@ -32,8 +32,9 @@ __global__ void __launch_bounds__(256) jpeg_histogram_kernel(const int16_t* __re
         jpegopt_walk_block(coef + (long)img * g.NB * 64, g, s, sink);
     }
     __syncthreads();
-    uint32_t* dst = hist + (size_t)img * 4 * JPEGOPT_HIST;
-    for (int i = threadIdx.x; i < 4 * JPEGOPT_HIST; i += 256) {
+    const int bins = jpegopt_tables(g) * JPEGOPT_HIST;   // a grey-scale file has the two luma histograms alone
+    uint32_t* dst = hist + (size_t)img * bins;
+    for (int i = threadIdx.x; i < bins; i += 256) {
         const uint32_t v = s_hist[i];
         if (v) atomicAdd(dst + i, v);
     }
@@ -151,10 +152,11 @@ __global__ void __launch_bounds__(256) jpeg_optimal_tables_kernel(const uint32_t
 // ---- entropy coding with the tables of each image ----------------------------------------------------------------------------
 // one thread per image: status[image] = JPEGOPT_ST_TABLE or 0 (the call's only plain store to it; the bit-length pass ORs into it)
 __global__ void __launch_bounds__(64) jpeg_derive_kernel(const uint8_t* __restrict__ tables, uint32_t* __restrict__ codes,
-                                                         uint32_t* __restrict__ status, int n) {
+                                                         uint32_t* __restrict__ status, int n, int n_tables) {
     const int img = blockIdx.x * 64 + threadIdx.x;
     if (img >= n) return;
-    const bool ok = jpegopt_derive_image(tables + (size_t)img * 4 * JPEGOPT_TABLE_BYTES, codes + (size_t)img * JPEGOPT_CODE_WORDS);
+    const bool ok = jpegopt_derive_image(tables + (size_t)img * n_tables * JPEGOPT_TABLE_BYTES, codes + (size_t)img * JPEGOPT_CODE_WORDS,
+                                         n_tables);
     status[img] = ok ? 0u : JPEGOPT_ST_TABLE;
 }
 
@@ -207,19 +209,70 @@ __global__ void __launch_bounds__(256) jpeg_emit_tables_kernel(const int16_t* __
     sink.finish();
 }
 
+// ---- the launchers, for files of three components (nc = 3) and of one (nc = 1, section 4p) ----------------------------------------
+int histogram_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, int restart_interval, uint32_t* hist, void* stream) {
+    JpegGeo g;
+    if (!coef || !hist || !make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval)) return NIMG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)n * jpegopt_tables(g) * JPEGOPT_HIST * 4, st) != hipSuccess) return NIMG_ERR_LAUNCH;
+    hipLaunchKernelGGL(jpeg_histogram_kernel, dim3((unsigned)((g.SB + 255) / 256), (unsigned)n), dim3(256), 0, st, coef, hist, g);
+    NIMG_CHECK_LAUNCH();
+    return NIMG_OK;
+}
+
+size_t tables_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval) {
+    JpegGeo g;
+    if (!make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval)) return 0;
+    return carve(g, nullptr, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS).bytes;
+}
+
+int encode_tables_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, int restart_interval, const uint8_t* tables,
+                         uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    JpegGeo g;
+    if (!coef || !tables || !out || !lengths || !status || !workspace || !make_geo(&g, n, h, w, hs, vs, nc) ||
+        !set_restart(&g, restart_interval))
+        return NIMG_ERR_ARG;
+    const Workspace ws = carve(g, workspace, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS);
+    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((g.SB + 255) / 256), (unsigned)n);
+    hipLaunchKernelGGL(jpeg_derive_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, tables, ws.codes, status, n, jpegopt_tables(g));
+    NIMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jpeg_bitlen_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, ws.off, status, g);
+    NIMG_CHECK_LAUNCH();
+    int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, g, ws.raw_words, st);
+    if (rc != NIMG_OK) return rc;
+    hipLaunchKernelGGL(jpeg_emit_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, (const uint32_t*)ws.off,
+                       (const uint32_t*)status, ws.raw, g, ws.raw_words);
+    NIMG_CHECK_LAUNCH();
+    return nimg_internal_jpeg_pack(ws.raw, ws.total, ws.off, lengths, ws.dst, out, out_capacity, g, ws.raw_words, st);
+}
+
 }  // namespace
 
 extern "C" {
 
 int nimg_jpeg_histogram_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint32_t* hist,
                                 void* stream) {
-    JpegGeo g;
-    if (!coef || !hist || !make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return NIMG_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(hist, 0, (size_t)n * 4 * JPEGOPT_HIST * 4, st) != hipSuccess) return NIMG_ERR_LAUNCH;
-    hipLaunchKernelGGL(jpeg_histogram_kernel, dim3((unsigned)((g.SB + 255) / 256), (unsigned)n), dim3(256), 0, st, coef, hist, g);
-    NIMG_CHECK_LAUNCH();
-    return NIMG_OK;
+    return histogram_launch(coef, n, h, w, hs, vs, 3, restart_interval, hist, stream);
+}
+
+int nimg_jpeg_grey_histogram(const int16_t* coef, int n, int h, int w, int restart_interval, uint32_t* hist, void* stream) {
+    if (n == 0) return NIMG_OK;
+    return histogram_launch(coef, n, h, w, 1, 1, 1, restart_interval, hist, stream);
+}
+
+size_t nimg_jpeg_grey_encode_tables_workspace_bytes(int n, int h, int w, int restart_interval) {
+    return tables_workspace_size(n, h, w, 1, 1, 1, restart_interval);
+}
+
+int nimg_jpeg_grey_encode_tables(const int16_t* coef, int n, int h, int w, int restart_interval, const uint8_t* tables, uint8_t* out,
+                                 size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    if (n == 0) return NIMG_OK;
+    return encode_tables_launch(coef, n, h, w, 1, 1, 1, restart_interval, tables, out, out_capacity, lengths, status, workspace,
+                                workspace_bytes, stream);
 }
 
 int nimg_jpeg_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, uint32_t* hist, void* stream) {
@@ -235,9 +288,7 @@ int nimg_jpeg_optimal_tables(const uint32_t* hist, int n_tables, uint8_t* tables
 }
 
 size_t nimg_jpeg_encode_tables_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval) {
-    JpegGeo g;
-    if (!make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval)) return 0;
-    return carve(g, nullptr, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS).bytes;
+    return tables_workspace_size(n, h, w, hs, vs, 3, restart_interval);
 }
 
 size_t nimg_jpeg_encode_tables_workspace_bytes(int n, int h, int w, int hs, int vs) {
@@ -247,23 +298,8 @@ size_t nimg_jpeg_encode_tables_workspace_bytes(int n, int h, int w, int hs, int 
 int nimg_jpeg_encode_tables_restart(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, const uint8_t* tables,
                                     uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    JpegGeo g;
-    if (!coef || !tables || !out || !lengths || !status || !workspace || !make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval))
-        return NIMG_ERR_ARG;
-    const Workspace ws = carve(g, workspace, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS);
-    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((g.SB + 255) / 256), (unsigned)n);
-    hipLaunchKernelGGL(jpeg_derive_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, tables, ws.codes, status, n);
-    NIMG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_bitlen_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, ws.off, status, g);
-    NIMG_CHECK_LAUNCH();
-    int rc = nimg_internal_jpeg_offsets(ws.off, ws.total, ws.raw, g, ws.raw_words, st);
-    if (rc != NIMG_OK) return rc;
-    hipLaunchKernelGGL(jpeg_emit_tables_kernel, grid, dim3(256), 0, st, coef, (const uint32_t*)ws.codes, (const uint32_t*)ws.off,
-                       (const uint32_t*)status, ws.raw, g, ws.raw_words);
-    NIMG_CHECK_LAUNCH();
-    return nimg_internal_jpeg_pack(ws.raw, ws.total, ws.off, lengths, ws.dst, out, out_capacity, g, ws.raw_words, st);
+    return encode_tables_launch(coef, n, h, w, hs, vs, 3, restart_interval, tables, out, out_capacity, lengths, status, workspace,
+                                workspace_bytes, stream);
 }
 
 int nimg_jpeg_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint8_t* tables, uint8_t* out,

@@ -16,16 +16,18 @@ namespace {
 
 // jpegc.h's table source for the caller's tables: qtabs[item][component][64], natural order, in global memory.  An entry outside
 // 1..255 is clamped where it is used, so no thread divides by zero, and the thread of the item's first block, which looks at all
-// 192 entries of the item, raises *err.
+// entries of the item - 192, or the 64 of a grey-scale file's one table (NC = 1) -, raises *err.
+template <int NC>
 struct DeviceTables {
     const uint16_t* qtabs;
     int* err;
     int n_src;
     __device__ __forceinline__ const uint16_t* table(const JpegGeo& g, long t, int item, int comp) const {
-        const uint16_t* q = qtabs + (size_t)item * 192;
+        constexpr int entries = 64 * NC;
+        const uint16_t* q = qtabs + (size_t)item * entries;
         if (t == (long)item * g.NB) {
             bool bad = false;
-            for (int k = 0; k < 192; ++k) bad |= q[k] < 1 || q[k] > 255;
+            for (int k = 0; k < entries; ++k) bad |= q[k] < 1 || q[k] > 255;
             if (bad) atomicOr(err, 1);
         }
         return q + comp * 64;
@@ -45,14 +47,11 @@ __global__ void __launch_bounds__(256) jpeg_tables_from_float_kernel(const float
     if (st) atomicOr(status + s, st);
 }
 
-}  // namespace
-
-extern "C" {
-
-int nimg_jpeg_transform_tables(const void* x, int is_u8, int n_src, int h, int w, int hs, int vs, const uint16_t* qtabs, int n_items,
-                               int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream) {
+// the launcher of the transform with the caller's tables, for three components (nc = 3) and for one (nc = 1, section 4p)
+int transform_tables_launch(const void* x, int is_u8, int n_src, int h, int w, int hs, int vs, int nc, const uint16_t* qtabs, int n_items,
+                            int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream) {
     JpegGeo g, gs;
-    if (!x || !coef || !qtabs || !err || !workspace || !make_geo(&gs, n_src, h, w, hs, vs) || !make_geo(&g, n_items, h, w, hs, vs))
+    if (!x || !coef || !qtabs || !err || !workspace || !make_geo(&gs, n_src, h, w, hs, vs, nc) || !make_geo(&g, n_items, h, w, hs, vs, nc))
         return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
@@ -60,17 +59,38 @@ int nimg_jpeg_transform_tables(const void* x, int is_u8, int n_src, int h, int w
     if (!grid_ok(blocks, 256)) return NIMG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)((blocks + 255) / 256);
-    const DeviceTables tabs{qtabs, err, n_src};
-    if (is_u8) {
-        hipLaunchKernelGGL((jpeg_transform_kernel<true, DeviceTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, (const uint32_t*)ws.flag);
-    } else {
+    const uint32_t* flag = ws.flag;
+    if (!is_u8) {
         // one flag per call, as in nimg_jpeg_transform: over the source images, whatever tables they are coded with
-        const int rc = nimg_internal_jpeg_above_one((const float*)x, (long)n_src * h * w * 3, ws.flag, st);
+        const int rc = nimg_internal_jpeg_above_one((const float*)x, (long)n_src * h * w * nc, ws.flag, st);
         if (rc != NIMG_OK) return rc;
-        hipLaunchKernelGGL((jpeg_transform_kernel<false, DeviceTables>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, (const uint32_t*)ws.flag);
+    }
+    if (nc == 1) {
+        const DeviceTables<1> tabs{qtabs, err, n_src};
+        if (is_u8) hipLaunchKernelGGL((jpeg_transform_kernel<true, DeviceTables<1>, true>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
+        else hipLaunchKernelGGL((jpeg_transform_kernel<false, DeviceTables<1>, true>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
+    } else {
+        const DeviceTables<3> tabs{qtabs, err, n_src};
+        if (is_u8) hipLaunchKernelGGL((jpeg_transform_kernel<true, DeviceTables<3>>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
+        else hipLaunchKernelGGL((jpeg_transform_kernel<false, DeviceTables<3>>), dim3(grid), dim3(256), 0, st, x, coef, g, tabs, flag);
     }
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nimg_jpeg_transform_tables(const void* x, int is_u8, int n_src, int h, int w, int hs, int vs, const uint16_t* qtabs, int n_items,
+                               int16_t* coef, int* err, void* workspace, size_t workspace_bytes, void* stream) {
+    return transform_tables_launch(x, is_u8, n_src, h, w, hs, vs, 3, qtabs, n_items, coef, err, workspace, workspace_bytes, stream);
+}
+
+int nimg_jpeg_grey_transform_tables(const void* x, int is_u8, int n_src, int h, int w, const uint16_t* qtabs, int n_items, int16_t* coef,
+                                    int* err, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_src == 0 && n_items == 0) return NIMG_OK;
+    return transform_tables_launch(x, is_u8, n_src, h, w, 1, 1, 1, qtabs, n_items, coef, err, workspace, workspace_bytes, stream);
 }
 
 int nimg_jpeg_tables_from_float(const float* t, int n_sets, int n_tabs, uint16_t* qtabs, uint32_t* status, void* stream) {

@@ -96,7 +96,7 @@ JPEGD_HD inline int jpegd_symbol(const JpegdTable& t, uint32_t window, int& len)
 // scan-order block b -> the offset (in blocks) of its coefficients in the image's [Y | Cb | Cr][row][col] tensor, -1 for a dummy
 // block; comp = its component
 JPEGD_HD inline long jpegd_place(const JpegGeo& g, uint32_t b, int& comp) {
-    const int mcu = (int)(b / (uint32_t)g.per), k = (int)(b - (uint32_t)mcu * (uint32_t)g.per), ny = g.per - 2;
+    const int mcu = (int)(b / (uint32_t)g.per), k = (int)(b - (uint32_t)mcu * (uint32_t)g.per), ny = g.ny;
     if (k >= ny) {                                     // the chroma grid is the MCU grid
         comp = k - ny + 1;
         return (long)g.nbY + (long)(comp - 1) * g.nbC + mcu;
@@ -124,7 +124,7 @@ JPEGD_HD inline void jpegd_run_interval(const uint32_t* bits, uint32_t nwords, u
     if (p == JPEGD_INVALID) return;
     int m = (int)(s.mz >> 8), z = (int)(s.mz & 255u);
     if (m >= g.per || z > 63) { s.p = JPEGD_INVALID; s.mz = 0; return; }        // never a state this function left
-    const int ny = g.per - 2;
+    const int ny = g.ny;
     uint32_t cur = block - (z ? 1u : 0u);              // WRITE: the block in progress, or the one the next DC code begins
     int16_t* dst = nullptr;                            // WRITE: the block in progress, if it is real
     if (WRITE && z) {

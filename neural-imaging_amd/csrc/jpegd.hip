@@ -33,7 +33,7 @@ constexpr uint64_t ECD_MAX = (1ull << 28) - 1;        // bytes of one segment: b
 struct DLayout {
     uint32_t* total_bits;        // [n] bits of an image's un-stuffed stream
     uint32_t* nsub;              // [n] its subsequences (0: the image is not decoded)
-    JpegdTable* tabs;            // [n][6]
+    JpegdTable* tabs;            // [n][2 nc]: six, or the two of a grey-scale file
     int32_t* dcdiff;             // [n][SB] DC differences in scan order
     uint32_t* raw;               // un-stuffed streams; image i from word (ecd_off[i] >> 2) + 2 i, (len + 3) / 4 + 1 words
     JpegdState* exit;            // exit states; image i from slot 8 ecd_off[i] / subseq_bits + i
@@ -53,7 +53,7 @@ DLayout carve_d(const JpegGeo& g, uint64_t ecd_bytes, uint32_t sb, void* base) {
     uint8_t* p = (uint8_t*)base;
     d.total_bits = (uint32_t*)p; p += align256((size_t)g.n * 4);
     d.nsub = (uint32_t*)p; p += align256((size_t)g.n * 4);
-    d.tabs = (JpegdTable*)p; p += align256((size_t)g.n * 6 * sizeof(JpegdTable));
+    d.tabs = (JpegdTable*)p; p += align256((size_t)g.n * 2 * g.nc * sizeof(JpegdTable));
     d.dcdiff = (int32_t*)p; p += align256((size_t)g.n * g.SB * 4);
     d.raw_words = (size_t)(ecd_bytes / 4) + 2 * (size_t)g.n + 2;
     d.raw = (uint32_t*)p; p += align256(d.raw_words * 4);
@@ -110,17 +110,18 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DL
         }
         return;
     }
-    if (tid < 6 && !jpegd_build_table(a.huffman + ((size_t)img * 6 + tid) * JPEGD_DHT_BYTES, d.tabs + (size_t)img * 6 + tid))
+    const int nt = 2 * a.g.nc;
+    if (tid < nt && !jpegd_build_table(a.huffman + ((size_t)img * nt + tid) * JPEGD_DHT_BYTES, d.tabs + (size_t)img * nt + tid))
         atomicOr(a.status + img, JPEGD_ST_TABLE);
     jpegd_prepare_segment<RST>(a.ecd + o0, (uint32_t)(o1 - o0), (uint8_t*)(d.raw + raw_start(o0, img)), a.K, a.sb, ibit, sub0, a.status + img,
                                d.total_bits + img, d.nsub + img, RST ? d.maxsub + img : nullptr);
 }
 
-// the six tables of an image into LDS
-__device__ __forceinline__ void load_tables(JpegdTable* dst, const JpegdTable* src, int threads) {
+// the `count` tables of an image into LDS
+__device__ __forceinline__ void load_tables(JpegdTable* dst, const JpegdTable* src, int count, int threads) {
     const uint32_t* s = (const uint32_t*)src;
     uint32_t* t = (uint32_t*)dst;
-    for (int k = threadIdx.x; k < (int)(6 * sizeof(JpegdTable) / 4); k += threads) t[k] = s[k];
+    for (int k = threadIdx.x; k < (int)(count * sizeof(JpegdTable) / 4); k += threads) t[k] = s[k];
     __syncthreads();
 }
 
@@ -131,7 +132,7 @@ __global__ void __launch_bounds__(DEC_THREADS) jpegd_decode_kernel(DArgs a, DLay
     const int img = blockIdx.y;
     const uint32_t S = d.nsub[img];
     if (blockIdx.x * DEC_THREADS >= S) return;           // uniform
-    load_tables(tabs, d.tabs + (size_t)img * 6, DEC_THREADS);
+    load_tables(tabs, d.tabs + (size_t)img * 2 * a.g.nc, 2 * a.g.nc, DEC_THREADS);
     const uint64_t o0 = a.off[img];
     const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
     const uint32_t* bits = d.raw + raw_start(o0, img);
@@ -175,7 +176,7 @@ __global__ void __launch_bounds__(SYNC_THREADS) jpegd_sync_kernel(DArgs a, DLayo
         if (tid == 0 && a.rounds) a.rounds[img] = 0;
         return;
     }
-    load_tables(tabs, d.tabs + (size_t)img * 6, SYNC_THREADS);
+    load_tables(tabs, d.tabs + (size_t)img * 2 * a.g.nc, 2 * a.g.nc, SYNC_THREADS);
     const uint64_t o0 = a.off[img];
     const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
     const uint32_t* bits = d.raw + raw_start(o0, img);
@@ -263,7 +264,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout
     __shared__ T wtot[SCAN_THREADS / 64];
     const int comp = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     if (d.nsub[img] == 0) return;
-    const int ny = a.g.per - 2, mcus = a.g.SB / a.g.per, count = comp ? mcus : mcus * ny;
+    const int ny = a.g.ny, mcus = a.g.SB / a.g.per, count = comp ? mcus : mcus * ny;
     const int span = a.g.ri ? (comp ? a.g.ri : a.g.ri * ny) : count;        // the component's blocks in one interval
     const int32_t* diff = d.dcdiff + (size_t)img * a.g.SB;
     int16_t* coef = a.coef + (size_t)img * a.g.NB * 64;
@@ -290,33 +291,27 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout
 // jpegc.h's table source for the tables of each file: qtabs[image][component][64], natural order, in global memory
 struct FileTables {
     const uint16_t* qtabs;
-    __device__ __forceinline__ const uint16_t* table(const JpegGeo&, long, int img, int comp) const { return qtabs + ((size_t)img * 3 + comp) * 64; }
+    __device__ __forceinline__ const uint16_t* table(const JpegGeo& g, long, int img, int comp) const {
+        return qtabs + ((size_t)img * g.nc + comp) * 64;
+    }
 };
 
-}  // namespace
-
-extern "C" {
-
-size_t nimg_jpeg_decode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, size_t ecd_bytes,
-                                                int subseq_bits) {
+// ---- the launchers, for files of three components (nc = 3) and of one (nc = 1, section 4p) ----------------------------------------
+size_t decode_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval, size_t ecd_bytes, int subseq_bits) {
     JpegGeo g;
     uint32_t sb;
-    if (!make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb) ||
+    if (!make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb) ||
         ecd_bytes > (size_t)n * ECD_MAX)
         return 0;
     return carve_d(g, ecd_bytes, sb, nullptr).bytes;
 }
 
-size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, size_t ecd_bytes, int subseq_bits) {
-    return nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, 0, ecd_bytes, subseq_bits);
-}
-
-int nimg_jpeg_decode_restart(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
-                             int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
-                             size_t workspace_bytes, void* stream) {
+int decode_launch(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs, int nc,
+                  int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
+                  size_t workspace_bytes, void* stream) {
     JpegGeo g;
     uint32_t sb;
-    if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs) ||
+    if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs, nc) ||
         !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb))
         return NIMG_ERR_ARG;
     // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
@@ -352,10 +347,63 @@ int nimg_jpeg_decode_restart(const uint8_t* ecd, const uint64_t* ecd_off, const 
     if (rst) hipLaunchKernelGGL((jpegd_decode_kernel<true, true>), dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
     else hipLaunchKernelGGL((jpegd_decode_kernel<true, false>), dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
-    if (rst) hipLaunchKernelGGL(jpegd_dc_kernel<DcSum>, dim3(3, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
-    else hipLaunchKernelGGL(jpegd_dc_kernel<int>, dim3(3, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    if (rst) hipLaunchKernelGGL(jpegd_dc_kernel<DcSum>, dim3((unsigned)nc, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
+    else hipLaunchKernelGGL(jpegd_dc_kernel<int>, dim3((unsigned)nc, (unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
+}
+
+int reconstruct_tables_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, const uint16_t* qtabs, void* y, int out_u8,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    JpegGeo g;
+    if (!coef || !y || !qtabs || !workspace || !make_geo(&g, n, h, w, hs, vs, nc)) return NIMG_ERR_ARG;
+    const Workspace ws = carve(g, workspace);
+    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
+    const long blocks = (long)n * g.NB, pixels = (long)n * h * w;
+    if (!grid_ok(blocks, 256) || !grid_ok(pixels, 256)) return NIMG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(jpeg_idct_kernel<FileTables>, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g,
+                       FileTables{qtabs});
+    NIMG_CHECK_LAUNCH();
+    return nimg_internal_jpeg_colour(ws.planes, y, out_u8 != 0, g, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nimg_jpeg_decode_restart_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, size_t ecd_bytes,
+                                                int subseq_bits) {
+    return decode_workspace_size(n, h, w, hs, vs, 3, restart_interval, ecd_bytes, subseq_bits);
+}
+
+size_t nimg_jpeg_decode_workspace_bytes(int n, int h, int w, int hs, int vs, size_t ecd_bytes, int subseq_bits) {
+    return decode_workspace_size(n, h, w, hs, vs, 3, 0, ecd_bytes, subseq_bits);
+}
+
+int nimg_jpeg_decode_restart(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                             int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    return decode_launch(ecd, ecd_off, huffman, n, h, w, hs, vs, 3, restart_interval, subseq_bits, coef, status, rounds, workspace,
+                         workspace_bytes, stream);
+}
+
+size_t nimg_jpeg_grey_decode_workspace_bytes(int n, int h, int w, int restart_interval, size_t ecd_bytes, int subseq_bits) {
+    return decode_workspace_size(n, h, w, 1, 1, 1, restart_interval, ecd_bytes, subseq_bits);
+}
+
+int nimg_jpeg_grey_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int restart_interval,
+                          int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    if (n == 0) return NIMG_OK;
+    return decode_launch(ecd, ecd_off, huffman, n, h, w, 1, 1, 1, restart_interval, subseq_bits, coef, status, rounds, workspace,
+                         workspace_bytes, stream);
+}
+
+int nimg_jpeg_grey_reconstruct_tables(const int16_t* coef, int n, int h, int w, const uint16_t* qtabs, void* y, int out_u8, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    if (n == 0) return NIMG_OK;
+    return reconstruct_tables_launch(coef, n, h, w, 1, 1, 1, qtabs, y, out_u8, workspace, workspace_bytes, stream);
 }
 
 int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
@@ -367,17 +415,7 @@ int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t*
 
 int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    JpegGeo g;
-    if (!coef || !y || !qtabs || !workspace || !make_geo(&g, n, h, w, hs, vs)) return NIMG_ERR_ARG;
-    const Workspace ws = carve(g, workspace);
-    if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
-    const long blocks = (long)n * g.NB, pixels = (long)n * h * w;
-    if (!grid_ok(blocks, 256) || !grid_ok(pixels, 256)) return NIMG_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(jpeg_idct_kernel<FileTables>, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, coef, ws.planes, g,
-                       FileTables{qtabs});
-    NIMG_CHECK_LAUNCH();
-    return nimg_internal_jpeg_colour(ws.planes, y, out_u8 != 0, g, st);
+    return reconstruct_tables_launch(coef, n, h, w, hs, vs, 3, qtabs, y, out_u8, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

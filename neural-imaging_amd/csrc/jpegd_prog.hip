@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(FIRST_THREADS) jpegd_prog_first_kernel(PArgs a
     if (sc.ss == 0) {
         // DC: per component the running sum of its differences in scan order, then every block's sum since its interval began
         __syncthreads();
-        const int ny = cg.per - 2, mcus = cg.SB / cg.per;
+        const int ny = cg.ny, mcus = cg.SB / cg.per;
         for (int comp = 0; comp < 3; ++comp) {
             if (!(sc.mask >> comp & 1)) continue;
             const int count = sc.mask != 7 ? cg.SB : (comp ? mcus : mcus * ny);
@@ -364,9 +364,9 @@ __global__ void __launch_bounds__(64) jpegd_prog_ac_refine_kernel(PArgs a, PLayo
 }
 
 // the script of a call, checked: the rules of jpegdprog.h, and the levels the caller passes are the ones they give
-bool take_script(const int32_t* script, int n_scans, PScript* out, int* top) {
+bool take_script(const int32_t* script, int n_scans, int nc, PScript* out, int* top) {
     int32_t levels[JPEGDPROG_SCANS_MAX];
-    if (!script || !jpegdprog_check_script(script, n_scans, levels)) return false;
+    if (!script || !jpegdprog_check_script(script, n_scans, levels, nc)) return false;
     out->n_scans = n_scans;
     *top = 0;
     for (int s = 0; s < n_scans; ++s) {
@@ -378,29 +378,26 @@ bool take_script(const int32_t* script, int n_scans, PScript* out, int* top) {
     return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t nimg_jpeg_decode_progressive_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, int n_scans, size_t ecd_bytes,
-                                                    int subseq_bits) {
+// ---- the launchers, for frames of three components (nc = 3) and of one (nc = 1, section 4p) ---------------------------------------
+size_t progressive_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval, int n_scans, size_t ecd_bytes,
+                                  int subseq_bits) {
     JpegGeo g;
     uint32_t sb;
-    if (!make_geo(&g, n, h, w, hs, vs) || !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || n_scans < 1 ||
+    if (!make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || n_scans < 1 ||
         n_scans > JPEGDPROG_SCANS_MAX || ecd_bytes > (size_t)n * n_scans * PROG_ECD_MAX)
         return 0;
     return carve_p(g, n_scans, ecd_bytes, sb, nullptr).bytes;
 }
 
-int nimg_jpeg_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans, const uint8_t* huffman, int n,
-                                 int h, int w, int hs, int vs, int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status,
-                                 uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream) {
+int progressive_launch(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans, const uint8_t* huffman, int n, int h,
+                       int w, int hs, int vs, int nc, int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status,
+                       uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream) {
     JpegGeo g;
     uint32_t sb;
     PArgs a;
     int top;
-    if (!ecd || !ecd_off || !huffman || !coef || !status || !rounds || !workspace || !make_geo(&g, n, h, w, hs, vs) ||
-        !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || !take_script(script, n_scans, &a.script, &top))
+    if (!ecd || !ecd_off || !huffman || !coef || !status || !rounds || !workspace || !make_geo(&g, n, h, w, hs, vs, nc) ||
+        !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || !take_script(script, n_scans, nc, &a.script, &top))
         return NIMG_ERR_ARG;
     // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
     if (carve_p(g, n_scans, 0, sb, workspace).bytes > workspace_bytes) return NIMG_ERR_ARG;
@@ -445,6 +442,35 @@ int nimg_jpeg_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, co
         }
     }
     return NIMG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nimg_jpeg_decode_progressive_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, int n_scans, size_t ecd_bytes,
+                                                    int subseq_bits) {
+    return progressive_workspace_size(n, h, w, hs, vs, 3, restart_interval, n_scans, ecd_bytes, subseq_bits);
+}
+
+int nimg_jpeg_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans, const uint8_t* huffman, int n,
+                                 int h, int w, int hs, int vs, int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status,
+                                 uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream) {
+    return progressive_launch(ecd, ecd_off, script, n_scans, huffman, n, h, w, hs, vs, 3, restart_interval, subseq_bits, coef, status, rounds,
+                              workspace, workspace_bytes, stream);
+}
+
+size_t nimg_jpeg_grey_decode_progressive_workspace_bytes(int n, int h, int w, int restart_interval, int n_scans, size_t ecd_bytes,
+                                                         int subseq_bits) {
+    return progressive_workspace_size(n, h, w, 1, 1, 1, restart_interval, n_scans, ecd_bytes, subseq_bits);
+}
+
+int nimg_jpeg_grey_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans, const uint8_t* huffman,
+                                      int n, int h, int w, int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status,
+                                      uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n == 0) return NIMG_OK;
+    return progressive_launch(ecd, ecd_off, script, n_scans, huffman, n, h, w, 1, 1, 1, restart_interval, subseq_bits, coef, status, rounds,
+                              workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

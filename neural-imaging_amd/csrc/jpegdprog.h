@@ -30,8 +30,9 @@ JPEGD_HD inline bool jpegdprog_first(const JpegdProgScan& sc) { return sc.ah == 
 
 // The rules of a script: a DC scan (Ss = Se = 0) holds one component or all three, an AC scan (1 <= Ss <= Se <= 63) exactly one; a
 // coefficient's first scan has Ah = 0, each later one Ah = the Al before and Al = Ah - 1; a component's DC first scan precedes its AC
-// scans; every coefficient of every component reaches Al = 0.  levels (may be null) takes the level of every scan.
-JPEGD_HD inline bool jpegdprog_check_script(const int32_t* script, int n_scans, int32_t* levels) {
+// scans; every coefficient of every component reaches Al = 0.  levels (may be null) takes the level of every scan.  A frame of one
+// component (nc = 1, a grey-scale file) has scans of that component alone: every mask is 1.
+JPEGD_HD inline bool jpegdprog_check_script(const int32_t* script, int n_scans, int32_t* levels, int nc = 3) {
     if (n_scans < 1 || n_scans > JPEGDPROG_SCANS_MAX) return false;
     int8_t al_of[3][64];
     int32_t lev[JPEGDPROG_SCANS_MAX];
@@ -41,6 +42,7 @@ JPEGD_HD inline bool jpegdprog_check_script(const int32_t* script, int n_scans, 
         const int32_t* q = script + 6 * s;
         const int mask = q[0], ss = q[1], se = q[2], ah = q[3], al = q[4];
         if (mask != 7 && mask != 1 && mask != 2 && mask != 4) return false;
+        if (nc == 1 && mask != 1) return false;
         if (ss < 0 || se > 63 || ss > se || (ss == 0 && se != 0) || (ss > 0 && mask == 7)) return false;
         if (ah < 0 || ah > 13 || al < 0 || al > 13) return false;
         for (int c = 0; c < 3; ++c) {
@@ -59,7 +61,7 @@ JPEGD_HD inline bool jpegdprog_check_script(const int32_t* script, int n_scans, 
         lev[s] = l + 1;
         if (levels) levels[s] = l + 1;
     }
-    for (int c = 0; c < 3; ++c)
+    for (int c = 0; c < nc; ++c)
         for (int k = 0; k < 64; ++k)
             if (al_of[c][k] != 0) return false;
     return true;
@@ -118,7 +120,7 @@ JPEGD_HD inline void jpegdprog_run_first(const uint32_t* bits, uint32_t nwords, 
     if (m >= per || (dc ? k != 0 : (k < sc.ss || k > sc.se))) { s.p = JPEGD_INVALID; s.mz = 0; return; }        // never a state left here
     uint32_t cur = block;
     if (WRITE && (cur < block_begin || cur > block_end)) return;
-    const int ny = per - 2;
+    const int ny = g.ny;
     uint32_t fail = 0;
     while (p < limit) {
         if (WRITE && cur >= block_end) break;

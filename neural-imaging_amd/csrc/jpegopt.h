@@ -49,7 +49,7 @@ JPEGOPT_HD inline int jpegopt_y_dc(const int16_t* cy, const JpegGeo& g, int mr, 
 // component in a restart interval (g.ri MCUs, section 4i) is predicted from 0, like the first of the image.
 template <typename Sink>
 JPEGOPT_HD inline void jpegopt_walk_block(const int16_t* ci, const JpegGeo& g, int s, Sink& sink) {
-    const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.per - 2;
+    const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.ny;
     const int16_t* blk;
     int dc, pred, t;
     bool real = true;
@@ -182,13 +182,21 @@ JPEGOPT_HD inline bool jpegopt_derive(const uint8_t* dht, uint32_t* codes, int n
     return ok;
 }
 
-// the four tables of an image (DHT-id order 00 10 01 11) -> its JPEGOPT_CODE_WORDS code words; false = one of them is refused, and
-// all code words are zero
-JPEGOPT_HD inline bool jpegopt_derive_image(const uint8_t* tables, uint32_t* codes) {
+// the tables an image's coder and histograms have: 00 10 01 11, or 00 10 alone in a grey-scale file
+JPEGOPT_HD inline int jpegopt_tables(const JpegGeo& g) { return g.nc == 1 ? 2 : 4; }
+
+// the n_tables (4, or 2 of a grey-scale file) tables of an image (DHT-id order 00 10 01 11) -> its JPEGOPT_CODE_WORDS code words, those
+// of a table it has not all zero; false = one of them is refused, and all code words are zero
+JPEGOPT_HD inline bool jpegopt_derive_image(const uint8_t* tables, uint32_t* codes, int n_tables = 4) {
     bool ok = jpegopt_derive(tables, codes, 16);
-    ok = jpegopt_derive(tables + 2 * JPEGOPT_TABLE_BYTES, codes + 16, 16) && ok;
     ok = jpegopt_derive(tables + JPEGOPT_TABLE_BYTES, codes + 32, 256) && ok;
-    ok = jpegopt_derive(tables + 3 * JPEGOPT_TABLE_BYTES, codes + 288, 256) && ok;
+    if (n_tables == 4) {
+        ok = jpegopt_derive(tables + 2 * JPEGOPT_TABLE_BYTES, codes + 16, 16) && ok;
+        ok = jpegopt_derive(tables + 3 * JPEGOPT_TABLE_BYTES, codes + 288, 256) && ok;
+    } else {
+        for (int i = 0; i < 16; ++i) codes[16 + i] = 0;
+        for (int i = 0; i < 256; ++i) codes[288 + i] = 0;
+    }
     if (!ok)
         for (int i = 0; i < JPEGOPT_CODE_WORDS; ++i) codes[i] = 0;
     return ok;

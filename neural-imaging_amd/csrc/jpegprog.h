@@ -66,7 +66,7 @@ JPEGPROG_HD inline JpegGeo jpegprog_class_geo(const JpegGeo& g, int cls) {
     if (cls != 0) {
         c.my = cls == 1 ? g.bhY : g.bhC;
         c.mx = cls == 1 ? g.bwY : g.bwC;
-        c.per = 1;
+        c.per = 1; c.ny = 1;
         c.SB = c.my * c.mx;
     }
     return c;
@@ -94,7 +94,7 @@ JPEGPROG_HD inline int jpegprog_clamp_ac(int v) { return v < -1023 ? -1023 : (v 
 // the component's block before it, 0 at the start of a restart interval; table 0 for Y, 1 for chroma.  Refine scan: one bit.
 template <typename Sink>
 JPEGPROG_HD inline void jpegprog_walk_dc(const int16_t* ci, const JpegGeo& g, int s, bool refine, int al, Sink& sink) {
-    const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.per - 2;
+    const int m = s / g.per, k = s - m * g.per, mr = m / g.mx, mc = m - mr * g.mx, ny = g.ny;
     int dc, pred = 0;
     bool real, have = true;
     if (k < ny) {

@@ -163,6 +163,9 @@ class JPEG(TFModel):
 
     # forward/backward used by the workflow ----------------------------------------------------------------------
     def forward(self, x, quality=None, training=False, out=None):
+        if x.dim() == 4 and x.shape[3] == 1:
+            raise ValueError('the JPEG model takes (n,h,w,3) batches: grey-scale (one-component) images are coded by '
+                             'compression.jpeg_helpers alone (DESIGN.md section 4p)')
         if self._codec_model is None:
             if training:
                 raise NotImplementedError('the libjpeg codec has no gradient (the reference has none either): train on a '
@@ -298,6 +301,9 @@ class JPEG(TFModel):
         files]) - what the learned tables, or the soft / sin / harmonic codec's, cost in bytes and do to the image once a standard
         encoder holds them.  Forward only: the real codec has no gradient (forward(training=True) of the libjpeg codec says the same)."""
         x = to_device(batch_x, self.device)
+        if tuple(x.shape)[-1:] == (1,):
+            raise ValueError('process_files needs an (n,h,w,3) batch: grey-scale (one-component) images are coded by '
+                             'compression.jpeg_helpers alone (DESIGN.md section 4p)')
         if isinstance(x, torch.Tensor) and x.requires_grad:
             raise NotImplementedError('the real codec has no gradient (the reference has none either): train on a differentiable '
                                       'codec, measure on this one')

@@ -2452,18 +2452,51 @@ def l3ic_decode(data, offsets, lengths, codebook, shape):
 # baseline JPEG codec (compression/jpeg_helpers.py, models/jpeg.py 'libjpeg'; include/nimg.h nimg_jpeg_*)
 JPEG_SUBSAMPLING = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
 JPEG_BLOCK_BITS_MAX = 1658       # DC 9 + 11 bits, 63 x (AC 16 + 10)
+JPEG_GREY = (0, 0)               # the factor form of a grey-scale file: one component, no chroma to sub-sample
 
 
 def jpeg_subsampling(subsampling):
-    """'4:4:4' | '4:2:2' | '4:2:0' -> the luma sampling factors (hs, vs)."""
+    """'4:4:4' | '4:2:2' | '4:2:0' -> the luma sampling factors (hs, vs); 'grey' -> JPEG_GREY, the factors that stand for a file of
+    one component wherever an op takes (hs, vs)."""
+    if subsampling == 'grey':
+        return JPEG_GREY
     if subsampling not in JPEG_SUBSAMPLING:
         raise ValueError('Unsupported chrominance sub-sampling: {} (4:4:4, 4:2:2 or 4:2:0)'.format(subsampling))
     return JPEG_SUBSAMPLING[subsampling]
 
 
+def jpeg_is_grey(hs, vs):
+    return (hs, vs) == JPEG_GREY
+
+
+def jpeg_mcu_blocks(hs, vs):
+    """Blocks of one MCU: the luma blocks and the two chroma blocks; 1 in a grey-scale file, whose scan is not interleaved."""
+    return 1 if jpeg_is_grey(hs, vs) else hs * vs + 2
+
+
+def _jpeg_entry(name, hs, vs, *middle):
+    """(entry point, its geometry arguments) of an operation: the colour entry `name` with (hs, vs), or its grey-scale form
+    nimg_jpeg_grey_* - one per operation, without factors and without a _restart twin - with `middle`, the restart interval 0 of
+    an operation whose colour entry has none."""
+    if not jpeg_is_grey(hs, vs):
+        return name, (hs, vs)
+    if name == 'nimg_jpeg_encode_restart_workspace_bytes':         # one size serves the pixel stages and the Annex K coder
+        return 'nimg_jpeg_grey_workspace_bytes', middle
+    return name.replace('nimg_jpeg_', 'nimg_jpeg_grey_').replace('_restart', ''), middle
+
+
+def _jpeg_colour_only(name, hs, vs):
+    """The ops that have no grey-scale form say so."""
+    if jpeg_is_grey(hs, vs):
+        raise ValueError('{}: grey-scale (one-component) batches are not supported here'.format(name))
+
+
 def jpeg_geometry(h, w, hs, vs):
     """(real blocks per image over Y, Cb, Cr; blocks per image in scan order, dummy blocks included; [(rows, cols)] of the real
-    blocks per component)."""
+    blocks per component).  Grey-scale (JPEG_GREY): one component, and the scan is its real blocks in raster order."""
+    if jpeg_is_grey(hs, vs):
+        rows, cols = -(-h // 8), -(-w // 8)
+        return rows * cols, rows * cols, [(rows, cols)]
     comps = [(-(-h // 8), -(-w // 8))] + [(-(-(-(-h // vs)) // 8), -(-(-(-w // hs)) // 8))] * 2
     scan = -(-h // (8 * vs)) * -(-w // (8 * hs)) * (hs * vs + 2)
     return sum(r * c for r, c in comps), scan, comps
@@ -2485,7 +2518,7 @@ def jpeg_restart_interval(restart_interval):
 def jpeg_restart_markers(h, w, hs, vs, restart_interval):
     """How many restart markers one image carries: one behind every interval but the last."""
     ri = jpeg_restart_interval(restart_interval)
-    return -(-(jpeg_geometry(h, w, hs, vs)[1] // (hs * vs + 2)) // ri) - 1 if ri else 0
+    return -(-(jpeg_geometry(h, w, hs, vs)[1] // jpeg_mcu_blocks(hs, vs)) // ri) - 1 if ri else 0
 
 
 def jpeg_ecd_bound(h, w, hs, vs, restart_interval=0):
@@ -2497,7 +2530,8 @@ def jpeg_ecd_bound(h, w, hs, vs, restart_interval=0):
 def jpeg_workspace_bytes(n, h, w, hs, vs, restart_interval=0):
     """Bytes of workspace the transforms, jpeg_encode and the reconstructions need for n images, 0 = a batch the library does not
     serve.  A restart interval only adds to it, so one workspace of the interval's size serves all three stages of a batch."""
-    return int(_lib.load().nimg_jpeg_encode_restart_workspace_bytes(n, h, w, hs, vs, jpeg_restart_interval(restart_interval)))
+    entry, factors = _jpeg_entry('nimg_jpeg_encode_restart_workspace_bytes', hs, vs)
+    return int(getattr(_lib.load(), entry)(n, h, w, *factors, jpeg_restart_interval(restart_interval)))
 
 
 def _jpeg_workspace(need, batch, device, workspace, name='JPEG workspace', empty_ok=False):
@@ -2515,12 +2549,15 @@ def _jpeg_workspace(need, batch, device, workspace, name='JPEG workspace', empty
 
 
 def _jpeg_batch(n, h, w, hs, vs, kind='JPEG'):
+    if jpeg_is_grey(hs, vs):
+        return '{} batch: n={} h={} w={} grey-scale'.format(kind, n, h, w)
     return '{} batch: n={} h={} w={} sampling {}x{}'.format(kind, n, h, w, hs, vs)
 
 
 def _jpeg_pixel_workspace(n, h, w, hs, vs, device, workspace):
     """The workspace of a transform or a reconstruction: these know no restart interval."""
-    return _jpeg_workspace(_lib.load().nimg_jpeg_workspace_bytes(n, h, w, hs, vs), _jpeg_batch(n, h, w, hs, vs), device, workspace)
+    entry, factors = _jpeg_entry('nimg_jpeg_workspace_bytes', hs, vs, 0)
+    return _jpeg_workspace(getattr(_lib.load(), entry)(n, h, w, *factors), _jpeg_batch(n, h, w, hs, vs), device, workspace)
 
 
 def _jpeg_coef(name, coef, h, w, hs, vs):
@@ -2531,22 +2568,29 @@ def _jpeg_coef(name, coef, h, w, hs, vs):
     return n
 
 
-def _jpeg_rgb(name, x):
-    """The one input check of the transforms."""
+def _jpeg_rgb(name, x, hs=1, vs=1, grey_ok=False):
+    """The one input check of the transforms -> the factors the op goes on with.  Where `grey_ok`, an (n,h,w,1) tensor is a batch of
+    grey-scale images: its factors are JPEG_GREY, given as such or left at (1, 1); a colour batch never has them."""
     _chk(x)
-    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or x.shape[3] != 3:
+    grey = grey_ok and x.dim() == 4 and x.shape[3] == 1
+    if x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4 or (x.shape[3] != 3 and not grey):
         raise RuntimeError('{} needs an (n,h,w,3) float32 or uint8 tensor, got {} {}'.format(name, x.dtype, tuple(x.shape)))
+    if grey and (hs, vs) not in ((1, 1), JPEG_GREY):
+        raise ValueError('{}: a grey-scale batch (n,h,w,1) has no chroma to sub-sample, got the factors {}x{}'.format(name, hs, vs))
+    if not grey and grey_ok and jpeg_is_grey(hs, vs):
+        raise ValueError('{}: grey-scale factors with an (n,h,w,3) batch'.format(name))
+    return JPEG_GREY if grey else (hs, vs)
 
 
 def jpeg_transform(x, quality, hs=1, vs=1, workspace=None):
     """(n,h,w,3) float32 or uint8 -> (n, real blocks, 64) int16 quantised coefficients in zig-zag order, the blocks of an image
-    ordered [Y | Cb | Cr][block row][block col]."""
-    _jpeg_rgb('jpeg_transform', x)
+    ordered [Y | Cb | Cr][block row][block col].  (n,h,w,1): a grey-scale batch, coded with the luma table, one component."""
+    hs, vs = _jpeg_rgb('jpeg_transform', x, hs, vs, grey_ok=True)
     n, h, w, _ = x.shape
     ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, x.device, workspace)
     coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
-    _lib.call('nimg_jpeg_transform', _p(x), int(x.dtype == torch.uint8), n, h, w, hs, vs, int(quality), _p(coef), _p(ws), need,
-              _stream())
+    entry, factors = _jpeg_entry('nimg_jpeg_transform', hs, vs)
+    _lib.call(entry, _p(x), int(x.dtype == torch.uint8), n, h, w, *factors, int(quality), _p(coef), _p(ws), need, _stream())
     return coef
 
 
@@ -2571,8 +2615,10 @@ def _jpeg_encode(name, entry, size, bound, n_tables, per_image, coef, tables, h,
     n = _jpeg_coef(name, coef, h, w, hs, vs)
     if n_tables and (tables.dtype != torch.uint8 or tuple(tables.shape) != (n, n_tables, JPEG_TABLE_BYTES)):
         raise RuntimeError('{}: tables {} {}, ({}, {}, 272) uint8 needed'.format(name, tables.dtype, tuple(tables.shape), n, n_tables))
-    ws, need = _jpeg_workspace(getattr(_lib.load(), size)(n, h, w, hs, vs, ri), _jpeg_batch(n, h, w, hs, vs, kind), coef.device, workspace,
-                               empty_ok=empty_ok and n == 0)
+    entry, factors = _jpeg_entry(entry, hs, vs)
+    size = _jpeg_entry(size, hs, vs)[0]
+    ws, need = _jpeg_workspace(getattr(_lib.load(), size)(n, h, w, *factors, ri), _jpeg_batch(n, h, w, hs, vs, kind), coef.device,
+                               workspace, empty_ok=empty_ok and n == 0)
     if out is None:
         room = n * bound(h, w, hs, vs, ri) if capacity is None else int(capacity)
         out = torch.empty(max(room, 1) if empty_ok else room, dtype=torch.uint8, device=coef.device)
@@ -2580,7 +2626,7 @@ def _jpeg_encode(name, entry, size, bound, n_tables, per_image, coef, tables, h,
     lengths = torch.empty((n,) + per_image, dtype=torch.int32, device=coef.device)
     status = torch.empty(n, dtype=torch.int32, device=coef.device) if n_tables else None
     capacity = out.numel() if capacity is None else int(capacity)
-    _lib.call(entry, _p(coef), n, h, w, hs, vs, ri, *((_p(tables),) if n_tables else ()), _p(out), capacity, _p(lengths),
+    _lib.call(entry, _p(coef), n, h, w, *factors, ri, *((_p(tables),) if n_tables else ()), _p(out), capacity, _p(lengths),
               *((_p(status),) if n_tables else ()), _p(ws), need, _stream())
     return out, lengths, status
 
@@ -2588,6 +2634,7 @@ def _jpeg_encode(name, entry, size, bound, n_tables, per_image, coef, tables, h,
 def jpeg_reconstruct(coef, h, w, quality, hs=1, vs=1, workspace=None, out=None):
     """Coefficients of jpeg_transform -> the (n,h,w,3) float32 image libjpeg decodes from them, in [0, 1]."""
     _chk(coef)
+    _jpeg_colour_only('jpeg_reconstruct', hs, vs)
     n = _jpeg_coef('jpeg_reconstruct', coef, h, w, hs, vs)
     ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
     y = torch.empty((n, h, w, 3), dtype=torch.float32, device=coef.device) if out is None else out
@@ -2617,6 +2664,7 @@ def jpeg_transform_items(x, quality, hs=1, vs=1, workspace=None, err=None):
     """(n_src,h,w,3) float32 or uint8 and one quality per item -> ((n_items, real blocks, 64) int16 coefficients laid out as
     jpeg_transform's, (1,) int32 error flag: non-zero = a quality byte outside 1..100 was clamped).  Item j codes source image
     j % n_src at quality[j]; n_items = len(quality), so a quality-major sweep reads the sources in place."""
+    _jpeg_colour_only('jpeg_transform_items', hs, vs)
     _jpeg_rgb('jpeg_transform_items', x)
     n_src, h, w, _ = x.shape
     n_items = int(quality.numel() if isinstance(quality, torch.Tensor) else np.size(quality))
@@ -2633,6 +2681,7 @@ def jpeg_reconstruct_items(coef, h, w, quality, hs=1, vs=1, workspace=None, out=
     """Coefficients of n_items images and one quality per item -> ((n_items,h,w,3) float32 decoded images, (1,) int32 error flag as
     jpeg_transform_items')."""
     _chk(coef)
+    _jpeg_colour_only('jpeg_reconstruct_items', hs, vs)
     n = _jpeg_coef('jpeg_reconstruct_items', coef, h, w, hs, vs)
     q = jpeg_item_qualities(quality, n, coef.device)
     ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
@@ -2651,7 +2700,8 @@ def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspac
     leaves them, status (n,) int32 - 0 = decoded, the bits are include/nimg.h's - and rounds (n,) int32, the synchronisation rounds
     each image took).  ecd: uint8 device tensor, the segments back to back as they stand in the files; ecd_off: (n + 1,) int64
     offsets into it; huffman: (n, 6, 272) uint8, per image the tables Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC as 16 counts + 256
-    symbols.  subseq_bits: bits one thread decodes (a multiple of 32, 0 = the default; at least the stream = a sequential decode).
+    symbols - (n, 2, 272), DC and AC, for grey-scale files (hs, vs = JPEG_GREY).  subseq_bits: bits one thread decodes (a multiple
+    of 32, 0 = the default; at least the stream = a sequential decode).
     restart_interval: the DRI value the files share (nimg_jpeg_decode_restart) - their markers FF D0 .. D7 are taken out and checked
     (status bit 512), and every interval is decoded from its own known start; 0 = files without markers."""
     _chk(ecd)
@@ -2661,18 +2711,21 @@ def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspac
     if ecd.dtype != torch.uint8 or ecd_off.dtype != torch.int64 or n < 1:
         raise RuntimeError('jpeg_decode: uint8 segments and (n + 1,) int64 offsets needed, got {} and {} {}'.format(
             ecd.dtype, ecd_off.dtype, tuple(ecd_off.shape)))
-    if huffman.dtype != torch.uint8 or tuple(huffman.shape) != (n, 6, 272):
-        raise RuntimeError('jpeg_decode: Huffman tables {} {}, ({}, 6, 272) uint8 needed'.format(huffman.dtype, tuple(huffman.shape), n))
+    n_tables = 2 if jpeg_is_grey(hs, vs) else 6
+    if huffman.dtype != torch.uint8 or tuple(huffman.shape) != (n, n_tables, 272):
+        raise RuntimeError('jpeg_decode: Huffman tables {} {}, ({}, {}, 272) uint8 needed'.format(huffman.dtype, tuple(huffman.shape), n,
+                                                                                                  n_tables))
     subseq_bits = int(subseq_bits)
     ri = jpeg_restart_interval(restart_interval)
-    workspace, _ = _jpeg_workspace(_lib.load().nimg_jpeg_decode_restart_workspace_bytes(n, h, w, hs, vs, ri, ecd.numel(), subseq_bits),
+    entry, factors = _jpeg_entry('nimg_jpeg_decode_restart', hs, vs)
+    workspace, _ = _jpeg_workspace(getattr(_lib.load(), entry + '_workspace_bytes')(n, h, w, *factors, ri, ecd.numel(), subseq_bits),
                                    '{} subseq_bits={}'.format(_jpeg_batch(n, h, w, hs, vs), subseq_bits), ecd.device, workspace,
                                    name='JPEG decode workspace')
     coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
     status = torch.empty(n, dtype=torch.int32, device=ecd.device)
     rounds = torch.empty(n, dtype=torch.int32, device=ecd.device)
-    _lib.call('nimg_jpeg_decode_restart', _p(ecd), _p(ecd_off), _p(huffman), n, h, w, hs, vs, ri, subseq_bits, _p(coef), _p(status),
-              _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    _lib.call(entry, _p(ecd), _p(ecd_off), _p(huffman), n, h, w, *factors, ri, subseq_bits, _p(coef), _p(status), _p(rounds),
+              _p(workspace), workspace.numel() * workspace.element_size(), _stream())
     return coef, status, rounds
 
 
@@ -2686,7 +2739,8 @@ def jpeg_decode_progressive(ecd, ecd_off, huffman, script, h, w, hs=1, vs=1, sub
     every first scan).  ecd: uint8 device tensor, the segments back to back, image-major; ecd_off: (n * n_scans + 1,) int64 offsets
     into it; huffman: (n, n_scans, 3, 272) uint8, slot c = the table of the scan's c-th component, zero where it has none; script:
     (n_scans, 6) int32 on the host - component mask, Ss, Se, Ah, Al, level.  A script that breaks the rules of the header comment is
-    refused by the library (NIMG_ERR_ARG) before anything is launched."""
+    refused by the library (NIMG_ERR_ARG) before anything is launched.  Grey-scale files (hs, vs = JPEG_GREY): every scan's mask is 1,
+    and slot 0 of its tables alone is read."""
     _chk(ecd)
     _chk(ecd_off)
     _chk(huffman)
@@ -2703,33 +2757,38 @@ def jpeg_decode_progressive(ecd, ecd_off, huffman, script, h, w, hs=1, vs=1, sub
             huffman.dtype, tuple(huffman.shape), n, n_scans))
     subseq_bits = int(subseq_bits)
     ri = jpeg_restart_interval(restart_interval)
+    entry, factors = _jpeg_entry('nimg_jpeg_decode_progressive', hs, vs)
     workspace, _ = _jpeg_workspace(
-        _lib.load().nimg_jpeg_decode_progressive_workspace_bytes(n, h, w, hs, vs, ri, n_scans, ecd.numel(), subseq_bits),
+        getattr(_lib.load(), entry + '_workspace_bytes')(n, h, w, *factors, ri, n_scans, ecd.numel(), subseq_bits),
         '{} scans={} subseq_bits={}'.format(_jpeg_batch(n, h, w, hs, vs), n_scans, subseq_bits), ecd.device, workspace,
         name='JPEG decode workspace')
     coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
     status = torch.empty(n, dtype=torch.int32, device=ecd.device)
     rounds = torch.empty((n, n_scans), dtype=torch.int32, device=ecd.device)
-    _lib.call('nimg_jpeg_decode_progressive', _p(ecd), _p(ecd_off), script.ctypes.data, n_scans, _p(huffman), n, h, w, hs, vs, ri,
+    _lib.call(entry, _p(ecd), _p(ecd_off), script.ctypes.data, n_scans, _p(huffman), n, h, w, *factors, ri,
               subseq_bits, _p(coef), _p(status), _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
     return coef, status, rounds
 
 
 def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspace=None, out=None):
     """jpeg_reconstruct with the quantisation tables given per image and component: qtabs (n, 3, 64) uint16 (or int16 bit patterns)
-    in natural order.  Returns (n,h,w,3) uint8 - the bytes libjpeg decodes - when out_u8, else float32 = byte / 255."""
+    in natural order.  Returns (n,h,w,3) uint8 - the bytes libjpeg decodes - when out_u8, else float32 = byte / 255.  Grey-scale
+    (hs, vs = JPEG_GREY): qtabs (n, 1, 64) and an (n,h,w,1) image."""
     _chk(coef)
     _chk(qtabs)
     n = _jpeg_coef('jpeg_reconstruct_tables', coef, h, w, hs, vs)
-    if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, 3, 64):
-        raise RuntimeError('jpeg_reconstruct_tables: tables {} {}, ({}, 3, 64) 16-bit integers needed'.format(qtabs.dtype, tuple(qtabs.shape), n))
+    nc = 1 if jpeg_is_grey(hs, vs) else 3
+    if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, nc, 64):
+        raise RuntimeError('jpeg_reconstruct_tables: tables {} {}, ({}, {}, 64) 16-bit integers needed'.format(qtabs.dtype, tuple(qtabs.shape),
+                                                                                                             n, nc))
     ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
     dtype = torch.uint8 if out_u8 else torch.float32
-    y = torch.empty((n, h, w, 3), dtype=dtype, device=coef.device) if out is None else out
+    y = torch.empty((n, h, w, nc), dtype=dtype, device=coef.device) if out is None else out
     _chk(y)
-    if y.dtype != dtype or tuple(y.shape) != (n, h, w, 3):
-        raise RuntimeError('jpeg_reconstruct_tables: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, (n, h, w, 3)))
-    _lib.call('nimg_jpeg_reconstruct_tables', _p(coef), n, h, w, hs, vs, _p(qtabs), _p(y), int(bool(out_u8)), _p(ws), need, _stream())
+    if y.dtype != dtype or tuple(y.shape) != (n, h, w, nc):
+        raise RuntimeError('jpeg_reconstruct_tables: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, (n, h, w, nc)))
+    entry, factors = _jpeg_entry('nimg_jpeg_reconstruct_tables', hs, vs)
+    _lib.call(entry, _p(coef), n, h, w, *factors, _p(qtabs), _p(y), int(bool(out_u8)), _p(ws), need, _stream())
     return y
 
 
@@ -2747,8 +2806,10 @@ def jpeg_ecd_bound_tables(h, w, hs, vs, restart_interval=0):
 
 def jpeg_histogram(coef, h, w, hs=1, vs=1, out=None, *, restart_interval=0):
     """Coefficients of jpeg_transform -> (n, 4, 257) int32: how often jpeg_encode emits each symbol of each table; entry 256 is 0.
-    restart_interval: as jpeg_encode's - the DC differences at the start of an interval are taken from 0."""
-    return _jpeg_histogram('jpeg_histogram', 'nimg_jpeg_histogram_restart', 4, coef, h, w, hs, vs, out, restart_interval)
+    restart_interval: as jpeg_encode's - the DC differences at the start of an interval are taken from 0.  Grey-scale (hs, vs =
+    JPEG_GREY): (n, 2, 257), DC and AC."""
+    return _jpeg_histogram('jpeg_histogram', 'nimg_jpeg_histogram_restart', 2 if jpeg_is_grey(hs, vs) else 4, coef, h, w, hs, vs, out,
+                           restart_interval)
 
 
 def _jpeg_histogram(name, entry, n_tables, coef, h, w, hs, vs, out, restart_interval):
@@ -2760,7 +2821,8 @@ def _jpeg_histogram(name, entry, n_tables, coef, h, w, hs, vs, out, restart_inte
     _chk(hist)
     if hist.dtype != torch.int32 or tuple(hist.shape) != shape:
         raise RuntimeError('{}: output {} {}, int32 {} needed'.format(name, hist.dtype, tuple(hist.shape), shape))
-    _lib.call(entry, _p(coef), shape[0], h, w, hs, vs, ri, _p(hist), _stream())
+    entry, factors = _jpeg_entry(entry, hs, vs)
+    _lib.call(entry, _p(coef), shape[0], h, w, *factors, ri, _p(hist), _stream())
     return hist
 
 
@@ -2781,9 +2843,11 @@ def jpeg_optimal_tables(hist):
 def jpeg_encode_tables(coef, tables, h, w, hs=1, vs=1, out=None, workspace=None, capacity=None, *, restart_interval=0):
     """jpeg_encode with the Huffman tables of each image given: tables (n, 4, 272) uint8 -> (segments back to back (uint8), lengths
     (n,) int32, status (n,) int32: bits 1 = tables that are no prefix code (length 0, or the restart markers alone), 2 = a symbol of
-    the image has no code).  restart_interval: as jpeg_encode's (nimg_jpeg_encode_tables_restart)."""
+    the image has no code).  restart_interval: as jpeg_encode's (nimg_jpeg_encode_tables_restart).  Grey-scale (hs, vs = JPEG_GREY):
+    tables (n, 2, 272), DC and AC."""
     return _jpeg_encode('jpeg_encode_tables', 'nimg_jpeg_encode_tables_restart', 'nimg_jpeg_encode_tables_restart_workspace_bytes',
-                        jpeg_ecd_bound_tables, 4, (), coef, tables, h, w, hs, vs, out, workspace, capacity, restart_interval)
+                        jpeg_ecd_bound_tables, 2 if jpeg_is_grey(hs, vs) else 4, (), coef, tables, h, w, hs, vs, out, workspace, capacity,
+                        restart_interval)
 
 
 # progressive files (DESIGN.md section 4l): ten scans, ten tables per image in the order of the file's DHT segments
@@ -2806,6 +2870,7 @@ def jpeg_progressive_histogram(coef, h, w, hs=1, vs=1, out=None, *, restart_inte
     """Coefficients of jpeg_transform -> (n, 10, 257) int32: how often the progressive coder (jpeg_encode_progressive) emits each
     symbol of each of its ten tables - DC 00, DC 01, then the AC tables of the scans 2, 3, 4, 5, 6, 8, 9, 10 -, the EOBn symbols of
     the end-of-band runs included; entry 256 is 0.  jpeg_optimal_tables on it gives the tables libjpeg writes."""
+    _jpeg_colour_only('jpeg_progressive_histogram', hs, vs)
     return _jpeg_histogram('jpeg_progressive_histogram', 'nimg_jpeg_progressive_histogram', JPEG_PROGRESSIVE_SCANS, coef, h, w, hs, vs, out,
                            restart_interval)
 
@@ -2814,32 +2879,35 @@ def jpeg_encode_progressive(coef, tables, h, w, hs=1, vs=1, out=None, workspace=
     """The ten scans of libjpeg's simple progression with the tables of each image given: tables (n, 10, 272) uint8 -> (the ten
     entropy-coded segments of every image back to back (uint8), lengths (n, 10) int32, status (n,) int32: bits 1 = tables that are no
     prefix code, 2 = a symbol of the image has no code).  Headers, DHT and SOS segments and EOI are the caller's."""
+    _jpeg_colour_only('jpeg_encode_progressive', hs, vs)
     return _jpeg_encode('jpeg_encode_progressive', 'nimg_jpeg_encode_progressive', 'nimg_jpeg_progressive_workspace_bytes',
                         jpeg_progressive_ecd_bound, JPEG_PROGRESSIVE_SCANS, (JPEG_PROGRESSIVE_SCANS,), coef, tables, h, w, hs, vs, out,
                         workspace, capacity, restart_interval, kind='progressive JPEG', empty_ok=True)
 
 
 # any quantisation tables (DESIGN.md section 4h): a table set is (3, 64) uint16 [Y, Cb, Cr] in natural order, one set per item
-def _jpeg_qtabs(qtabs, name):
+def _jpeg_qtabs(qtabs, name, nc=3):
     _chk(qtabs)
-    if qtabs.element_size() != 2 or qtabs.is_floating_point() or qtabs.dim() != 3 or tuple(qtabs.shape[1:]) != (3, 64) or qtabs.shape[0] < 1:
-        raise RuntimeError('{}: tables {} {}, (n_items, 3, 64) 16-bit integers needed'.format(name, qtabs.dtype, tuple(qtabs.shape)))
+    if qtabs.element_size() != 2 or qtabs.is_floating_point() or qtabs.dim() != 3 or tuple(qtabs.shape[1:]) != (nc, 64) or qtabs.shape[0] < 1:
+        raise RuntimeError('{}: tables {} {}, (n_items, {}, 64) 16-bit integers needed'.format(name, qtabs.dtype, tuple(qtabs.shape), nc))
     return qtabs
 
 
 def jpeg_transform_tables(x, qtabs, hs=1, vs=1, workspace=None, err=None):
     """(n_src,h,w,3) float32 or uint8 and one table set per item, qtabs (n_items, 3, 64) uint16 (or int16 bit patterns) in natural order
     on the device -> ((n_items, real blocks, 64) int16 coefficients laid out as jpeg_transform's, (1,) int32 error flag: non-zero = an
-    entry outside 1..255 was clamped).  Item j codes source image j % n_src with qtabs[j]."""
-    _jpeg_rgb('jpeg_transform_tables', x)
-    qtabs = _jpeg_qtabs(qtabs, 'jpeg_transform_tables')
+    entry outside 1..255 was clamped).  Item j codes source image j % n_src with qtabs[j].  (n_src,h,w,1): a grey-scale batch, with
+    its one table per item, qtabs (n_items, 1, 64)."""
+    hs, vs = _jpeg_rgb('jpeg_transform_tables', x, hs, vs, grey_ok=True)
+    qtabs = _jpeg_qtabs(qtabs, 'jpeg_transform_tables', 1 if jpeg_is_grey(hs, vs) else 3)
     n_src, h, w, _ = x.shape
     n_items = qtabs.shape[0]
     ws, need = _jpeg_pixel_workspace(n_items, h, w, hs, vs, x.device, workspace)
     coef = torch.empty((n_items, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=x.device)
     err = torch.zeros((1,), dtype=torch.int32, device=x.device) if err is None else err
-    _lib.call('nimg_jpeg_transform_tables', _p(x), int(x.dtype == torch.uint8), n_src, h, w, hs, vs, _p(qtabs), n_items, _p(coef), _p(err),
-              _p(ws), need, _stream())
+    entry, factors = _jpeg_entry('nimg_jpeg_transform_tables', hs, vs)
+    _lib.call(entry, _p(x), int(x.dtype == torch.uint8), n_src, h, w, *factors, _p(qtabs), n_items, _p(coef), _p(err), _p(ws), need,
+              _stream())
     return coef, err
 
 
