@@ -1017,6 +1017,25 @@ int nimg_jpeg_grey_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_of
                                       int n, int h, int w, int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status,
                                       uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scaled reconstruction: nimg_jpeg_reconstruct_tables at libjpeg's scale_num / scale_denom = 1 / scale, scale
+ * 1, 2, 4 or 8 - the image libjpeg (Pillow's draft()) decodes from the same file at that scale, byte for byte: per component the
+ * reduced inverse DCT of jidctred.c at the block size jdmaster.c gives it, for 4:2:2 the 2:1 up-sampling jdsample.c then chooses, the
+ * unchanged colour conversion.
+ *   y              (n, ceil(h / scale), ceil(w / scale), 3) - grey: (.., .., 1) -, uint8 if out_u8, else float32 = byte / 255
+ *   coef, qtabs    as nimg_jpeg_reconstruct_tables (nimg_jpeg_grey_reconstruct_tables)
+ *   _grey          the one-component form, without sampling factors, as the nimg_jpeg_grey_* entries are to theirs; the nimg_jpeg_grey_
+ *                  names themselves stay the closed set of section 4p - one per operation of the full-size codec
+ *   workspace      nimg_jpeg_reconstruct_scaled_workspace_bytes of the same geometry and scale; 0 = a geometry or scale not served
+ * scale 1 IS nimg_jpeg_reconstruct_tables: its launches, its workspace size, its bytes.  A scale outside {1, 2, 4, 8} or a null pointer
+ * is NIMG_ERR_ARG, a short workspace NIMG_ERR_WORKSPACE, both before any launch.  No allocation, no synchronisation, capturable; the
+ * _grey forms take n == 0 as a no-op.  Purely added: NIMG_ABI_VERSION stays. */
+size_t nimg_jpeg_reconstruct_scaled_workspace_bytes(int n, int h, int w, int hs, int vs, int scale);
+int nimg_jpeg_reconstruct_scaled(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, int scale, void* y,
+                                 int out_u8, void* workspace, size_t workspace_bytes, void* stream);
+size_t nimg_jpeg_reconstruct_scaled_grey_workspace_bytes(int n, int h, int w, int scale);
+int nimg_jpeg_reconstruct_scaled_grey(const int16_t* coef, int n, int h, int w, const uint16_t* qtabs, int scale, void* y, int out_u8,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* Sign planes of the FAN's bf16-stored pooled activations: all that a layer's input gradient reads of the
  * activation in front of it is LeakyReLU', one bit per value.  A plane is (n, h, w, c / 8) bytes next to a bf16 tensor (n, h, w, c),
  * c % 8 == 0: bit e of byte c' / 8 is 1 iff the STORED bf16 value of channel c' + e is > 0 (-0, +0 and NaN give 0) - the predicate of

@@ -1092,8 +1092,20 @@ def _as_files(files):
     return [bytes(files)] if isinstance(files, (bytes, bytearray, memoryview)) else [bytes(f) for f in files]
 
 
+def scaled_size(h, w, scale):
+    """(rows, cols) of an h x w file decoded with decode_batch(scale=): ceil(h / scale), ceil(w / scale), as libjpeg rounds."""
+    return ops.jpeg_scaled_size(h, w, scale)
+
+
+def draft_scale(h, w, size):
+    """The scale Pillow's Image.draft(mode, size) chooses for an h x w file and a requested size (width, height): the largest of 8, 4,
+    2, 1 that is not above min(w // size[0], h // size[1]) - the image stays at least as large as asked for - and 1 where that is 0."""
+    ratio = min(w // int(size[0]), h // int(size[1]))
+    return next((s for s in (8, 4, 2) if s <= ratio), 1)
+
+
 def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False,
-                 allow_grey=False):
+                 allow_grey=False, scale=1):
     """Decode baseline JPEG files on the GPU: a list of bytes (or one bytes) -> (n,h,w,3) uint8, the array imageio.imread returns for
     each (libjpeg's islow inverse DCT and fancy up-sampling, bit for bit), or float32(byte) / 255 with as_float.  Files of different
     geometry give a list of (h,w,3) arrays in input order.  Any 8-bit quantisation and Huffman tables are read from each file
@@ -1104,11 +1116,21 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     allow_progressive: progressive files of any legal scan script are read too (parse_header), next to baseline
     ones in the same call; a group is then the files of equal geometry, interval and script (nimg_jpeg_decode_progressive).
     allow_grey: grey-scale files are read too (parse_header) and decode to (n,h,w,1) - the array imageio.imread
-    returns for them with a last axis added; next to colour files they are another geometry, so the result is then a list."""
+    returns for them with a last axis added; next to colour files they are another geometry, so the result is then a list.
+    scale (1, 2, 4 or 8): every file is decoded at 1 / scale, to (n, ceil(h / scale), ceil(w / scale), 3 | 1) -
+    libjpeg's scaled decoding, the pixels Pillow returns after Image.draft() (draft_scale names the scale it chooses), by reduced
+    inverse DCTs in place of the full one (ops.jpeg_reconstruct_scaled); the entropy decoding is the same.  At a reduced scale the files
+    of ONE geometry come back as one batch in input order whatever their restart intervals and scan scripts (at scale 1 they stay the
+    list they were).  Any other scale is a ValueError before a byte goes to the device."""
+    scale = ops.jpeg_scale(scale)
     files = _as_files(files)
     headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey)
-    images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
-              for _, (h, w, hs, vs), coef, _, _, qt in groups]
+    if scale == 1:
+        images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
+                  for _, (h, w, hs, vs), coef, _, _, qt in groups]
+    else:
+        images = [ops.jpeg_reconstruct_scaled(coef, h, w, qt, scale, hs, vs, out_u8=not as_float)
+                  for _, (h, w, hs, vs), coef, _, _, qt in groups]
     words = [len(g[0]) for g in groups]
     parts = [g[3].view(torch.uint8) for g in groups]                    # one download: the status words, then the images
     if not device_output:
@@ -1124,6 +1146,11 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
         images = out
     if len(groups) == 1:
         return images[0]
+    if scale != 1 and len({g[1] for g in groups}) == 1:                 # one geometry, several intervals or scripts: one batch
+        order = np.argsort([i for g in groups for i in g[0]])
+        if device_output:
+            return torch.cat(images)[torch.from_numpy(order).to(images[0].device)]
+        return np.concatenate(images)[order]
     result = [None] * len(files)
     for (idx, _, _, _, _, _), y in zip(groups, images):
         for j, i in enumerate(idx):

@@ -74,6 +74,15 @@ struct BatchTables {
     __device__ __forceinline__ int divisor(const uint16_t* q, int nat) const { return q[nat]; }
 };
 
+// The tables of each file, for the two units that reconstruct what was read (jpegd.hip, jpegd_scaled.hip): qtabs[image][component][64],
+// natural order, in global memory.  Nothing transforms with it, so it has no source() and no divisor().
+struct FileTables {
+    const uint16_t* qtabs;
+    __device__ __forceinline__ const uint16_t* table(const JpegGeo& g, long, int img, int comp) const {
+        return qtabs + ((size_t)img * g.nc + comp) * 64;
+    }
+};
+
 constexpr int Q_BASE[2][64] = {
     {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
      18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,

@@ -287,15 +287,6 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout
     if (bad) atomicOr(a.status + img, JPEGD_ST_DC);
 }
 
-// ---- reconstruct with the tables of each image ----------------------------------------------------------------------------------
-// jpegc.h's table source for the tables of each file: qtabs[image][component][64], natural order, in global memory
-struct FileTables {
-    const uint16_t* qtabs;
-    __device__ __forceinline__ const uint16_t* table(const JpegGeo& g, long, int img, int comp) const {
-        return qtabs + ((size_t)img * g.nc + comp) * 64;
-    }
-};
-
 // ---- the launchers, for files of three components (nc = 3) and of one (nc = 1, section 4p) ----------------------------------------
 size_t decode_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval, size_t ecd_bytes, int subseq_bits) {
     JpegGeo g;

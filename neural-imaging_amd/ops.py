@@ -2482,6 +2482,8 @@ def _jpeg_entry(name, hs, vs, *middle):
         return name, (hs, vs)
     if name == 'nimg_jpeg_encode_restart_workspace_bytes':         # one size serves the pixel stages and the Annex K coder
         return 'nimg_jpeg_grey_workspace_bytes', middle
+    if name.startswith('nimg_jpeg_reconstruct_scaled'):             # section 4q: nimg_jpeg_reconstruct_scaled_grey[_workspace_bytes]
+        return name.replace('reconstruct_scaled', 'reconstruct_scaled_grey'), middle
     return name.replace('nimg_jpeg_', 'nimg_jpeg_grey_').replace('_restart', ''), middle
 
 
@@ -2789,6 +2791,47 @@ def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspa
         raise RuntimeError('jpeg_reconstruct_tables: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, (n, h, w, nc)))
     entry, factors = _jpeg_entry('nimg_jpeg_reconstruct_tables', hs, vs)
     _lib.call(entry, _p(coef), n, h, w, *factors, _p(qtabs), _p(y), int(bool(out_u8)), _p(ws), need, _stream())
+    return y
+
+
+JPEG_SCALES = (1, 2, 4, 8)       # the denominators of libjpeg's scale_num / scale_denom that the codec reads at
+
+
+def jpeg_scale(scale):
+    """A scale denominator as an op takes it: the integer 1, 2, 4 or 8; everything else is a ValueError."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) not in JPEG_SCALES:
+        raise ValueError('scale: one of the integers 1, 2, 4, 8 needed (the image is decoded at 1 / scale), got {!r}'.format(scale))
+    return int(scale)
+
+
+def jpeg_scaled_size(h, w, scale):
+    """(rows, cols) of an h x w image decoded at 1 / scale: libjpeg rounds up."""
+    scale = jpeg_scale(scale)
+    return -(-h // scale), -(-w // scale)
+
+
+def jpeg_reconstruct_scaled(coef, h, w, qtabs, scale, hs=1, vs=1, out_u8=False, workspace=None, out=None):
+    """jpeg_reconstruct_tables at 1 / scale (scale 1, 2, 4 or 8): the (n, ceil(h / scale), ceil(w / scale), 3) image libjpeg decodes
+    with scale_num / scale_denom = 1 / scale - what Pillow returns after Image.draft() - by the reduced inverse DCTs, bit for bit.
+    Grey-scale (hs, vs = JPEG_GREY): (.., .., 1).  scale 1 is jpeg_reconstruct_tables.  The workspace is
+    nimg_jpeg_reconstruct_scaled_workspace_bytes."""
+    scale = jpeg_scale(scale)
+    _chk(coef)
+    _chk(qtabs)
+    n = _jpeg_coef('jpeg_reconstruct_scaled', coef, h, w, hs, vs)
+    nc = 1 if jpeg_is_grey(hs, vs) else 3
+    if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, nc, 64):
+        raise RuntimeError('jpeg_reconstruct_scaled: tables {} {}, ({}, {}, 64) 16-bit integers needed'.format(qtabs.dtype, tuple(qtabs.shape),
+                                                                                                             n, nc))
+    size, factors = _jpeg_entry('nimg_jpeg_reconstruct_scaled_workspace_bytes', hs, vs)
+    ws, need = _jpeg_workspace(getattr(_lib.load(), size)(n, h, w, *factors, scale), _jpeg_batch(n, h, w, hs, vs), coef.device, workspace)
+    dtype, shape = torch.uint8 if out_u8 else torch.float32, (n,) + jpeg_scaled_size(h, w, scale) + (nc,)
+    y = torch.empty(shape, dtype=dtype, device=coef.device) if out is None else out
+    _chk(y)
+    if y.dtype != dtype or tuple(y.shape) != shape:
+        raise RuntimeError('jpeg_reconstruct_scaled: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, shape))
+    entry, factors = _jpeg_entry('nimg_jpeg_reconstruct_scaled', hs, vs)
+    _lib.call(entry, _p(coef), n, h, w, *factors, _p(qtabs), scale, _p(y), int(bool(out_u8)), _p(ws), need, _stream())
     return y
 
 
