@@ -1036,6 +1036,43 @@ size_t nimg_jpeg_reconstruct_scaled_grey_workspace_bytes(int n, int h, int w, in
 int nimg_jpeg_reconstruct_scaled_grey(const int16_t* coef, int n, int h, int w, const uint16_t* qtabs, int scale, void* y, int out_u8,
                                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* Any sampling: the operations that read a file and write it again, over the same launchers, for colour files
+ * whose luma sampling factors are 1x2 (4:4:0), 4x1 (4:1:1), 4x2 (4:1:0), 1x4 or 2x4 over 1x1 chroma - next to 1x1, 2x1 and 2x2, which
+ * these entries serve with the launches and the bytes of their namesakes.  Every other entry point refuses the five as it did.  A
+ * sampling outside the eight (a factor of 3, 4x4, ...) is NIMG_ERR_ARG before any launch; the size functions then return 0.
+ *   sampling_decode                 nimg_jpeg_decode_restart, and its workspace size
+ *   sampling_decode_progressive     nimg_jpeg_decode_progressive, and its workspace size
+ *   sampling_reconstruct_tables     nimg_jpeg_reconstruct_tables: 1x2 is brought up by libjpeg's h1v2 triangle filter, the other four by
+ *                                   replication; workspace nimg_jpeg_sampling_reconstruct_scaled_workspace_bytes at scale 1
+ *   sampling_reconstruct_scaled     nimg_jpeg_reconstruct_scaled, and its workspace size: the chroma block may have up to 8 samples a
+ *                                   side at any scale, and is brought up by the h2v1 or h1v2 filter or by replication as jdsample.c
+ *                                   chooses for its ratios; scale 1 is nimg_jpeg_sampling_reconstruct_tables
+ *   sampling_histogram              nimg_jpeg_histogram_restart
+ *   sampling_encode_tables          nimg_jpeg_encode_tables_restart, and its workspace size
+ * Arguments, results and error codes are their namesakes'.  Purely added: NIMG_ABI_VERSION stays. */
+size_t nimg_jpeg_sampling_decode_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, size_t ecd_bytes,
+                                                 int subseq_bits);
+int nimg_jpeg_sampling_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                              int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
+                              size_t workspace_bytes, void* stream);
+size_t nimg_jpeg_sampling_decode_progressive_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, int n_scans,
+                                                             size_t ecd_bytes, int subseq_bits);
+int nimg_jpeg_sampling_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans,
+                                          const uint8_t* huffman, int n, int h, int w, int hs, int vs, int restart_interval, int subseq_bits,
+                                          int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
+                                          void* stream);
+int nimg_jpeg_sampling_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y,
+                                          int out_u8, void* workspace, size_t workspace_bytes, void* stream);
+size_t nimg_jpeg_sampling_reconstruct_scaled_workspace_bytes(int n, int h, int w, int hs, int vs, int scale);
+int nimg_jpeg_sampling_reconstruct_scaled(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, int scale, void* y,
+                                          int out_u8, void* workspace, size_t workspace_bytes, void* stream);
+int nimg_jpeg_sampling_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint32_t* hist,
+                                 void* stream);
+size_t nimg_jpeg_sampling_encode_tables_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval);
+int nimg_jpeg_sampling_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, const uint8_t* tables,
+                                     uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
 /* Sign planes of the FAN's bf16-stored pooled activations: all that a layer's input gradient reads of the
  * activation in front of it is LeakyReLU', one bit per value.  A plane is (n, h, w, c / 8) bytes next to a bf16 tensor (n, h, w, c),
  * c % 8 == 0: bit e of byte c' / 8 is 1 iff the STORED bf16 value of channel c' + e is > 0 (-0, +0 and NaN give 0) - the predicate of

@@ -249,7 +249,9 @@ def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qt
 
 
 def _jpeg_header(h, w, quality, subsampling, huffman, qtables, restart_interval):
-    hs, vs = ops.jpeg_subsampling(subsampling)
+    # a file that is written again may have one of the samplings that are only read: transcode_batch passes their
+    # factors themselves, (hs, vs); by name they stay refused, as writing them from pixels is
+    hs, vs = subsampling if isinstance(subsampling, tuple) else ops.jpeg_subsampling(subsampling)
     grey = ops.jpeg_is_grey(hs, vs)
     ri = ops.jpeg_restart_interval(restart_interval)
     quality, qtables = _quality_or_tables(quality, qtables, clamp=True, grey=grey)
@@ -724,7 +726,7 @@ _SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless'
               0xce: 'arithmetic-coded differential progressive', 0xcf: 'arithmetic-coded differential lossless'}
 
 
-def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=False):
+def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=False, allow_sampling=False):
     """The header of a baseline JPEG file, read on the host without decoding: JPEGHeader(h, w, hs, vs, qtables (3, 64) uint16 in
     natural order per component, huffman = six (16 counts, symbols) pairs of bytes in the order Y-DC, Y-AC, Cb-DC, Cb-AC, Cr-DC, Cr-AC
     as the DHT bodies have them, ecd_offset, ecd_end = the offset of the final FFD9, restart_interval).  Accepted: SOF0 with 8-bit
@@ -741,7 +743,10 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
     any marker between scans but DHT, DRI, COM and APPn.  allow_grey: a grey-scale file - a frame of one
     component, SOF0 or with allow_progressive SOF2, 8-bit samples, every scan of that component, any Huffman table ids, with
     allow_restart a DRI - is accepted too.  Its sampling factors may be any of 1..4: a one-component scan is never interleaved, so they
-    change nothing, and hs = vs = 1 is reported.  Its qtables are (1, 64), its huffman two pairs (DC, AC), its `ncomp` 1."""
+    change nothing, and hs = vs = 1 is reported.  Its qtables are (1, 64), its huffman two pairs (DC, AC), its `ncomp` 1.
+    allow_sampling: a colour file whose luma sampling is 1x2 (4:4:0), 4x1 (4:1:1), 4x2 (4:1:0), 1x4 or 2x4 over 1x1 chroma (DESIGN.md
+    section 4r) is accepted too, baseline or with allow_progressive progressive, with allow_restart a DRI.  Still refused, the factors
+    named: chroma that is not 1x1, a factor of 3, and every pair whose ratios are not those (4x4, ...)."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise ValueError('JPEG data: bytes needed, got {}'.format(type(data).__name__))
     data = bytes(data)
@@ -799,8 +804,12 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
                 if not (1 <= sampling[0][0] <= 4 and 1 <= sampling[0][1] <= 4):
                     raise ValueError('illegal sampling factors {}x{} of the one component (1..4 each)'.format(*sampling[0]))
             elif sampling[0] not in ((1, 1), (2, 1), (2, 2)) or sampling[1:] != ((1, 1), (1, 1)):
-                raise ValueError('unsupported sampling factors {} (luma 1x1, 2x1 or 2x2 over 1x1 chroma)'.format(
-                    ' '.join('{}x{}'.format(*f) for f in sampling)))
+                if not allow_sampling:
+                    raise ValueError('unsupported sampling factors {} (luma 1x1, 2x1 or 2x2 over 1x1 chroma)'.format(
+                        ' '.join('{}x{}'.format(*f) for f in sampling)))
+                if sampling[1:] != ((1, 1), (1, 1)) or not ops.jpeg_is_wide(*sampling[0]):
+                    raise ValueError('unsupported sampling factors {} (luma 1x1, 2x1, 2x2, 1x2, 4x1, 4x2, 1x4 or 2x4 over 1x1 chroma)'.format(
+                        ' '.join('{}x{}'.format(*f) for f in sampling)))
             frame = (h, w, comps)
         elif marker in _SOF_NAMES:
             raise ValueError('{} file (SOF{}): only baseline sequential files (SOF0) are read'.format(_SOF_NAMES[marker], marker - 0xc0))
@@ -1030,12 +1039,12 @@ def _status_text(status):
     return ' | '.join(text for bit, text in JPEG_STATUS_BITS.items() if status & bit)
 
 
-def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progressive=False, allow_grey=False):
+def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progressive=False, allow_grey=False, allow_sampling=False):
     """Headers parsed, one upload, one nimg_jpeg_decode[_restart] per group of equal (h, w, hs, vs, restart interval) - for progressive
     files (allow_progressive) one nimg_jpeg_decode_progressive per group of equal geometry, interval and scan script.  Returns
     (headers, groups) with groups = [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back.  The
     (hs, vs) of a group of grey-scale files (allow_grey) is ops.JPEG_GREY: another geometry, so never in a group with colour files."""
-    headers = [parse_header(f, allow_restart, allow_progressive, allow_grey) for f in files]
+    headers = [parse_header(f, allow_restart, allow_progressive, allow_grey, allow_sampling) for f in files]
     if not headers:
         raise ValueError('no files to decode')
     keys = OrderedDict()
@@ -1105,7 +1114,7 @@ def draft_scale(h, w, size):
 
 
 def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False,
-                 allow_grey=False, scale=1):
+                 allow_grey=False, allow_sampling=False, scale=1):
     """Decode baseline JPEG files on the GPU: a list of bytes (or one bytes) -> (n,h,w,3) uint8, the array imageio.imread returns for
     each (libjpeg's islow inverse DCT and fancy up-sampling, bit for bit), or float32(byte) / 255 with as_float.  Files of different
     geometry give a list of (h,w,3) arrays in input order.  Any 8-bit quantisation and Huffman tables are read from each file
@@ -1117,6 +1126,8 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     ones in the same call; a group is then the files of equal geometry, interval and script (nimg_jpeg_decode_progressive).
     allow_grey: grey-scale files are read too (parse_header) and decode to (n,h,w,1) - the array imageio.imread
     returns for them with a last axis added; next to colour files they are another geometry, so the result is then a list.
+    allow_sampling: colour files of the samplings 4:4:0, 4:1:1, 4:1:0, 1x4 and 2x4 are read too (parse_header), at
+    every scale, with the up-sampling libjpeg chooses for them; a sampling is part of the geometry, as it always was.
     scale (1, 2, 4 or 8): every file is decoded at 1 / scale, to (n, ceil(h / scale), ceil(w / scale), 3 | 1) -
     libjpeg's scaled decoding, the pixels Pillow returns after Image.draft() (draft_scale names the scale it chooses), by reduced
     inverse DCTs in place of the full one (ops.jpeg_reconstruct_scaled); the entropy decoding is the same.  At a reduced scale the files
@@ -1124,7 +1135,7 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     list they were).  Any other scale is a ValueError before a byte goes to the device."""
     scale = ops.jpeg_scale(scale)
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey, allow_sampling)
     if scale == 1:
         images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
                   for _, (h, w, hs, vs), coef, _, _, qt in groups]
@@ -1159,15 +1170,16 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
 
 
 def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, *, allow_restart=False, allow_progressive=False,
-                        allow_grey=False):
+                        allow_grey=False, allow_sampling=False):
     """The quantised coefficients of baseline files of ONE geometry, as stored in the files: ((n, real blocks, 64) int16 in the layout
     of DESIGN.md section 4c - [Y | Cb | Cr][block row][block col][zig-zag] - and the (n, 3, 64) uint16 quantisation tables per
     component in natural order; jpeg_qf_estimation(tables[i, c].reshape(8, 8), c) names the quality they came from).
     allow_restart: as decode_batch's; the files must then share their restart interval too.  allow_progressive: as decode_batch's;
     the files must then share their scan script too (baseline files count as one script).  allow_grey: grey-scale files are read too
-    - (n, blocks, 64) coefficients in raster order and (n, 1, 64) tables -, never in one call with colour files."""
+    - (n, blocks, 64) coefficients in raster order and (n, 1, 64) tables -, never in one call with colour files.  allow_sampling: as
+    decode_batch's; the layout is the same, over the real blocks ops.jpeg_geometry names for the factors."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey)
+    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey, allow_sampling)
     if len(groups) != 1:
         raise ValueError('decode_coefficients needs files of one geometry{}, got {}'.format(
             (' and restart interval' if allow_restart else '') + (' and scan script' if allow_progressive else ''), [g[1] for g in groups]))
@@ -1176,7 +1188,21 @@ def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, 
     return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
 
 
-def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False, allow_progressive=False, allow_grey=False):
+def _annex_k_coding():
+    """_coding's triple for Annex K's tables through the coder that takes tables: what serves the samplings that nimg_jpeg_encode does
+    not.  The segments are the ones nimg_jpeg_encode writes - the same walk, the same clamps, the same codes."""
+    annex_k = np.zeros((4, ops.JPEG_TABLE_BYTES), np.uint8)
+    for j, t in enumerate(_DHT):
+        annex_k[j, :len(t) - 1] = np.frombuffer(t, np.uint8, offset=1)
+
+    def encode(coef, h, w, hs, vs, workspace=None, capacity=None, restart_interval=0):
+        tables = torch.from_numpy(annex_k).to(coef.device).expand(coef.shape[0], 4, ops.JPEG_TABLE_BYTES).contiguous()
+        return ops.jpeg_encode_tables(coef, tables, h, w, hs, vs, capacity=capacity, restart_interval=restart_interval)[:2]
+    return None, encode, ops.jpeg_ecd_bound_tables
+
+
+def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False, allow_progressive=False, allow_grey=False,
+                    allow_sampling=False):
     """Baseline files written again with their coefficients and their quantisation tables untouched - a list of bytes in input order.
     The Huffman tables are the optimal ones of each image (what jpegtran -optimize does) or, with optimize=False, Annex K's.  Every
     file parse_header accepts is read; the header written is the one of encode_batch - JFIF APP0, two DQT segments where the file's Cb
@@ -1187,18 +1213,26 @@ def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=Fa
     tables are optimal whatever `optimize` says.  allow_progressive: progressive files of any legal scan script are read too
     (parse_header) and written as baseline files - jpegtran -optimize of a progressive file - or, with progressive, as libjpeg's simple
     progression whatever script came in.  allow_grey: grey-scale files, baseline or with allow_progressive progressive, are read too and
-    written again as grey-scale baseline files (one DQT segment, the DC and AC table 0) - not with `progressive`."""
+    written again as grey-scale baseline files (one DQT segment, the DC and AC table 0) - not with `progressive`.  allow_sampling: files
+    of the samplings 4:4:0, 4:1:1, 4:1:0, 1x4 and 2x4 are read too and written again as baseline files of the same
+    sampling factors - not with `progressive`, which is a ValueError for them."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, 0, None, allow_restart, allow_progressive, allow_grey)
+    headers, groups = _decode_groups(files, 0, None, allow_restart, allow_progressive, allow_grey, allow_sampling)
     _colour_only('progressive=True (writing the six scans libjpeg writes for one component)',
                  progressive and any(hd.ncomp == 1 for hd in headers))
+    wide = sorted({(hd.hs, hd.vs) for hd in headers if hd.ncomp == 3 and ops.jpeg_is_wide(hd.hs, hd.vs)})
+    if progressive and wide:
+        raise ValueError('progressive=True: progressive files are not written with the sampling factors {} (DESIGN.md section 8); they '
+                         'are written again as baseline files'.format(', '.join('{}x{}'.format(*f) for f in wide)))
     _raise_on_status(groups, np.split(torch.cat([g[3] for g in groups]).cpu().numpy(), np.cumsum([len(g[0]) for g in groups])[:-1]))
     names = {v: k for k, v in ops.JPEG_SUBSAMPLING.items()}
     names[ops.JPEG_GREY] = 'grey'
+    names.update({v: v for v in ops.JPEG_SAMPLING_WIDE.values()})           # (_jpeg_header takes their factors as they are)
     result = [None] * len(files)
     for idx, (h, w, hs, vs), coef, _, _, _ in groups:
         ri = headers[idx[0]].restart_interval                               # the group's: files are grouped by it
-        segments, tables = _device_segments(_coding(optimize, progressive), coef, len(idx), h, w, hs, vs, restart_interval=ri)
+        coding = _annex_k_coding() if ops.jpeg_is_wide(hs, vs) and not optimize else _coding(optimize, progressive)
+        segments, tables = _device_segments(coding, coef, len(idx), h, w, hs, vs, restart_interval=ri)
         for j, i in enumerate(idx):                                         # a file at a time: each keeps its quantisation tables
             qt = headers[i].qtables
             qt = qt if len(qt) == 1 else (qt[:2] if np.array_equal(qt[1], qt[2]) else qt)

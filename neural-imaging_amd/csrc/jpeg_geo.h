@@ -38,12 +38,27 @@ inline bool set_restart(JpegGeo* g, int restart_interval) {
     return true;
 }
 
+// The luma sampling factors a caller of make_geo admits over 1x1 chroma.  JPEG_FACTORS_THREE: 1x1, 2x1 and 2x2, what every entry point
+// took before DESIGN.md section 4r and what all but the nimg_jpeg_sampling_* entries still take.  JPEG_FACTORS_WIDE: also 1x2, 4x1, 4x2,
+// 1x4 and 2x4 - every power-of-two pair whose MCU has at most the ten blocks T.81 allows.
+enum { JPEG_FACTORS_THREE = 0, JPEG_FACTORS_WIDE = 1 };
+// the set of a call that names none: the three - but for a host program that holds the cores to the wide set (tests/jpegsamp_host.cpp)
+#ifndef JPEG_FACTORS_DEFAULT
+#define JPEG_FACTORS_DEFAULT JPEG_FACTORS_THREE
+#endif
+
+inline bool jpeg_factors_ok(int hs, int vs, int factors) {
+    if ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2)) return true;
+    if (factors != JPEG_FACTORS_WIDE) return false;
+    return (hs == 1 && vs == 2) || (hs == 4 && vs == 1) || (hs == 4 && vs == 2) || (hs == 1 && vs == 4) || (hs == 2 && vs == 4);
+}
+
 // nc = 1: a grey-scale file - one component, never sub-sampled, one block per MCU in raster order; it has no chroma blocks at all
-inline bool make_geo(JpegGeo* g, int n, int h, int w, int hs, int vs, int nc = 3) {
+inline bool make_geo(JpegGeo* g, int n, int h, int w, int hs, int vs, int nc = 3, int factors = JPEG_FACTORS_DEFAULT) {
     if (n < 1 || n > 65535 || h < 1 || w < 1 || h > 4096 || w > 4096) return false;
-    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
+    if (!jpeg_factors_ok(hs, vs, factors)) return false;
     if (nc != 3 && !(nc == 1 && hs == 1 && vs == 1)) return false;
-    g->n = n; g->h = h; g->w = w; g->hs = hs; g->vs = vs; g->hsh = hs - 1;
+    g->n = n; g->h = h; g->w = w; g->hs = hs; g->vs = vs; g->hsh = hs == 4 ? 2 : hs - 1;
     g->bhY = (h + 7) / 8; g->bwY = (w + 7) / 8;
     g->ceh = (h + vs - 1) / vs; g->cew = (w + hs - 1) / hs;
     g->bhC = (g->ceh + 7) / 8; g->bwC = (g->cew + 7) / 8;

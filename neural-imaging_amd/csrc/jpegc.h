@@ -349,6 +349,35 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, const Jp
     return fancy_h2v2(si, sn, x);
 }
 
+// The up-sampler of the colour pass, a compile-time choice per launch so that the instantiation that serves 1x1,
+// 2x1 and 2x2 is the code it was before the other samplings were read.  jpeg_chroma_mode names libjpeg's choice (jdsample.c) for a
+// geometry: 1x2 is its h1v2 triangle filter, every other integral ratio plain replication.
+enum { CHROMA_FANCY = 0, CHROMA_H1V2 = 1, CHROMA_REPLICATE = 2 };
+inline int jpeg_chroma_mode(const JpegGeo& g) {
+    if (g.hs <= 2 && g.vs <= g.hs) return CHROMA_FANCY;
+    return g.hs == 1 && g.vs == 2 ? CHROMA_H1V2 : CHROMA_REPLICATE;
+}
+
+// h1v2 "fancy": rows 2j and 2j + 1 are (3 p[j] + p[j - 1] + 1) >> 2 and (3 p[j] + p[j + 1] + 2) >> 2, the neighbour row clamped to the
+// component's real extent, whatever the width
+__device__ __forceinline__ int chroma_h1v2_at(const uint8_t* __restrict__ p, const JpegGeo& g, int y, int x) {
+    const int stride = 8 * g.bwC, j = y >> 1;
+    const int nb = (y & 1) ? min(j + 1, g.ceh - 1) : max(j - 1, 0);
+    return (3 * p[(size_t)j * stride + x] + p[(size_t)nb * stride + x] + 1 + (y & 1)) >> 2;
+}
+
+// int_upsample: the sample is repeated hs times along its row and vs times down its column (both powers of two)
+__device__ __forceinline__ int chroma_replicated_at(const uint8_t* __restrict__ p, const JpegGeo& g, int y, int x) {
+    return p[(size_t)(y >> (g.vs == 4 ? 2 : g.vs - 1)) * (8 * g.bwC) + (x >> g.hsh)];
+}
+
+template <int UP>
+__device__ __forceinline__ int chroma_sample(const uint8_t* __restrict__ p, const JpegGeo& g, int y, int x) {
+    if (UP == CHROMA_H1V2) return chroma_h1v2_at(p, g, y, x);
+    if (UP == CHROMA_REPLICATE) return chroma_replicated_at(p, g, y, x);
+    return chroma_at(p, g, y, x);
+}
+
 // one thread per real block: dequantise, inverse DCT (columns, then rows), + 128, clamp -> the component's sample plane
 template <class Tables>
 __global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t* __restrict__ coef, uint8_t* __restrict__ planes, JpegGeo g, Tables tabs) {

@@ -206,8 +206,9 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpeg_stuff_kernel(const uint32_t
 }
 
 // ---- reconstruct --------------------------------------------------------------------------------------------------------
-// one thread per pixel: clamp, then k / 255 in float32 or the byte itself
-template <bool U8>
+// one thread per pixel: clamp, then k / 255 in float32 or the byte itself.  UP: jpegc.h's up-sampler of the chroma, CHROMA_FANCY for
+// every geometry but those of section 4r
+template <bool U8, int UP = CHROMA_FANCY>
 __global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ planes, void* __restrict__ out, JpegGeo g) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)g.n * g.h * g.w) return;
@@ -218,8 +219,8 @@ __global__ void __launch_bounds__(256) jpeg_colour_kernel(uint8_t* __restrict__ 
         else ((float*)out)[t] = __fdiv_rn((float)yy, 255.0f);
         return;
     }
-    const int cb = chroma_at(plane_of(planes, g, img, 1), g, y, x) - 128;
-    const int cr = chroma_at(plane_of(planes, g, img, 2), g, y, x) - 128;
+    const int cb = chroma_sample<UP>(plane_of(planes, g, img, 1), g, y, x) - 128;
+    const int cr = chroma_sample<UP>(plane_of(planes, g, img, 2), g, y, x) - 128;
     const int R = min(max(red_of(yy, cr), 0), 255);
     const int G = min(max(green_of(yy, cb, cr), 0), 255);
     const int B = min(max(blue_of(yy, cb), 0), 255);
@@ -357,7 +358,14 @@ int nimg_internal_jpeg_colour(uint8_t* planes, void* y, bool u8, const JpegGeo& 
     const long pixels = (long)g.n * g.h * g.w;
     if (!grid_ok(pixels, 256)) return NIMG_ERR_ARG;
     const dim3 grid((unsigned)((pixels + 255) / 256));
-    if (u8) hipLaunchKernelGGL(jpeg_colour_kernel<true>, grid, dim3(256), 0, stream, planes, y, g);
+    const int up = g.nc == 1 ? CHROMA_FANCY : jpeg_chroma_mode(g);
+    if (up == CHROMA_H1V2) {
+        if (u8) hipLaunchKernelGGL((jpeg_colour_kernel<true, CHROMA_H1V2>), grid, dim3(256), 0, stream, planes, y, g);
+        else hipLaunchKernelGGL((jpeg_colour_kernel<false, CHROMA_H1V2>), grid, dim3(256), 0, stream, planes, y, g);
+    } else if (up == CHROMA_REPLICATE) {
+        if (u8) hipLaunchKernelGGL((jpeg_colour_kernel<true, CHROMA_REPLICATE>), grid, dim3(256), 0, stream, planes, y, g);
+        else hipLaunchKernelGGL((jpeg_colour_kernel<false, CHROMA_REPLICATE>), grid, dim3(256), 0, stream, planes, y, g);
+    } else if (u8) hipLaunchKernelGGL(jpeg_colour_kernel<true>, grid, dim3(256), 0, stream, planes, y, g);
     else hipLaunchKernelGGL(jpeg_colour_kernel<false>, grid, dim3(256), 0, stream, planes, y, g);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;

@@ -210,9 +210,10 @@ __global__ void __launch_bounds__(256) jpeg_emit_tables_kernel(const int16_t* __
 }
 
 // ---- the launchers, for files of three components (nc = 3) and of one (nc = 1, section 4p) ----------------------------------------
-int histogram_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, int restart_interval, uint32_t* hist, void* stream) {
+int histogram_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, int restart_interval, uint32_t* hist, void* stream,
+                     int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
-    if (!coef || !hist || !make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval)) return NIMG_ERR_ARG;
+    if (!coef || !hist || !make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval)) return NIMG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(hist, 0, (size_t)n * jpegopt_tables(g) * JPEGOPT_HIST * 4, st) != hipSuccess) return NIMG_ERR_LAUNCH;
     hipLaunchKernelGGL(jpeg_histogram_kernel, dim3((unsigned)((g.SB + 255) / 256), (unsigned)n), dim3(256), 0, st, coef, hist, g);
@@ -220,17 +221,17 @@ int histogram_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, i
     return NIMG_OK;
 }
 
-size_t tables_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval) {
+size_t tables_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
-    if (!make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval)) return 0;
+    if (!make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval)) return 0;
     return carve(g, nullptr, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS).bytes;
 }
 
 int encode_tables_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, int restart_interval, const uint8_t* tables,
                          uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace, size_t workspace_bytes,
-                         void* stream) {
+                         void* stream, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
-    if (!coef || !tables || !out || !lengths || !status || !workspace || !make_geo(&g, n, h, w, hs, vs, nc) ||
+    if (!coef || !tables || !out || !lengths || !status || !workspace || !make_geo(&g, n, h, w, hs, vs, nc, factors) ||
         !set_restart(&g, restart_interval))
         return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace, JPEGOPT_BLOCK_BITS_MAX, JPEGOPT_CODE_WORDS);
@@ -273,6 +274,23 @@ int nimg_jpeg_grey_encode_tables(const int16_t* coef, int n, int h, int w, int r
     if (n == 0) return NIMG_OK;
     return encode_tables_launch(coef, n, h, w, 1, 1, 1, restart_interval, tables, out, out_capacity, lengths, status, workspace,
                                 workspace_bytes, stream);
+}
+
+// the same launchers with the wide set of sampling factors
+int nimg_jpeg_sampling_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, uint32_t* hist,
+                                 void* stream) {
+    return histogram_launch(coef, n, h, w, hs, vs, 3, restart_interval, hist, stream, JPEG_FACTORS_WIDE);
+}
+
+size_t nimg_jpeg_sampling_encode_tables_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval) {
+    return tables_workspace_size(n, h, w, hs, vs, 3, restart_interval, JPEG_FACTORS_WIDE);
+}
+
+int nimg_jpeg_sampling_encode_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, int restart_interval, const uint8_t* tables,
+                                     uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return encode_tables_launch(coef, n, h, w, hs, vs, 3, restart_interval, tables, out, out_capacity, lengths, status, workspace,
+                                workspace_bytes, stream, JPEG_FACTORS_WIDE);
 }
 
 int nimg_jpeg_histogram(const int16_t* coef, int n, int h, int w, int hs, int vs, uint32_t* hist, void* stream) {

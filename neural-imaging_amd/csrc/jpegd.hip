@@ -288,10 +288,11 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout
 }
 
 // ---- the launchers, for files of three components (nc = 3) and of one (nc = 1, section 4p) ----------------------------------------
-size_t decode_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval, size_t ecd_bytes, int subseq_bits) {
+size_t decode_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval, size_t ecd_bytes, int subseq_bits,
+                             int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     uint32_t sb;
-    if (!make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb) ||
+    if (!make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb) ||
         ecd_bytes > (size_t)n * ECD_MAX)
         return 0;
     return carve_d(g, ecd_bytes, sb, nullptr).bytes;
@@ -299,10 +300,10 @@ size_t decode_workspace_size(int n, int h, int w, int hs, int vs, int nc, int re
 
 int decode_launch(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs, int nc,
                   int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
-                  size_t workspace_bytes, void* stream) {
+                  size_t workspace_bytes, void* stream, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     uint32_t sb;
-    if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs, nc) ||
+    if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs, nc, factors) ||
         !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb))
         return NIMG_ERR_ARG;
     // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
@@ -345,9 +346,9 @@ int decode_launch(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* hu
 }
 
 int reconstruct_tables_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, const uint16_t* qtabs, void* y, int out_u8,
-                              void* workspace, size_t workspace_bytes, void* stream) {
+                              void* workspace, size_t workspace_bytes, void* stream, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
-    if (!coef || !y || !qtabs || !workspace || !make_geo(&g, n, h, w, hs, vs, nc)) return NIMG_ERR_ARG;
+    if (!coef || !y || !qtabs || !workspace || !make_geo(&g, n, h, w, hs, vs, nc, factors)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
     if (workspace_bytes < ws.bytes) return NIMG_ERR_WORKSPACE;
     const long blocks = (long)n * g.NB, pixels = (long)n * h * w;
@@ -407,6 +408,24 @@ int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t*
 int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,
                                  void* workspace, size_t workspace_bytes, void* stream) {
     return reconstruct_tables_launch(coef, n, h, w, hs, vs, 3, qtabs, y, out_u8, workspace, workspace_bytes, stream);
+}
+
+// ---- the same launchers with the wide set of sampling factors -----------------------------------------------
+size_t nimg_jpeg_sampling_decode_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, size_t ecd_bytes,
+                                                 int subseq_bits) {
+    return decode_workspace_size(n, h, w, hs, vs, 3, restart_interval, ecd_bytes, subseq_bits, JPEG_FACTORS_WIDE);
+}
+
+int nimg_jpeg_sampling_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
+                              int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    return decode_launch(ecd, ecd_off, huffman, n, h, w, hs, vs, 3, restart_interval, subseq_bits, coef, status, rounds, workspace,
+                         workspace_bytes, stream, JPEG_FACTORS_WIDE);
+}
+
+int nimg_jpeg_sampling_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y,
+                                          int out_u8, void* workspace, size_t workspace_bytes, void* stream) {
+    return reconstruct_tables_launch(coef, n, h, w, hs, vs, 3, qtabs, y, out_u8, workspace, workspace_bytes, stream, JPEG_FACTORS_WIDE);
 }
 
 }  // extern "C"

@@ -380,10 +380,10 @@ bool take_script(const int32_t* script, int n_scans, int nc, PScript* out, int* 
 
 // ---- the launchers, for frames of three components (nc = 3) and of one (nc = 1, section 4p) ---------------------------------------
 size_t progressive_workspace_size(int n, int h, int w, int hs, int vs, int nc, int restart_interval, int n_scans, size_t ecd_bytes,
-                                  int subseq_bits) {
+                                  int subseq_bits, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     uint32_t sb;
-    if (!make_geo(&g, n, h, w, hs, vs, nc) || !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || n_scans < 1 ||
+    if (!make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || n_scans < 1 ||
         n_scans > JPEGDPROG_SCANS_MAX || ecd_bytes > (size_t)n * n_scans * PROG_ECD_MAX)
         return 0;
     return carve_p(g, n_scans, ecd_bytes, sb, nullptr).bytes;
@@ -391,12 +391,12 @@ size_t progressive_workspace_size(int n, int h, int w, int hs, int vs, int nc, i
 
 int progressive_launch(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans, const uint8_t* huffman, int n, int h,
                        int w, int hs, int vs, int nc, int restart_interval, int subseq_bits, int16_t* coef, uint32_t* status,
-                       uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream) {
+                       uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     uint32_t sb;
     PArgs a;
     int top;
-    if (!ecd || !ecd_off || !huffman || !coef || !status || !rounds || !workspace || !make_geo(&g, n, h, w, hs, vs, nc) ||
+    if (!ecd || !ecd_off || !huffman || !coef || !status || !rounds || !workspace || !make_geo(&g, n, h, w, hs, vs, nc, factors) ||
         !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || !take_script(script, n_scans, nc, &a.script, &top))
         return NIMG_ERR_ARG;
     // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
@@ -458,6 +458,20 @@ int nimg_jpeg_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, co
                                  uint32_t* rounds, void* workspace, size_t workspace_bytes, void* stream) {
     return progressive_launch(ecd, ecd_off, script, n_scans, huffman, n, h, w, hs, vs, 3, restart_interval, subseq_bits, coef, status, rounds,
                               workspace, workspace_bytes, stream);
+}
+
+// the same launcher with the wide set of sampling factors
+size_t nimg_jpeg_sampling_decode_progressive_workspace_bytes(int n, int h, int w, int hs, int vs, int restart_interval, int n_scans,
+                                                             size_t ecd_bytes, int subseq_bits) {
+    return progressive_workspace_size(n, h, w, hs, vs, 3, restart_interval, n_scans, ecd_bytes, subseq_bits, JPEG_FACTORS_WIDE);
+}
+
+int nimg_jpeg_sampling_decode_progressive(const uint8_t* ecd, const uint64_t* ecd_off, const int32_t* script, int n_scans,
+                                          const uint8_t* huffman, int n, int h, int w, int hs, int vs, int restart_interval, int subseq_bits,
+                                          int16_t* coef, uint32_t* status, uint32_t* rounds, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    return progressive_launch(ecd, ecd_off, script, n_scans, huffman, n, h, w, hs, vs, 3, restart_interval, subseq_bits, coef, status, rounds,
+                              workspace, workspace_bytes, stream, JPEG_FACTORS_WIDE);
 }
 
 size_t nimg_jpeg_grey_decode_progressive_workspace_bytes(int n, int h, int w, int restart_interval, int n_scans, size_t ecd_bytes,

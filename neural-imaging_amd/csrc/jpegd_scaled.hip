@@ -92,8 +92,9 @@ __global__ void __launch_bounds__(256) jpeg_idct_scaled_kernel(const int16_t* __
     for (int r = 0; r < N; ++r) store_row<N>(p + (size_t)r * stride, d + N * r);
 }
 
-// one thread per output pixel
-template <bool U8>
+// one thread per output pixel.  ANY: the up-sampler of any sampling (jpegscale_chroma_at, section 4r) in place of the 4:2:2 form - a
+// compile-time choice, so that the instantiation of the three samplings of section 4q stays the code it was
+template <bool U8, bool ANY = false>
 __global__ void __launch_bounds__(256) jpeg_colour_scaled_kernel(const uint8_t* __restrict__ planes, void* __restrict__ out, JpegGeo g,
                                                                  JpegScaleGeo sg) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -109,7 +110,10 @@ __global__ void __launch_bounds__(256) jpeg_colour_scaled_kernel(const uint8_t* 
     const uint8_t* pb = planes + jpegscale_plane_offset(sg, img, 1) + (size_t)y * sg.strideC;
     const uint8_t* pr = pb + sg.planeC;
     int cb, cr;
-    if (sg.up == JPEGSCALE_UP_NONE) {
+    if (ANY) {
+        const uint8_t* plane = planes + jpegscale_plane_offset(sg, img, 1);
+        cb = jpegscale_chroma_at(plane, sg, y, x); cr = jpegscale_chroma_at(plane + sg.planeC, sg, y, x);
+    } else if (sg.up == JPEGSCALE_UP_NONE) {
         cb = pb[x]; cr = pr[x];
     } else {
         int near, nb;
@@ -150,19 +154,22 @@ void launch_idct_of(int N, const int16_t* coef, uint8_t* planes, const JpegGeo& 
     else launch_idct<8>(coef, planes, g, sg, qtabs, part, st);
 }
 
-size_t scaled_workspace_size(int n, int h, int w, int hs, int vs, int nc, int scale) {
+size_t scaled_workspace_size(int n, int h, int w, int hs, int vs, int nc, int scale, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     JpegScaleGeo sg;
-    if (!jpegscale_ok(scale) || !make_geo(&g, n, h, w, hs, vs, nc)) return 0;
+    if (!jpegscale_ok(scale) || !make_geo(&g, n, h, w, hs, vs, nc, factors)) return 0;
+    if (scale == 1 && factors == JPEG_FACTORS_WIDE) return carve(g, nullptr).bytes;        // what nimg_jpeg_workspace_bytes counts
     if (scale == 1) return nc == 1 ? nimg_jpeg_grey_workspace_bytes(n, h, w, 0) : nimg_jpeg_workspace_bytes(n, h, w, hs, vs);
     return make_scale_geo(&sg, g, scale) ? align256((size_t)n * sg.per) : 0;
 }
 
 int reconstruct_scaled_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, const uint16_t* qtabs, int scale, void* y,
-                              int out_u8, void* workspace, size_t workspace_bytes, void* stream) {
+                              int out_u8, void* workspace, size_t workspace_bytes, void* stream, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     JpegScaleGeo sg;
-    if (!coef || !y || !qtabs || !workspace || !jpegscale_ok(scale) || !make_geo(&g, n, h, w, hs, vs, nc)) return NIMG_ERR_ARG;
+    if (!coef || !y || !qtabs || !workspace || !jpegscale_ok(scale) || !make_geo(&g, n, h, w, hs, vs, nc, factors)) return NIMG_ERR_ARG;
+    if (scale == 1 && factors == JPEG_FACTORS_WIDE)
+        return nimg_jpeg_sampling_reconstruct_tables(coef, n, h, w, hs, vs, qtabs, y, out_u8, workspace, workspace_bytes, stream);
     if (scale == 1)
         return nc == 1 ? nimg_jpeg_grey_reconstruct_tables(coef, n, h, w, qtabs, y, out_u8, workspace, workspace_bytes, stream)
                        : nimg_jpeg_reconstruct_tables(coef, n, h, w, hs, vs, qtabs, y, out_u8, workspace, workspace_bytes, stream);
@@ -182,7 +189,10 @@ int reconstruct_scaled_launch(const int16_t* coef, int n, int h, int w, int hs, 
         NIMG_CHECK_LAUNCH();
     }
     const dim3 grid((unsigned)((pixels + 255) / 256));
-    if (out_u8) hipLaunchKernelGGL(jpeg_colour_scaled_kernel<true>, grid, dim3(256), 0, st, (const uint8_t*)planes, y, g, sg);
+    if (nc == 3 && !jpeg_factors_ok(hs, vs, JPEG_FACTORS_THREE)) {        // the samplings of section 4r
+        if (out_u8) hipLaunchKernelGGL((jpeg_colour_scaled_kernel<true, true>), grid, dim3(256), 0, st, (const uint8_t*)planes, y, g, sg);
+        else hipLaunchKernelGGL((jpeg_colour_scaled_kernel<false, true>), grid, dim3(256), 0, st, (const uint8_t*)planes, y, g, sg);
+    } else if (out_u8) hipLaunchKernelGGL(jpeg_colour_scaled_kernel<true>, grid, dim3(256), 0, st, (const uint8_t*)planes, y, g, sg);
     else hipLaunchKernelGGL(jpeg_colour_scaled_kernel<false>, grid, dim3(256), 0, st, (const uint8_t*)planes, y, g, sg);
     NIMG_CHECK_LAUNCH();
     return NIMG_OK;
@@ -199,6 +209,17 @@ size_t nimg_jpeg_reconstruct_scaled_workspace_bytes(int n, int h, int w, int hs,
 int nimg_jpeg_reconstruct_scaled(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, int scale, void* y,
                                  int out_u8, void* workspace, size_t workspace_bytes, void* stream) {
     return reconstruct_scaled_launch(coef, n, h, w, hs, vs, 3, qtabs, scale, y, out_u8, workspace, workspace_bytes, stream);
+}
+
+// the same launcher with the wide set of sampling factors; scale 1 is nimg_jpeg_sampling_reconstruct_tables
+size_t nimg_jpeg_sampling_reconstruct_scaled_workspace_bytes(int n, int h, int w, int hs, int vs, int scale) {
+    return scaled_workspace_size(n, h, w, hs, vs, 3, scale, JPEG_FACTORS_WIDE);
+}
+
+int nimg_jpeg_sampling_reconstruct_scaled(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, int scale, void* y,
+                                          int out_u8, void* workspace, size_t workspace_bytes, void* stream) {
+    return reconstruct_scaled_launch(coef, n, h, w, hs, vs, 3, qtabs, scale, y, out_u8, workspace, workspace_bytes, stream,
+                                     JPEG_FACTORS_WIDE);
 }
 
 size_t nimg_jpeg_reconstruct_scaled_grey_workspace_bytes(int n, int h, int w, int scale) {

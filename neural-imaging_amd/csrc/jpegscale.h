@@ -16,16 +16,21 @@
 #endif
 
 enum { JPEGSCALE_UP_NONE = 0, JPEGSCALE_UP_REPLICATE = 1, JPEGSCALE_UP_FANCY = 2 };
+// the up-sampler of any sampling: none, the h2v1 or the h1v2 triangle filter, replication by (rx, ry)
+enum { JPEGSCALE_MODE_NONE = 0, JPEGSCALE_MODE_REPLICATE = 1, JPEGSCALE_MODE_H2V1 = 2, JPEGSCALE_MODE_H1V2 = 3 };
 
 // The planes of one image lie [Y | Cb | Cr], every plane over the component's real blocks at its own block size (rows of
 // stride = block columns * N samples), and every plane begins at a multiple of 16 bytes.
 struct JpegScaleGeo {
     int s, m;                          // the denominator, and 8 / s: the scaled block size of the frame
     int oh, ow;                        // the output image: ceil(h / s), ceil(w / s)
-    int nY, nC;                        // the side of a luma and of a chroma block: m, and 2 m where the chroma is sub-sampled both ways
+    int nY, nC;                        // the side of a luma and of a chroma block: m, and m doubled while jpegscale_block lets it (up to 8)
     int ehY, ewY, ehC, ewC;            // a component's scaled extent in samples: ceil(h vc N / (8 vmax)), ceil(w hc N / (8 hmax))
     int strideY, strideC;              // samples from one plane row to the next
-    int up;                            // JPEGSCALE_UP_*: how a chroma row becomes an output row (2 : 1 horizontally, 4:2:2 only)
+    int up;                            // JPEGSCALE_UP_*: how a chroma row becomes an output row (2 : 1 horizontally, 4:2:2 only) - the
+                                       // form of section 4q, which says "as wide or half as wide": it holds for 1x1, 2x1 and 2x2 alone
+    int rx, ry, mode;                  // any sampling (section 4r): output samples per chroma sample along a row and down a column,
+                                       // hmax m / nC and vmax m / nC, and the JPEGSCALE_MODE_* that brings the chroma up by them
     size_t planeY, planeC, per;        // bytes of the luma plane, of one chroma plane, of an image's planes
 };
 
@@ -56,6 +61,14 @@ JPEG_GEO_HD inline bool make_scale_geo(JpegScaleGeo* sg, const JpegGeo& g, int s
     // jdsample.c: the chroma is as wide as the output (nothing to do) or half as wide; then the triangle filter, unless the frame's
     // block is one sample (do_fancy needs min_DCT_scaled_size > 1) or the row has at most two samples
     sg->up = (g.nc == 1 || sg->ewC == sg->ow) ? JPEGSCALE_UP_NONE : (scale < 8 && sg->ewC > 2) ? JPEGSCALE_UP_FANCY : JPEGSCALE_UP_REPLICATE;
+    // jdsample.c's choice by the ratios, in its order: none; h2v1, h1v2 and h2v2 with the triangle filter where do_fancy holds (and, for
+    // the two that widen, the row has more than two samples), else replication.  (2, 2) cannot arise over 1x1 chroma: the block of such a
+    // component would have been doubled once more - it is refused, not guessed at.
+    sg->rx = g.nc == 1 ? 1 : hmax * m / sg->nC; sg->ry = g.nc == 1 ? 1 : vmax * m / sg->nC;
+    if (sg->rx == 2 && sg->ry == 2) return false;
+    sg->mode = (sg->rx == 1 && sg->ry == 1) ? JPEGSCALE_MODE_NONE
+               : (sg->rx == 2 && sg->ry == 1 && m > 1 && sg->ewC > 2) ? JPEGSCALE_MODE_H2V1
+               : (sg->rx == 1 && sg->ry == 2 && m > 1) ? JPEGSCALE_MODE_H1V2 : JPEGSCALE_MODE_REPLICATE;
     sg->planeY = ((size_t)g.nbY * sg->nY * sg->nY + 15) & ~(size_t)15;
     sg->planeC = ((size_t)g.nbC * sg->nC * sg->nC + 15) & ~(size_t)15;
     sg->per = sg->planeY + (size_t)(g.nc - 1) * sg->planeC;
@@ -71,6 +84,23 @@ JPEG_GEO_HD inline size_t jpegscale_plane_offset(const JpegScaleGeo& sg, int img
 JPEG_GEO_HD inline void jpegscale_chroma_columns(const JpegScaleGeo& sg, int x, int& near, int& nb) {
     near = x >> 1;
     nb = (x & 1) ? (near + 1 < sg.ewC ? near + 1 : sg.ewC - 1) : (near > 0 ? near - 1 : 0);
+}
+
+// The chroma sample under output pixel (y, x) for any sampling: p = the component's scaled plane.  The arithmetic of the two triangle
+// filters is jpegc.h's (fancy_h2v1, chroma_h1v2_at); a neighbour beyond the component's extent is the edge sample itself.
+JPEG_GEO_HD inline int jpegscale_chroma_at(const uint8_t* p, const JpegScaleGeo& sg, int y, int x) {
+    if (sg.mode == JPEGSCALE_MODE_NONE) return p[(size_t)y * sg.strideC + x];
+    if (sg.mode == JPEGSCALE_MODE_H2V1) {
+        int near, nb;
+        jpegscale_chroma_columns(sg, x, near, nb);
+        const uint8_t* row = p + (size_t)y * sg.strideC;
+        return (3 * row[near] + row[nb] + 1 + (x & 1)) >> 2;
+    }
+    if (sg.mode == JPEGSCALE_MODE_H1V2) {
+        const int j = y >> 1, nb = (y & 1) ? (j + 1 < sg.ehC ? j + 1 : sg.ehC - 1) : (j > 0 ? j - 1 : 0);
+        return (3 * p[(size_t)j * sg.strideC + x] + p[(size_t)nb * sg.strideC + x] + 1 + (y & 1)) >> 2;
+    }
+    return p[(size_t)(y / sg.ry) * sg.strideC + x / sg.rx];
 }
 
 // ---- the reduced inverse DCTs -------------------------------------------------------------------------------------------------

@@ -2453,6 +2453,14 @@ def l3ic_decode(data, offsets, lengths, codebook, shape):
 JPEG_SUBSAMPLING = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
 JPEG_BLOCK_BITS_MAX = 1658       # DC 9 + 11 bits, 63 x (AC 16 + 10)
 JPEG_GREY = (0, 0)               # the factor form of a grey-scale file: one component, no chroma to sub-sample
+# The luma sampling factors (hs, vs) over 1x1 chroma that files are read with beyond the three above: 4:4:0, 4:1:1,
+# 4:1:0 and the two upright forms.  Only the ops that read a file or write its coefficients again take them (_JPEG_SAMPLING_ENTRIES).
+JPEG_SAMPLING_WIDE = {'4:4:0': (1, 2), '4:1:1': (4, 1), '4:1:0': (4, 2), '1x4': (1, 4), '2x4': (2, 4)}
+_JPEG_SAMPLING_ENTRIES = {name: name.replace('nimg_jpeg_', 'nimg_jpeg_sampling_').replace('_restart', '') for name in (
+    'nimg_jpeg_decode_restart', 'nimg_jpeg_decode_restart_workspace_bytes', 'nimg_jpeg_decode_progressive',
+    'nimg_jpeg_decode_progressive_workspace_bytes', 'nimg_jpeg_reconstruct_tables', 'nimg_jpeg_reconstruct_scaled',
+    'nimg_jpeg_reconstruct_scaled_workspace_bytes', 'nimg_jpeg_histogram_restart', 'nimg_jpeg_encode_tables_restart',
+    'nimg_jpeg_encode_tables_restart_workspace_bytes')}
 
 
 def jpeg_subsampling(subsampling):
@@ -2461,12 +2469,19 @@ def jpeg_subsampling(subsampling):
     if subsampling == 'grey':
         return JPEG_GREY
     if subsampling not in JPEG_SUBSAMPLING:
-        raise ValueError('Unsupported chrominance sub-sampling: {} (4:4:4, 4:2:2 or 4:2:0)'.format(subsampling))
+        raise ValueError('Unsupported chrominance sub-sampling: {} (4:4:4, 4:2:2 or 4:2:0)'.format(subsampling) + (
+            ': files of this sampling are read and transcoded (allow_sampling), not written from pixels'
+            if isinstance(subsampling, str) and subsampling in JPEG_SAMPLING_WIDE else ''))
     return JPEG_SUBSAMPLING[subsampling]
 
 
 def jpeg_is_grey(hs, vs):
     return (hs, vs) == JPEG_GREY
+
+
+def jpeg_is_wide(hs, vs):
+    """The factors are one of the five samplings of DESIGN.md section 4r, which the nimg_jpeg_sampling_* entry points serve."""
+    return (hs, vs) in JPEG_SAMPLING_WIDE.values()
 
 
 def jpeg_mcu_blocks(hs, vs):
@@ -2478,6 +2493,13 @@ def _jpeg_entry(name, hs, vs, *middle):
     """(entry point, its geometry arguments) of an operation: the colour entry `name` with (hs, vs), or its grey-scale form
     nimg_jpeg_grey_* - one per operation, without factors and without a _restart twin - with `middle`, the restart interval 0 of
     an operation whose colour entry has none."""
+    if jpeg_is_wide(hs, vs):                                        # section 4r: nimg_jpeg_sampling_*, for the ops that have one
+        if name == 'nimg_jpeg_workspace_bytes':                     # a reconstruction's: the scaled one's at scale 1
+            return 'nimg_jpeg_sampling_reconstruct_scaled_workspace_bytes', (hs, vs, 1)
+        if name not in _JPEG_SAMPLING_ENTRIES:
+            raise ValueError('{}: the sampling factors {}x{} are only read from files and written again with their coefficients '
+                             '(decode, reconstruct, histogram, encode_tables)'.format(name.replace('nimg_', ''), hs, vs))
+        return _JPEG_SAMPLING_ENTRIES[name], (hs, vs)
     if not jpeg_is_grey(hs, vs):
         return name, (hs, vs)
     if name == 'nimg_jpeg_encode_restart_workspace_bytes':         # one size serves the pixel stages and the Annex K coder
