@@ -471,6 +471,11 @@ inline bool grid_ok(long items, int per_block) { return (items + per_block - 1) 
 NIMG_HIDDEN int nimg_internal_jpeg_above_one(const float* x, long count, uint32_t* flag, hipStream_t stream);
 // the sample planes of g.n images (as the inverse DCT leaves them) -> y (n,h,w,g.nc): float32 k / 255, or the bytes themselves if u8
 NIMG_HIDDEN int nimg_internal_jpeg_colour(uint8_t* planes, void* y, bool u8, const JpegGeo& g, hipStream_t stream);
+// jpegd.hip's reconstruction with the tables of each file (what nimg_jpeg_[grey_ | sampling_]reconstruct_tables call): coef -> y
+// (n,h,w,nc) as nimg_internal_jpeg_colour leaves it; the workspace is carve(g, nullptr).bytes
+NIMG_HIDDEN int nimg_internal_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, const uint16_t* qtabs,
+                                                      void* y, int out_u8, void* workspace, size_t workspace_bytes, void* stream,
+                                                      int factors = JPEG_FACTORS_THREE);
 // the coder's passes around its bit-length and its emit pass (a raw buffer of raw_words words per image):
 // off[n][SB] bit lengths -> offsets in place, total[n]; the words of raw the bits will be OR-ed into zeroed.  With g.ri the end of an
 // interval that a marker follows is rounded up to a byte and 16 bits are left free behind it.

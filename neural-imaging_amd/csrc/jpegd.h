@@ -107,6 +107,11 @@ JPEGD_HD inline long jpegd_place(const JpegGeo& g, uint32_t b, int& comp) {
     return (br < g.bhY && bc < g.bwY) ? (long)br * g.bwY + bc : -1;
 }
 
+// the scan-order index of the j-th block of component `comp` in an interleaved scan of MCUs of `per` blocks, the first ny of them luma
+JPEGD_HD inline uint32_t jpegd_dc_block(int ny, int per, int comp, int j) {
+    return comp ? (uint32_t)(j * per + ny + comp - 1) : (uint32_t)((j / ny) * per + j % ny);
+}
+
 // Decodes from state `s` until a symbol starts at or beyond `limit` (the caller passes min(next boundary, total_bits)) and leaves
 // the exit state in `s`, the number of blocks begun (DC symbols met) in `begun`.  An invalid code, a category out of range and a
 // symbol that runs beyond total_bits all end the run with s.p = JPEGD_INVALID.  The run belongs to one restart interval (the whole

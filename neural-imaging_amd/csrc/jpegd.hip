@@ -4,15 +4,10 @@
 //   prepare    one workgroup per image: the six Huffman tables from the DHT counts; the segment without its stuffing (FF 00 -> FF),
 //              MSB first in 32-bit words, by a block scan with a carry; the number of subsequences
 //   speculate  one thread per subsequence of subseq_bits bits: decode from the guess (m, z) = (0, 0), store exit state and blocks begun
-//   sync       one workgroup per image: rounds in which thread i decodes subsequence i again from the stored exit state of i - 1,
-//              until a round changes nothing (or all are known to be true); then the exclusive scan of the block counts
+//   sync       one workgroup per image: the rounds of jpegd_sync.h - which also says why their number is the host program's for every
+//              chunking - then the exclusive scan of the block counts
 //   write      one thread per subsequence: decode from the true state; AC values into coef, DC differences into a scan-order array
 //   dc         one workgroup per (image, component): prefix sum of the differences, dummy blocks included, into position 0
-// The rounds are driven inside ONE workgroup per image: the states of an image are exchanged between the threads of a workgroup
-// only, behind its barrier, so nothing waits on another workgroup and no flag crosses a kernel.  An image with more subsequences
-// than the workgroup has threads is walked in chunks from the last to the first, which keeps a round a pure function of the states
-// of the round before (thread i reads i - 1 before any thread of this round has written it): the number of rounds is the same
-// for every chunking, on the host as on the device.
 // The sequential core - tables, block placement, the decode of one subsequence - is jpegd.h, shared with a host program.
 // Files with a restart interval (nimg_jpeg_decode_restart) go through the same kernels, instantiated with
 // RST: prepare also takes the markers FF D0 .. D7 out, checks their sequence and records where every interval begins; the
@@ -21,14 +16,13 @@
 #include "jpegc.h"
 #include "jpegd.h"
 #include "jpegd_prepare.h"
+#include "jpegd_sync.h"
 
 namespace {
 
 constexpr int DEC_THREADS = 256;
 constexpr int SYNC_THREADS = 256;        // the workgroup that synchronises one image; longer images are walked in chunks of it
 constexpr uint32_t SUBSEQ_DEFAULT = 2048;        // the fastest setting measured
-constexpr uint32_t SUBSEQ_MAX = 1u << 30;
-constexpr uint64_t ECD_MAX = (1ull << 28) - 1;        // bytes of one segment: bit positions stay below 2^31
 
 struct DLayout {
     uint32_t* total_bits;        // [n] bits of an image's un-stuffed stream
@@ -71,12 +65,6 @@ DLayout carve_d(const JpegGeo& g, uint64_t ecd_bytes, uint32_t sb, void* base) {
     return d;
 }
 
-bool subseq_ok(int subseq_bits, uint32_t* sb) {
-    if (subseq_bits < 0 || (subseq_bits & 31) || (uint32_t)subseq_bits > SUBSEQ_MAX) return false;
-    *sb = subseq_bits ? (uint32_t)subseq_bits : SUBSEQ_DEFAULT;
-    return true;
-}
-
 struct DArgs {
     const uint8_t* ecd;
     const uint64_t* off;
@@ -103,7 +91,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DL
     const uint64_t o0 = a.off[img], o1 = a.off[img + 1];
     uint32_t* ibit = RST ? d.ibit + (size_t)img * (a.K + 1u) : nullptr;
     uint32_t* sub0 = RST ? d.sub0 + (size_t)img * (a.K + 1u) : nullptr;
-    if (o1 < o0 || o1 > a.ecd_cap || o1 - o0 > ECD_MAX) {               // uniform
+    if (o1 < o0 || o1 > a.ecd_cap || o1 - o0 > JPEGD_ECD_MAX) {               // uniform
         if (tid == 0) {
             atomicOr(a.status + img, JPEGD_ST_OFFSETS);
             d.total_bits[img] = 0; d.nsub[img] = 0;
@@ -117,14 +105,6 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prepare_kernel(DArgs a, DL
                                d.total_bits + img, d.nsub + img, RST ? d.maxsub + img : nullptr);
 }
 
-// the `count` tables of an image into LDS
-__device__ __forceinline__ void load_tables(JpegdTable* dst, const JpegdTable* src, int count, int threads) {
-    const uint32_t* s = (const uint32_t*)src;
-    uint32_t* t = (uint32_t*)dst;
-    for (int k = threadIdx.x; k < (int)(count * sizeof(JpegdTable) / 4); k += threads) t[k] = s[k];
-    __syncthreads();
-}
-
 // ---- speculate / write: one thread per subsequence ------------------------------------------------------------------------
 template <bool WRITE, bool RST>
 __global__ void __launch_bounds__(DEC_THREADS) jpegd_decode_kernel(DArgs a, DLayout d) {
@@ -132,7 +112,7 @@ __global__ void __launch_bounds__(DEC_THREADS) jpegd_decode_kernel(DArgs a, DLay
     const int img = blockIdx.y;
     const uint32_t S = d.nsub[img];
     if (blockIdx.x * DEC_THREADS >= S) return;           // uniform
-    load_tables(tabs, d.tabs + (size_t)img * 2 * a.g.nc, 2 * a.g.nc, DEC_THREADS);
+    jpegd_load_tables(tabs, d.tabs + (size_t)img * 2 * a.g.nc, 2 * a.g.nc, DEC_THREADS);
     const uint64_t o0 = a.off[img];
     const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
     const uint32_t* bits = d.raw + raw_start(o0, img);
@@ -176,7 +156,7 @@ __global__ void __launch_bounds__(SYNC_THREADS) jpegd_sync_kernel(DArgs a, DLayo
         if (tid == 0 && a.rounds) a.rounds[img] = 0;
         return;
     }
-    load_tables(tabs, d.tabs + (size_t)img * 2 * a.g.nc, 2 * a.g.nc, SYNC_THREADS);
+    jpegd_load_tables(tabs, d.tabs + (size_t)img * 2 * a.g.nc, 2 * a.g.nc, SYNC_THREADS);
     const uint64_t o0 = a.off[img];
     const uint32_t nwords = ((uint32_t)(a.off[img + 1] - o0) + 3u) / 4u + 1u, total = d.total_bits[img];
     const uint32_t* bits = d.raw + raw_start(o0, img);
@@ -184,56 +164,22 @@ __global__ void __launch_bounds__(SYNC_THREADS) jpegd_sync_kernel(DArgs a, DLayo
     uint32_t* cnt = d.cnt + slot_start(a, o0, img);
     const uint32_t* ibit = RST ? d.ibit + (size_t)img * (a.K + 1u) : nullptr;
     const uint32_t* sub0 = RST ? d.sub0 + (size_t)img * (a.K + 1u) : nullptr;
-    const uint32_t chunks = (S + SYNC_THREADS - 1) / SYNC_THREADS;
-    const uint32_t longest = RST ? d.maxsub[img] : S;        // the subsequences of the longest interval
-    uint32_t rounds = 0, unused = 0;
-    // after round r the subsequences 0 .. r of every interval are true: the longest interval's - 1 rounds always suffice
-    while (rounds + 1 < longest) {
-        ++rounds;
-        int changed = 0;
-        for (uint32_t c = chunks; c-- > 0;) {
-            const uint32_t i = c * SYNC_THREADS + tid;
-            JpegdSpan sp;
-            bool active = i >= rounds && i < S;
-            if (RST && active) {
-                sp = jpegd_span(a.g, ibit, sub0, a.K, a.sb, i);
-                active = sp.j >= rounds;
-            }
-            JpegdState s;
-            if (active) s = ex[i - 1];
-            __syncthreads();                           // every state of this chunk's predecessors is read before one is written
-            if (active) {
-                const JpegdState old = ex[i];
-                uint32_t begun;
-                if (RST)
-                    jpegd_run_interval<false>(bits, nwords, sp.end, sp.limit, tabs, a.g, s, begun, 0u, 0u, 0u, nullptr, nullptr, unused);
-                else
-                    jpegd_run<false>(bits, nwords, total, min((i + 1u) * a.sb, total), tabs, a.g, s, begun, 0u, nullptr, nullptr, unused);
-                if (s.p != old.p || s.mz != old.mz) changed = 1;
-                ex[i] = s; cnt[i] = begun;
-            }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
-    __syncthreads();
-    uint32_t carry = 0;
-    for (uint32_t c = 0; c < chunks; ++c) {
-        const uint32_t i = c * SYNC_THREADS + tid;
-        const uint32_t v = i < S ? cnt[i] : 0u;
-        uint32_t sum;
-        const uint32_t exq = block_excl_scan<uint32_t, SYNC_THREADS>(v, wtot, sum);
-        if (i < S) cnt[i] = carry + exq;
-        carry += sum;
-    }
-    bool few = !RST && tid == 0 && carry < (uint32_t)a.g.SB;
-    if (RST) {                                             // every interval must have begun its own blocks
-        __syncthreads();
-        const uint32_t per = (uint32_t)a.g.ri * (uint32_t)a.g.per;
-        for (uint32_t k = tid; k < a.K; k += SYNC_THREADS) {
-            const uint32_t begun = (k + 1u < a.K ? cnt[sub0[k + 1u]] : carry) - cnt[sub0[k]];
-            few |= begun < min(per, (uint32_t)a.g.SB - k * per);
-        }
-    }
+    // without restart intervals (a separate instantiation for its instruction count) the scan is the one interval, and sp is not used
+    const auto active = [&](uint32_t i, uint32_t r, JpegdSpan& sp) {
+        if (!RST) return i >= r;
+        sp = jpegd_span(a.g, ibit, sub0, a.K, a.sb, i);
+        return sp.j >= r;
+    };
+    uint32_t unused = 0;                                   // the status of runs that do not write
+    const auto run = [&](uint32_t i, const JpegdSpan& sp, JpegdState& s, uint32_t& begun) {
+        if (RST) jpegd_run_interval<false>(bits, nwords, sp.end, sp.limit, tabs, a.g, s, begun, 0u, 0u, 0u, nullptr, nullptr, unused);
+        else jpegd_run<false>(bits, nwords, total, min((i + 1u) * a.sb, total), tabs, a.g, s, begun, 0u, nullptr, nullptr, unused);
+    };
+    const uint32_t rounds = jpegd_sync_rounds<SYNC_THREADS>(S, RST ? d.maxsub[img] : S, ex, cnt, active, run);
+    const uint32_t begun = jpegd_place_blocks<SYNC_THREADS>(S, cnt, wtot);
+    // every interval must have begun its own blocks
+    const bool few = RST ? jpegd_intervals_short(cnt, sub0, a.K, begun, (uint32_t)a.g.ri * (uint32_t)a.g.per, (uint32_t)a.g.SB, tid, SYNC_THREADS)
+                         : tid == 0 && begun < (uint32_t)a.g.SB;
     if (few) atomicOr(a.status + img, JPEGD_ST_BLOCKS);
     if (tid == 0 && a.rounds) a.rounds[img] = rounds;
 }
@@ -272,7 +218,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_dc_kernel(DArgs a, DLayout
     bool bad = false;
     for (int base = 0; base < count; base += SCAN_THREADS) {
         const int j = base + tid;
-        const uint32_t b = comp ? (uint32_t)(j * a.g.per + ny + comp - 1) : (uint32_t)((j / ny) * a.g.per + j % ny);
+        const uint32_t b = jpegd_dc_block(ny, a.g.per, comp, j);
         const T v = dc_item<T>(j < count ? diff[b] : 0, j % span == 0);
         T sum;
         const int dc = dc_value(carry + block_excl_scan(v, wtot, sum) + v);
@@ -292,8 +238,8 @@ size_t decode_workspace_size(int n, int h, int w, int hs, int vs, int nc, int re
                              int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     uint32_t sb;
-    if (!make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb) ||
-        ecd_bytes > (size_t)n * ECD_MAX)
+    if (!make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval) || !jpegd_subseq_ok(subseq_bits, SUBSEQ_DEFAULT, &sb) ||
+        ecd_bytes > (size_t)n * JPEGD_ECD_MAX)
         return 0;
     return carve_d(g, ecd_bytes, sb, nullptr).bytes;
 }
@@ -304,16 +250,11 @@ int decode_launch(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* hu
     JpegGeo g;
     uint32_t sb;
     if (!ecd || !ecd_off || !huffman || !coef || !status || !workspace || !make_geo(&g, n, h, w, hs, vs, nc, factors) ||
-        !set_restart(&g, restart_interval) || !subseq_ok(subseq_bits, &sb))
+        !set_restart(&g, restart_interval) || !jpegd_subseq_ok(subseq_bits, SUBSEQ_DEFAULT, &sb))
         return NIMG_ERR_ARG;
-    // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
-    if (carve_d(g, 0, sb, workspace).bytes > workspace_bytes) return NIMG_ERR_WORKSPACE;
-    uint64_t lo = 0, hi = (uint64_t)n * ECD_MAX;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (carve_d(g, mid, sb, workspace).bytes <= workspace_bytes) lo = mid;
-        else hi = mid - 1;
-    }
+    const auto bytes_for = [&](uint64_t ecd_bytes) { return carve_d(g, ecd_bytes, sb, workspace).bytes; };
+    if (bytes_for(0) > workspace_bytes) return NIMG_ERR_WORKSPACE;
+    const uint64_t lo = jpegd_ecd_capacity(bytes_for, (uint64_t)n * JPEGD_ECD_MAX, workspace_bytes);
     const DLayout d = carve_d(g, lo, sb, workspace);
     DArgs a;
     a.ecd = ecd; a.off = ecd_off; a.huffman = huffman; a.ecd_cap = lo; a.sb = sb; a.K = jpegd_intervals(g); a.extra = slot_extra(g); a.g = g;
@@ -327,7 +268,7 @@ int decode_launch(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* hu
     else hipLaunchKernelGGL(jpegd_prepare_kernel<false>, dim3((unsigned)n), dim3(SCAN_THREADS), 0, st, a, d);
     NIMG_CHECK_LAUNCH();
     // no valid stream is longer than SB blocks of JPEGD_BLOCK_BITS_MAX bits; a longer (damaged) one is covered by the threads' stride
-    const uint64_t bits_max = min((uint64_t)g.SB * JPEGD_BLOCK_BITS_MAX, 8 * min(lo, ECD_MAX));
+    const uint64_t bits_max = min((uint64_t)g.SB * JPEGD_BLOCK_BITS_MAX, 8 * min(lo, JPEGD_ECD_MAX));
     const uint64_t subs_max = bits_max / sb + (rst ? a.K : 0u);
     const unsigned gx = (unsigned)min((uint64_t)4096, max((uint64_t)1, (subs_max + DEC_THREADS) / DEC_THREADS));
     if (rst) hipLaunchKernelGGL((jpegd_decode_kernel<false, true>), dim3(gx, (unsigned)n), dim3(DEC_THREADS), 0, st, a, d);
@@ -345,8 +286,11 @@ int decode_launch(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* hu
     return NIMG_OK;
 }
 
-int reconstruct_tables_launch(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, const uint16_t* qtabs, void* y, int out_u8,
-                              void* workspace, size_t workspace_bytes, void* stream, int factors = JPEG_FACTORS_THREE) {
+}  // namespace
+
+// declared in jpegc.h: jpegd_scaled.hip calls it for scale 1
+int nimg_internal_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, const uint16_t* qtabs, void* y,
+                                          int out_u8, void* workspace, size_t workspace_bytes, void* stream, int factors) {
     JpegGeo g;
     if (!coef || !y || !qtabs || !workspace || !make_geo(&g, n, h, w, hs, vs, nc, factors)) return NIMG_ERR_ARG;
     const Workspace ws = carve(g, workspace);
@@ -359,8 +303,6 @@ int reconstruct_tables_launch(const int16_t* coef, int n, int h, int w, int hs, 
     NIMG_CHECK_LAUNCH();
     return nimg_internal_jpeg_colour(ws.planes, y, out_u8 != 0, g, st);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -395,7 +337,7 @@ int nimg_jpeg_grey_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uin
 int nimg_jpeg_grey_reconstruct_tables(const int16_t* coef, int n, int h, int w, const uint16_t* qtabs, void* y, int out_u8, void* workspace,
                                       size_t workspace_bytes, void* stream) {
     if (n == 0) return NIMG_OK;
-    return reconstruct_tables_launch(coef, n, h, w, 1, 1, 1, qtabs, y, out_u8, workspace, workspace_bytes, stream);
+    return nimg_internal_jpeg_reconstruct_tables(coef, n, h, w, 1, 1, 1, qtabs, y, out_u8, workspace, workspace_bytes, stream);
 }
 
 int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t* huffman, int n, int h, int w, int hs, int vs,
@@ -407,7 +349,7 @@ int nimg_jpeg_decode(const uint8_t* ecd, const uint64_t* ecd_off, const uint8_t*
 
 int nimg_jpeg_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y, int out_u8,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    return reconstruct_tables_launch(coef, n, h, w, hs, vs, 3, qtabs, y, out_u8, workspace, workspace_bytes, stream);
+    return nimg_internal_jpeg_reconstruct_tables(coef, n, h, w, hs, vs, 3, qtabs, y, out_u8, workspace, workspace_bytes, stream);
 }
 
 // ---- the same launchers with the wide set of sampling factors -----------------------------------------------
@@ -425,7 +367,8 @@ int nimg_jpeg_sampling_decode(const uint8_t* ecd, const uint64_t* ecd_off, const
 
 int nimg_jpeg_sampling_reconstruct_tables(const int16_t* coef, int n, int h, int w, int hs, int vs, const uint16_t* qtabs, void* y,
                                           int out_u8, void* workspace, size_t workspace_bytes, void* stream) {
-    return reconstruct_tables_launch(coef, n, h, w, hs, vs, 3, qtabs, y, out_u8, workspace, workspace_bytes, stream, JPEG_FACTORS_WIDE);
+    return nimg_internal_jpeg_reconstruct_tables(coef, n, h, w, hs, vs, 3, qtabs, y, out_u8, workspace, workspace_bytes, stream,
+                                                 JPEG_FACTORS_WIDE);
 }
 
 }  // extern "C"

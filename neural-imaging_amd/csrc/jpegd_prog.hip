@@ -4,10 +4,8 @@
 //   prepare    one workgroup per (image, scan): the scan's Huffman tables; the segment without its stuffing and restart markers and
 //              the bit every restart interval begins at (jpegd_prepare.h, the baseline decoder's un-stuffing)
 //   first      DC and AC first scans of a level, one workgroup per (image, scan): speculate, synchronise, place and write as section
-//              4e orders them, all four inside the workgroup - an image's states are exchanged behind its barrier only, chunks of
-//              FIRST_THREADS subsequences are walked from the last to the first, so a round is a pure function of the round before and
-//              `rounds` is the host program's whatever the chunking; then, in a DC scan, the sums of the differences per component
-//              and restart interval
+//              4e orders them, all four inside the workgroup, the rounds and the placement by jpegd_sync.h - the baseline decoder's
+//              code; then, in a DC scan, the sums of the differences per component and restart interval
 //   dc refine  one thread per block: its bit is at a known place
 //   ac refine  one wave per (image, scan, restart interval), its blocks in order: which bits a block consumes depends on which of its
 //              coefficients are non-zero already, so nothing can be decoded ahead of its block.  The lanes hold the block's 64
@@ -17,6 +15,7 @@
 #include "jpegc.h"
 #include "jpegd.h"
 #include "jpegd_prepare.h"
+#include "jpegd_sync.h"
 #include "jpegdprog.h"
 
 namespace {
@@ -24,8 +23,6 @@ namespace {
 constexpr int FIRST_THREADS = 256;
 constexpr int REFINE_THREADS = 256;
 constexpr uint32_t PROG_SUBSEQ_DEFAULT = 512;         // the fastest setting measured
-constexpr uint32_t PROG_SUBSEQ_MAX = 1u << 30;
-constexpr uint64_t PROG_ECD_MAX = (1ull << 28) - 1;        // bytes of one segment: bit positions stay below 2^31
 
 struct PScript {
     int n_scans;
@@ -70,12 +67,6 @@ PLayout carve_p(const JpegGeo& g, int n_scans, uint64_t ecd_bytes, uint32_t sb, 
     return d;
 }
 
-bool prog_subseq_ok(int subseq_bits, uint32_t* sb) {
-    if (subseq_bits < 0 || (subseq_bits & 31) || (uint32_t)subseq_bits > PROG_SUBSEQ_MAX) return false;
-    *sb = subseq_bits ? (uint32_t)subseq_bits : PROG_SUBSEQ_DEFAULT;
-    return true;
-}
-
 struct PArgs {
     const uint8_t* ecd;
     const uint64_t* off;
@@ -116,7 +107,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prog_prepare_kernel(PArgs 
     const size_t q = (size_t)img * a.script.n_scans + scan;
     const uint64_t o0 = a.off[q], o1 = a.off[q + 1];
     if (tid == 0) a.rounds[q] = 0;
-    if (o1 < o0 || o1 > a.ecd_cap || o1 - o0 > PROG_ECD_MAX) {          // uniform
+    if (o1 < o0 || o1 > a.ecd_cap || o1 - o0 > JPEGD_ECD_MAX) {          // uniform
         if (tid == 0) {
             atomicOr(a.status + img, JPEGD_ST_OFFSETS);
             d.total_bits[q] = 0; d.nsub[q] = 0; d.maxsub[q] = 0;
@@ -136,13 +127,6 @@ __global__ void __launch_bounds__(SCAN_THREADS) jpegd_prog_prepare_kernel(PArgs 
     }
 }
 
-__device__ __forceinline__ void load_scan_tables(JpegdTable* dst, const JpegdTable* src, int count, int threads) {
-    const uint32_t* s = (const uint32_t*)src;
-    uint32_t* t = (uint32_t*)dst;
-    for (int k = threadIdx.x; k < (int)(count * sizeof(JpegdTable) / 4); k += threads) t[k] = s[k];
-    __syncthreads();
-}
-
 // ---- first scans of a level: one workgroup per (image, scan) ---------------------------------------------------------------------
 __global__ void __launch_bounds__(FIRST_THREADS) jpegd_prog_first_kernel(PArgs a, PLayout d, int level) {
     __shared__ JpegdTable tabs[3];
@@ -153,7 +137,7 @@ __global__ void __launch_bounds__(FIRST_THREADS) jpegd_prog_first_kernel(PArgs a
     const size_t q = (size_t)img * a.script.n_scans + scan;
     const uint32_t S = d.nsub[q];
     if (S == 0) return;
-    load_scan_tables(tabs, d.tabs + q * 3, 3, FIRST_THREADS);
+    jpegd_load_tables(tabs, d.tabs + q * 3, 3, FIRST_THREADS);
     const JpegGeo cg = jpegdprog_geo(a.g, sc);
     const uint32_t K = jpegd_intervals(cg);
     const PSeg sg = segment(a, d, q);
@@ -174,53 +158,18 @@ __global__ void __launch_bounds__(FIRST_THREADS) jpegd_prog_first_kernel(PArgs a
         ex[i] = s; cnt[i] = done;
     }
     __syncthreads();
-    // synchronise: after round r the subsequences 0 .. r of every interval are true
-    const uint32_t longest = d.maxsub[q];
-    uint32_t rounds = 0;
-    while (rounds + 1 < longest) {
-        ++rounds;
-        int changed = 0;
-        for (uint32_t c = chunks; c-- > 0;) {
-            const uint32_t i = c * FIRST_THREADS + tid;
-            JpegdSpan sp;
-            bool active = i >= rounds && i < S;
-            if (active) {
-                sp = jpegd_span(cg, sg.ibit, sg.sub0, K, a.sb, i);
-                active = sp.j >= rounds;
-            }
-            JpegdState s;
-            if (active) s = ex[i - 1];
-            __syncthreads();                           // every state of this chunk's predecessors is read before one is written
-            if (active) {
-                const JpegdState old = ex[i];
-                uint32_t done;
-                jpegdprog_run_first<false>(sg.bits, sg.nwords, sp.end, sp.limit, tabs, a.g, sc, cg.per, s, done, 0u, 0u, 0u, nullptr, nullptr,
-                                           unused);
-                if (s.p != old.p || s.mz != old.mz) changed = 1;
-                ex[i] = s; cnt[i] = done;
-            }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
-    __syncthreads();
-    // place: the first block every subsequence completes
-    uint32_t carry = 0;
-    for (uint32_t c = 0; c < chunks; ++c) {
-        const uint32_t i = c * FIRST_THREADS + tid;
-        const uint32_t v = i < S ? cnt[i] : 0u;
-        uint32_t sum;
-        const uint32_t exq = block_excl_scan<uint32_t, FIRST_THREADS>(v, wtot, sum);
-        if (i < S) cnt[i] = carry + exq;
-        carry += sum;
-    }
-    __syncthreads();
-    const uint32_t per = jpegdprog_interval_blocks(cg);
-    bool few = false;
-    for (uint32_t k = tid; k < K; k += FIRST_THREADS) {
-        const uint32_t have = (k + 1u < K ? cnt[sg.sub0[k + 1u]] : carry) - cnt[sg.sub0[k]];
-        few |= have < min(per, (uint32_t)cg.SB - k * per);
-    }
-    uint32_t status = few ? JPEGD_ST_BLOCKS : 0u;
+    // synchronise (jpegd_sync.h), then place: the first block every subsequence completes
+    const auto active = [&](uint32_t i, uint32_t r, JpegdSpan& sp) {
+        sp = jpegd_span(cg, sg.ibit, sg.sub0, K, a.sb, i);
+        return sp.j >= r;
+    };
+    const auto run = [&](uint32_t, const JpegdSpan& sp, JpegdState& s, uint32_t& done) {
+        jpegdprog_run_first<false>(sg.bits, sg.nwords, sp.end, sp.limit, tabs, a.g, sc, cg.per, s, done, 0u, 0u, 0u, nullptr, nullptr, unused);
+    };
+    const uint32_t rounds = jpegd_sync_rounds<FIRST_THREADS>(S, d.maxsub[q], ex, cnt, active, run);
+    const uint32_t completed = jpegd_place_blocks<FIRST_THREADS>(S, cnt, wtot);
+    const uint32_t per = jpegdprog_interval_blocks(cg);        // every interval must have completed its own blocks
+    uint32_t status = jpegd_intervals_short(cnt, sg.sub0, K, completed, per, (uint32_t)cg.SB, tid, FIRST_THREADS) ? JPEGD_ST_BLOCKS : 0u;
     // write
     for (uint32_t c = 0; c < chunks; ++c) {
         const uint32_t i = c * FIRST_THREADS + tid;
@@ -243,7 +192,7 @@ __global__ void __launch_bounds__(FIRST_THREADS) jpegd_prog_first_kernel(PArgs a
             int sums = 0;
             for (int base = 0; base < count; base += FIRST_THREADS) {
                 const int j = base + tid;
-                const uint32_t b = sc.mask != 7 ? (uint32_t)j : (comp ? (uint32_t)(j * cg.per + ny + comp - 1) : (uint32_t)((j / ny) * cg.per + j % ny));
+                const uint32_t b = sc.mask != 7 ? (uint32_t)j : jpegd_dc_block(ny, cg.per, comp, j);
                 const int v = j < count ? dcdiff[jpegdprog_dc_slot(a.g, sc, b)] : 0;
                 int sum;
                 const int incl = sums + block_excl_scan<int, FIRST_THREADS>(v, (int*)wtot, sum) + v;
@@ -253,10 +202,8 @@ __global__ void __launch_bounds__(FIRST_THREADS) jpegd_prog_first_kernel(PArgs a
             __syncthreads();
             for (int j = tid; j < count; j += FIRST_THREADS) {
                 const int first = j / span * span;
-                const uint32_t b = sc.mask != 7 ? (uint32_t)j : (comp ? (uint32_t)(j * cg.per + ny + comp - 1) : (uint32_t)((j / ny) * cg.per + j % ny));
-                const uint32_t bf = sc.mask != 7 ? (uint32_t)(first - 1)
-                                                 : (comp ? (uint32_t)((first - 1) * cg.per + ny + comp - 1)
-                                                         : (uint32_t)(((first - 1) / ny) * cg.per + (first - 1) % ny));
+                const uint32_t b = sc.mask != 7 ? (uint32_t)j : jpegd_dc_block(ny, cg.per, comp, j);
+                const uint32_t bf = sc.mask != 7 ? (uint32_t)(first - 1) : jpegd_dc_block(ny, cg.per, comp, first - 1);
                 const int sum = dcdiff[jpegdprog_dc_slot(a.g, sc, b)] - (first ? dcdiff[jpegdprog_dc_slot(a.g, sc, bf)] : 0);
                 status |= jpegdprog_dc_store(coef, jpegdprog_place(a.g, sc, b), sum, sc.al);
             }
@@ -297,7 +244,7 @@ __global__ void __launch_bounds__(64) jpegd_prog_ac_refine_kernel(PArgs a, PLayo
     const JpegGeo cg = jpegdprog_geo(a.g, sc);
     const uint32_t k = blockIdx.x, per = jpegdprog_interval_blocks(cg);
     if (k >= jpegd_intervals(cg)) return;
-    load_scan_tables(&tab, d.tabs + q * 3, 1, 64);
+    jpegd_load_tables(&tab, d.tabs + q * 3, 1, 64);
     const PSeg sg = segment(a, d, q);
     const uint32_t b0 = k * per, nb = min(b0 + per, (uint32_t)cg.SB) - b0, end = sg.ibit[k + 1u];
     int16_t* blk = a.coef + ((size_t)img * a.g.NB + (size_t)jpegdprog_place(a.g, sc, b0)) * 64;
@@ -383,8 +330,8 @@ size_t progressive_workspace_size(int n, int h, int w, int hs, int vs, int nc, i
                                   int subseq_bits, int factors = JPEG_FACTORS_THREE) {
     JpegGeo g;
     uint32_t sb;
-    if (!make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || n_scans < 1 ||
-        n_scans > JPEGDPROG_SCANS_MAX || ecd_bytes > (size_t)n * n_scans * PROG_ECD_MAX)
+    if (!make_geo(&g, n, h, w, hs, vs, nc, factors) || !set_restart(&g, restart_interval) || !jpegd_subseq_ok(subseq_bits, PROG_SUBSEQ_DEFAULT, &sb) || n_scans < 1 ||
+        n_scans > JPEGDPROG_SCANS_MAX || ecd_bytes > (size_t)n * n_scans * JPEGD_ECD_MAX)
         return 0;
     return carve_p(g, n_scans, ecd_bytes, sb, nullptr).bytes;
 }
@@ -397,16 +344,11 @@ int progressive_launch(const uint8_t* ecd, const uint64_t* ecd_off, const int32_
     PArgs a;
     int top;
     if (!ecd || !ecd_off || !huffman || !coef || !status || !rounds || !workspace || !make_geo(&g, n, h, w, hs, vs, nc, factors) ||
-        !set_restart(&g, restart_interval) || !prog_subseq_ok(subseq_bits, &sb) || !take_script(script, n_scans, nc, &a.script, &top))
+        !set_restart(&g, restart_interval) || !jpegd_subseq_ok(subseq_bits, PROG_SUBSEQ_DEFAULT, &sb) || !take_script(script, n_scans, nc, &a.script, &top))
         return NIMG_ERR_ARG;
-    // the offsets are on the device: the largest total the workspace serves bounds every index derived from them
-    if (carve_p(g, n_scans, 0, sb, workspace).bytes > workspace_bytes) return NIMG_ERR_ARG;
-    uint64_t lo = 0, hi = (uint64_t)n * n_scans * PROG_ECD_MAX;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (carve_p(g, n_scans, mid, sb, workspace).bytes <= workspace_bytes) lo = mid;
-        else hi = mid - 1;
-    }
+    const auto bytes_for = [&](uint64_t ecd_bytes) { return carve_p(g, n_scans, ecd_bytes, sb, workspace).bytes; };
+    if (bytes_for(0) > workspace_bytes) return NIMG_ERR_ARG;
+    const uint64_t lo = jpegd_ecd_capacity(bytes_for, (uint64_t)n * n_scans * JPEGD_ECD_MAX, workspace_bytes);
     const PLayout d = carve_p(g, n_scans, lo, sb, workspace);
     a.ecd = ecd; a.off = ecd_off; a.huffman = huffman; a.ecd_cap = lo; a.sb = sb; a.Kmax = intervals_max(g); a.g = g;
     a.coef = coef; a.status = status; a.rounds = rounds;

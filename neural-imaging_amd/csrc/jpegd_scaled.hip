@@ -6,7 +6,7 @@
 //   colour   one thread per output pixel: the luma sample, the chroma samples - as wide as the output, or for 4:2:2 half as wide and
 //            brought up by jpegc.h's h2v1 triangle filter or by replication, as libjpeg chooses at that scale - colour, clamp,
 //            the byte or k / 255
-// The geometry and the transforms are jpegscale.h, shared with a host program.  Scale 1 is nimg_jpeg_reconstruct_tables itself.
+// The geometry and the transforms are jpegscale.h, shared with a host program.  Scale 1 is jpegd.hip's launcher behind nimg_jpeg_reconstruct_tables.
 #include "jpegc.h"
 #include "jpegscale.h"
 
@@ -158,8 +158,7 @@ size_t scaled_workspace_size(int n, int h, int w, int hs, int vs, int nc, int sc
     JpegGeo g;
     JpegScaleGeo sg;
     if (!jpegscale_ok(scale) || !make_geo(&g, n, h, w, hs, vs, nc, factors)) return 0;
-    if (scale == 1 && factors == JPEG_FACTORS_WIDE) return carve(g, nullptr).bytes;        // what nimg_jpeg_workspace_bytes counts
-    if (scale == 1) return nc == 1 ? nimg_jpeg_grey_workspace_bytes(n, h, w, 0) : nimg_jpeg_workspace_bytes(n, h, w, hs, vs);
+    if (scale == 1) return carve(g, nullptr).bytes;        // what nimg_jpeg_workspace_bytes counts
     return make_scale_geo(&sg, g, scale) ? align256((size_t)n * sg.per) : 0;
 }
 
@@ -168,11 +167,8 @@ int reconstruct_scaled_launch(const int16_t* coef, int n, int h, int w, int hs, 
     JpegGeo g;
     JpegScaleGeo sg;
     if (!coef || !y || !qtabs || !workspace || !jpegscale_ok(scale) || !make_geo(&g, n, h, w, hs, vs, nc, factors)) return NIMG_ERR_ARG;
-    if (scale == 1 && factors == JPEG_FACTORS_WIDE)
-        return nimg_jpeg_sampling_reconstruct_tables(coef, n, h, w, hs, vs, qtabs, y, out_u8, workspace, workspace_bytes, stream);
     if (scale == 1)
-        return nc == 1 ? nimg_jpeg_grey_reconstruct_tables(coef, n, h, w, qtabs, y, out_u8, workspace, workspace_bytes, stream)
-                       : nimg_jpeg_reconstruct_tables(coef, n, h, w, hs, vs, qtabs, y, out_u8, workspace, workspace_bytes, stream);
+        return nimg_internal_jpeg_reconstruct_tables(coef, n, h, w, hs, vs, nc, qtabs, y, out_u8, workspace, workspace_bytes, stream, factors);
     if (!make_scale_geo(&sg, g, scale)) return NIMG_ERR_ARG;
     if (workspace_bytes < align256((size_t)n * sg.per)) return NIMG_ERR_WORKSPACE;
     const long blocks = (long)n * g.NB, pixels = (long)n * sg.oh * sg.ow;

@@ -2717,6 +2717,46 @@ def jpeg_reconstruct_items(coef, h, w, quality, hs=1, vs=1, workspace=None, out=
 
 
 JPEG_SUBSEQ_BITS_MAX = 1 << 30
+JPEG_SCANS_MAX = 64
+
+
+def _jpeg_decode(name, entry, ecd, ecd_off, huffman, script, tables, h, w, hs, vs, subseq_bits, workspace, restart_interval):
+    """The body of jpeg_decode and jpeg_decode_progressive: the library's `entry`, its workspace sized by `entry`_workspace_bytes, on
+    the segments of n files -> (coefficients, status (n,), rounds).  script: None for baseline files - one segment each, rounds (n,) -
+    or the scan script, which the entry then takes with the number of its scans - n_scans segments each, rounds (n, n_scans).
+    tables: the shape of the Huffman tables of one file, or of one scan of it."""
+    _chk(ecd)
+    _chk(ecd_off)
+    _chk(huffman)
+    if script is None:
+        per, scans, offsets = 1, (), 'n'                            # segments of one file; the axis they add; how the message counts them
+    else:
+        script = np.ascontiguousarray(script, np.int32)
+        if script.ndim != 2 or script.shape[1] != 6 or not 1 <= script.shape[0] <= JPEG_SCANS_MAX:
+            raise RuntimeError('{}: script {}, (1..{}, 6) int32 needed'.format(name, script.shape, JPEG_SCANS_MAX))
+        per = script.shape[0]
+        scans, offsets = (per,), 'n * {}'.format(per)
+    n = (ecd_off.numel() - 1) // per
+    if ecd.dtype != torch.uint8 or ecd_off.dtype != torch.int64 or n < 1 or ecd_off.numel() != n * per + 1:
+        raise RuntimeError('{}: uint8 segments and ({} + 1,) int64 offsets needed, got {} and {} {}'.format(
+            name, offsets, ecd.dtype, ecd_off.dtype, tuple(ecd_off.shape)))
+    shape = (n,) + scans + tables
+    if huffman.dtype != torch.uint8 or tuple(huffman.shape) != shape:
+        raise RuntimeError('{}: Huffman tables {} {}, {} uint8 needed'.format(name, huffman.dtype, tuple(huffman.shape), shape))
+    subseq_bits = int(subseq_bits)
+    ri = jpeg_restart_interval(restart_interval)
+    entry, factors = _jpeg_entry(entry, hs, vs)
+    batch = _jpeg_batch(n, h, w, hs, vs) + (' scans={}'.format(per) if scans else '')
+    size = getattr(_lib.load(), entry + '_workspace_bytes')
+    workspace, _ = _jpeg_workspace(size(n, h, w, *factors, ri, *scans, ecd.numel(), subseq_bits),
+                                   '{} subseq_bits={}'.format(batch, subseq_bits), ecd.device, workspace, name='JPEG decode workspace')
+    coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
+    status = torch.empty(n, dtype=torch.int32, device=ecd.device)
+    rounds = torch.empty((n,) + scans, dtype=torch.int32, device=ecd.device)
+    script_args = () if script is None else (script.ctypes.data, per)
+    _lib.call(entry, _p(ecd), _p(ecd_off), *script_args, _p(huffman), n, h, w, *factors, ri, subseq_bits, _p(coef), _p(status),
+              _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    return coef, status, rounds
 
 
 def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspace=None, *, restart_interval=0):
@@ -2728,32 +2768,8 @@ def jpeg_decode(ecd, ecd_off, huffman, h, w, hs=1, vs=1, subseq_bits=0, workspac
     of 32, 0 = the default; at least the stream = a sequential decode).
     restart_interval: the DRI value the files share (nimg_jpeg_decode_restart) - their markers FF D0 .. D7 are taken out and checked
     (status bit 512), and every interval is decoded from its own known start; 0 = files without markers."""
-    _chk(ecd)
-    _chk(ecd_off)
-    _chk(huffman)
-    n = ecd_off.numel() - 1
-    if ecd.dtype != torch.uint8 or ecd_off.dtype != torch.int64 or n < 1:
-        raise RuntimeError('jpeg_decode: uint8 segments and (n + 1,) int64 offsets needed, got {} and {} {}'.format(
-            ecd.dtype, ecd_off.dtype, tuple(ecd_off.shape)))
-    n_tables = 2 if jpeg_is_grey(hs, vs) else 6
-    if huffman.dtype != torch.uint8 or tuple(huffman.shape) != (n, n_tables, 272):
-        raise RuntimeError('jpeg_decode: Huffman tables {} {}, ({}, {}, 272) uint8 needed'.format(huffman.dtype, tuple(huffman.shape), n,
-                                                                                                  n_tables))
-    subseq_bits = int(subseq_bits)
-    ri = jpeg_restart_interval(restart_interval)
-    entry, factors = _jpeg_entry('nimg_jpeg_decode_restart', hs, vs)
-    workspace, _ = _jpeg_workspace(getattr(_lib.load(), entry + '_workspace_bytes')(n, h, w, *factors, ri, ecd.numel(), subseq_bits),
-                                   '{} subseq_bits={}'.format(_jpeg_batch(n, h, w, hs, vs), subseq_bits), ecd.device, workspace,
-                                   name='JPEG decode workspace')
-    coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
-    status = torch.empty(n, dtype=torch.int32, device=ecd.device)
-    rounds = torch.empty(n, dtype=torch.int32, device=ecd.device)
-    _lib.call(entry, _p(ecd), _p(ecd_off), _p(huffman), n, h, w, *factors, ri, subseq_bits, _p(coef), _p(status), _p(rounds),
-              _p(workspace), workspace.numel() * workspace.element_size(), _stream())
-    return coef, status, rounds
-
-
-JPEG_SCANS_MAX = 64
+    return _jpeg_decode('jpeg_decode', 'nimg_jpeg_decode_restart', ecd, ecd_off, huffman, None, (2 if jpeg_is_grey(hs, vs) else 6, 272),
+                        h, w, hs, vs, subseq_bits, workspace, restart_interval)
 
 
 def jpeg_decode_progressive(ecd, ecd_off, huffman, script, h, w, hs=1, vs=1, subseq_bits=0, workspace=None, *, restart_interval=0):
@@ -2765,55 +2781,8 @@ def jpeg_decode_progressive(ecd, ecd_off, huffman, script, h, w, hs=1, vs=1, sub
     (n_scans, 6) int32 on the host - component mask, Ss, Se, Ah, Al, level.  A script that breaks the rules of the header comment is
     refused by the library (NIMG_ERR_ARG) before anything is launched.  Grey-scale files (hs, vs = JPEG_GREY): every scan's mask is 1,
     and slot 0 of its tables alone is read."""
-    _chk(ecd)
-    _chk(ecd_off)
-    _chk(huffman)
-    script = np.ascontiguousarray(script, np.int32)
-    if script.ndim != 2 or script.shape[1] != 6 or not 1 <= script.shape[0] <= JPEG_SCANS_MAX:
-        raise RuntimeError('jpeg_decode_progressive: script {}, (1..{}, 6) int32 needed'.format(script.shape, JPEG_SCANS_MAX))
-    n_scans = script.shape[0]
-    n = (ecd_off.numel() - 1) // n_scans
-    if ecd.dtype != torch.uint8 or ecd_off.dtype != torch.int64 or n < 1 or ecd_off.numel() != n * n_scans + 1:
-        raise RuntimeError('jpeg_decode_progressive: uint8 segments and (n * {} + 1,) int64 offsets needed, got {} and {} {}'.format(
-            n_scans, ecd.dtype, ecd_off.dtype, tuple(ecd_off.shape)))
-    if huffman.dtype != torch.uint8 or tuple(huffman.shape) != (n, n_scans, 3, 272):
-        raise RuntimeError('jpeg_decode_progressive: Huffman tables {} {}, ({}, {}, 3, 272) uint8 needed'.format(
-            huffman.dtype, tuple(huffman.shape), n, n_scans))
-    subseq_bits = int(subseq_bits)
-    ri = jpeg_restart_interval(restart_interval)
-    entry, factors = _jpeg_entry('nimg_jpeg_decode_progressive', hs, vs)
-    workspace, _ = _jpeg_workspace(
-        getattr(_lib.load(), entry + '_workspace_bytes')(n, h, w, *factors, ri, n_scans, ecd.numel(), subseq_bits),
-        '{} scans={} subseq_bits={}'.format(_jpeg_batch(n, h, w, hs, vs), n_scans, subseq_bits), ecd.device, workspace,
-        name='JPEG decode workspace')
-    coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
-    status = torch.empty(n, dtype=torch.int32, device=ecd.device)
-    rounds = torch.empty((n, n_scans), dtype=torch.int32, device=ecd.device)
-    _lib.call(entry, _p(ecd), _p(ecd_off), script.ctypes.data, n_scans, _p(huffman), n, h, w, *factors, ri,
-              subseq_bits, _p(coef), _p(status), _p(rounds), _p(workspace), workspace.numel() * workspace.element_size(), _stream())
-    return coef, status, rounds
-
-
-def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspace=None, out=None):
-    """jpeg_reconstruct with the quantisation tables given per image and component: qtabs (n, 3, 64) uint16 (or int16 bit patterns)
-    in natural order.  Returns (n,h,w,3) uint8 - the bytes libjpeg decodes - when out_u8, else float32 = byte / 255.  Grey-scale
-    (hs, vs = JPEG_GREY): qtabs (n, 1, 64) and an (n,h,w,1) image."""
-    _chk(coef)
-    _chk(qtabs)
-    n = _jpeg_coef('jpeg_reconstruct_tables', coef, h, w, hs, vs)
-    nc = 1 if jpeg_is_grey(hs, vs) else 3
-    if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, nc, 64):
-        raise RuntimeError('jpeg_reconstruct_tables: tables {} {}, ({}, {}, 64) 16-bit integers needed'.format(qtabs.dtype, tuple(qtabs.shape),
-                                                                                                             n, nc))
-    ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
-    dtype = torch.uint8 if out_u8 else torch.float32
-    y = torch.empty((n, h, w, nc), dtype=dtype, device=coef.device) if out is None else out
-    _chk(y)
-    if y.dtype != dtype or tuple(y.shape) != (n, h, w, nc):
-        raise RuntimeError('jpeg_reconstruct_tables: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, (n, h, w, nc)))
-    entry, factors = _jpeg_entry('nimg_jpeg_reconstruct_tables', hs, vs)
-    _lib.call(entry, _p(coef), n, h, w, *factors, _p(qtabs), _p(y), int(bool(out_u8)), _p(ws), need, _stream())
-    return y
+    return _jpeg_decode('jpeg_decode_progressive', 'nimg_jpeg_decode_progressive', ecd, ecd_off, huffman, script, (3, 272), h, w, hs, vs,
+                        subseq_bits, workspace, restart_interval)
 
 
 JPEG_SCALES = (1, 2, 4, 8)       # the denominators of libjpeg's scale_num / scale_denom that the codec reads at (DESIGN.md section 4q)
@@ -2832,29 +2801,46 @@ def jpeg_scaled_size(h, w, scale):
     return -(-h // scale), -(-w // scale)
 
 
+def _jpeg_reconstruct_tables(name, entry, coef, h, w, qtabs, scale, hs, vs, out_u8, workspace, out):
+    """The body of jpeg_reconstruct_tables (scale None: the workspace of the pixel stages) and of jpeg_reconstruct_scaled (a checked
+    scale, which the library's `entry` takes behind the tables, and the workspace `entry`_workspace_bytes counts)."""
+    _chk(coef)
+    _chk(qtabs)
+    n = _jpeg_coef(name, coef, h, w, hs, vs)
+    nc = 1 if jpeg_is_grey(hs, vs) else 3
+    if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, nc, 64):
+        raise RuntimeError('{}: tables {} {}, {} 16-bit integers needed'.format(name, qtabs.dtype, tuple(qtabs.shape), (n, nc, 64)))
+    if scale is None:
+        ws, need = _jpeg_pixel_workspace(n, h, w, hs, vs, coef.device, workspace)
+    else:
+        size, factors = _jpeg_entry(entry + '_workspace_bytes', hs, vs)
+        ws, need = _jpeg_workspace(getattr(_lib.load(), size)(n, h, w, *factors, scale), _jpeg_batch(n, h, w, hs, vs), coef.device, workspace)
+    dtype, shape = torch.uint8 if out_u8 else torch.float32, (n,) + jpeg_scaled_size(h, w, scale or 1) + (nc,)
+    y = torch.empty(shape, dtype=dtype, device=coef.device) if out is None else out
+    _chk(y)
+    if y.dtype != dtype or tuple(y.shape) != shape:
+        raise RuntimeError('{}: output {} {}, {} {} needed'.format(name, y.dtype, tuple(y.shape), dtype, shape))
+    entry, factors = _jpeg_entry(entry, hs, vs)
+    scale_arg = () if scale is None else (scale,)
+    _lib.call(entry, _p(coef), n, h, w, *factors, _p(qtabs), *scale_arg, _p(y), int(bool(out_u8)), _p(ws), need, _stream())
+    return y
+
+
+def jpeg_reconstruct_tables(coef, h, w, qtabs, hs=1, vs=1, out_u8=False, workspace=None, out=None):
+    """jpeg_reconstruct with the quantisation tables given per image and component: qtabs (n, 3, 64) uint16 (or int16 bit patterns)
+    in natural order.  Returns (n,h,w,3) uint8 - the bytes libjpeg decodes - when out_u8, else float32 = byte / 255.  Grey-scale
+    (hs, vs = JPEG_GREY): qtabs (n, 1, 64) and an (n,h,w,1) image."""
+    return _jpeg_reconstruct_tables('jpeg_reconstruct_tables', 'nimg_jpeg_reconstruct_tables', coef, h, w, qtabs, None, hs, vs, out_u8,
+                                    workspace, out)
+
+
 def jpeg_reconstruct_scaled(coef, h, w, qtabs, scale, hs=1, vs=1, out_u8=False, workspace=None, out=None):
     """jpeg_reconstruct_tables at 1 / scale (scale 1, 2, 4 or 8): the (n, ceil(h / scale), ceil(w / scale), 3) image libjpeg decodes
     with scale_num / scale_denom = 1 / scale - what Pillow returns after Image.draft() - by the reduced inverse DCTs, bit for bit.
     Grey-scale (hs, vs = JPEG_GREY): (.., .., 1).  scale 1 is jpeg_reconstruct_tables.  The workspace is
     nimg_jpeg_reconstruct_scaled_workspace_bytes."""
-    scale = jpeg_scale(scale)
-    _chk(coef)
-    _chk(qtabs)
-    n = _jpeg_coef('jpeg_reconstruct_scaled', coef, h, w, hs, vs)
-    nc = 1 if jpeg_is_grey(hs, vs) else 3
-    if qtabs.element_size() != 2 or qtabs.is_floating_point() or tuple(qtabs.shape) != (n, nc, 64):
-        raise RuntimeError('jpeg_reconstruct_scaled: tables {} {}, ({}, {}, 64) 16-bit integers needed'.format(qtabs.dtype, tuple(qtabs.shape),
-                                                                                                             n, nc))
-    size, factors = _jpeg_entry('nimg_jpeg_reconstruct_scaled_workspace_bytes', hs, vs)
-    ws, need = _jpeg_workspace(getattr(_lib.load(), size)(n, h, w, *factors, scale), _jpeg_batch(n, h, w, hs, vs), coef.device, workspace)
-    dtype, shape = torch.uint8 if out_u8 else torch.float32, (n,) + jpeg_scaled_size(h, w, scale) + (nc,)
-    y = torch.empty(shape, dtype=dtype, device=coef.device) if out is None else out
-    _chk(y)
-    if y.dtype != dtype or tuple(y.shape) != shape:
-        raise RuntimeError('jpeg_reconstruct_scaled: output {} {}, {} {} needed'.format(y.dtype, tuple(y.shape), dtype, shape))
-    entry, factors = _jpeg_entry('nimg_jpeg_reconstruct_scaled', hs, vs)
-    _lib.call(entry, _p(coef), n, h, w, *factors, _p(qtabs), scale, _p(y), int(bool(out_u8)), _p(ws), need, _stream())
-    return y
+    return _jpeg_reconstruct_tables('jpeg_reconstruct_scaled', 'nimg_jpeg_reconstruct_scaled', coef, h, w, qtabs, jpeg_scale(scale), hs, vs,
+                                    out_u8, workspace, out)
 
 
 # optimised Huffman tables (DESIGN.md section 4f): a table is 16 counts + 256 symbols in code order, an image has four of them in
