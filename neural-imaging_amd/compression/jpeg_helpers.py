@@ -34,6 +34,7 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
 """
 import functools
+import re
 import struct
 from collections import OrderedDict, namedtuple
 
@@ -203,10 +204,24 @@ def _colour_only(what, grey):
         raise ValueError('grey-scale (one-component) images: {} is not supported'.format(what))
 
 
+_PROGRESSIVE_GREY = 'progressive=True (writing the six scans libjpeg writes for one component)'
+
+
+def _factors(subsampling):
+    """The factors (hs, vs) of what a caller names a geometry by: a name of ops.JPEG_SUBSAMPLING or 'grey' (ops.jpeg_subsampling: by name the
+    samplings that are only read stay refused, as writing them from pixels is), or the factors themselves - ops.JPEG_GREY and the pairs
+    of ops.JPEG_SAMPLING_WIDE too, which transcode_batch passes for the file it writes again."""
+    return subsampling if isinstance(subsampling, tuple) else ops.jpeg_subsampling(subsampling)
+
+
+def _grey_shape(shape):                  # an image (h,w,1) or a batch (n,h,w,1): one component
+    return len(shape) in (3, 4) and shape[-1] == 1
+
+
 def _grey_input(shape, subsampling, name):
     """The sub-sampling a batch of `shape` is coded with: 'grey' for (..., 1) - which takes no other than the default or 'grey' itself,
     there being no chroma to sub-sample -, else `subsampling`, which is then not 'grey'."""
-    if len(shape) in (3, 4) and shape[-1] == 1:
+    if _grey_shape(shape):
         if subsampling not in ('4:4:4', 'grey'):
             raise ValueError('{}: grey-scale input {} takes no chroma sub-sampling, got {!r}'.format(name, tuple(shape), subsampling))
         return 'grey'
@@ -230,7 +245,7 @@ def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qt
         raise ValueError('huffman: the (10, 272) uint8 tables of a progressive file are needed, got {}'.format(
             None if huffman is None else (huffman.dtype, huffman.shape)))
     ri = ops.jpeg_restart_interval(restart_interval)
-    _colour_only('progressive=True (writing the six scans libjpeg writes for one component)', subsampling == 'grey')
+    _colour_only(_PROGRESSIVE_GREY, ops.jpeg_is_grey(*_factors(subsampling)))
     base = _jpeg_header(h, w, quality, subsampling, None, qtables, 0)
     dht = _header_bytes(None if qtables is None else check_qtables(qtables))[1]
     sof = dht - 19
@@ -249,9 +264,7 @@ def jpeg_progressive_pieces(h, w, quality, subsampling='4:4:4', huffman=None, qt
 
 
 def _jpeg_header(h, w, quality, subsampling, huffman, qtables, restart_interval):
-    # a file that is written again may have one of the samplings that are only read: transcode_batch passes their
-    # factors themselves, (hs, vs); by name they stay refused, as writing them from pixels is
-    hs, vs = subsampling if isinstance(subsampling, tuple) else ops.jpeg_subsampling(subsampling)
+    hs, vs = _factors(subsampling)
     grey = ops.jpeg_is_grey(hs, vs)
     ri = ops.jpeg_restart_interval(restart_interval)
     quality, qtables = _quality_or_tables(quality, qtables, clamp=True, grey=grey)
@@ -261,22 +274,18 @@ def _jpeg_header(h, w, quality, subsampling, huffman, qtables, restart_interval)
     out = bytes.fromhex('ffd8' 'ffe00010' '4a46494600' '0101' '00' '0001' '0001' '0000')
     for t, table in enumerate(qtables):
         out += bytes.fromhex('ffdb0043') + bytes([t]) + table[order].astype(np.uint8).tobytes()
+    idents = (0x00, 0x10) if grey else (0x00, 0x10, 0x01, 0x11)          # the luma tables are all a grey-scale file carries
+    dht = _ANNEX_K_DHT[:_GREY_DHT_BYTES] if grey else _ANNEX_K_DHT
+    if huffman is not None:
+        huffman = np.asarray(huffman)
+        if huffman.dtype != np.uint8 or huffman.shape != (len(idents), 272):
+            raise ValueError('huffman: ({}, 272) uint8 needed{}, got {} {}'.format(len(idents), ' for a grey-scale file' if grey else '',
+                                                                                   huffman.dtype, huffman.shape))
+        dht = b''.join(_dht_segment(ident, t) for ident, t in zip(idents, huffman))
     if grey:
-        dht = _ANNEX_K_DHT[:_GREY_DHT_BYTES]
-        if huffman is not None:
-            huffman = np.asarray(huffman)
-            if huffman.dtype != np.uint8 or huffman.shape != (2, 272):
-                raise ValueError('huffman: (2, 272) uint8 needed for a grey-scale file, got {} {}'.format(huffman.dtype, huffman.shape))
-            dht = b''.join(_dht_segment(ident, t) for ident, t in zip((0x00, 0x10), huffman))
         return out + bytes.fromhex('ffc0000b' '08') + struct.pack('>HH', h, w) + bytes([1, 1, 0x11, 0]) + dht + _dri_segment(ri) + \
             bytes.fromhex('ffda0008' '01' '0100' '00' '3f' '00')
     out += bytes.fromhex('ffc00011' '08') + struct.pack('>HH', h, w) + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, len(qtables) - 1])
-    dht = _ANNEX_K_DHT
-    if huffman is not None:
-        huffman = np.asarray(huffman)
-        if huffman.dtype != np.uint8 or huffman.shape != (4, 272):
-            raise ValueError('huffman: (4, 272) uint8 needed, got {} {}'.format(huffman.dtype, huffman.shape))
-        dht = b''.join(_dht_segment(ident, t) for ident, t in zip((0x00, 0x10, 0x01, 0x11), huffman))
     return out + dht + _dri_segment(ri) + bytes.fromhex('ffda000c' '03' '0100' '0211' '0311' '00' '3f' '00')
 
 
@@ -379,7 +388,7 @@ def device_codec(x, quality, subsampling='4:4:4', want_image=True, want_bytes=Tr
     subsampling = _grey_input(x.shape, subsampling, 'device_codec')
     hs, vs = ops.jpeg_subsampling(subsampling)
     grey = ops.jpeg_is_grey(hs, vs)
-    _colour_only('progressive=True (writing the six scans libjpeg writes for one component)', grey and progressive)
+    _colour_only(_PROGRESSIVE_GREY, grey and progressive)
     quality, qtables = _quality_or_tables(quality, qtables, grey=grey)
     ri = ops.jpeg_restart_interval(restart_interval)
     n, h, w, _ = x.shape
@@ -413,8 +422,9 @@ def encode_batch(batch_x, quality, subsampling='4:4:4', optimize=False, *, qtabl
     optimal table of its own, the same bytes with `optimize` or without; in a single-component scan the restart interval counts
     blocks.  (n,h,w,1) or (h,w,1): grey-scale files, the ones libjpeg writes for a mode 'L' image - subsampling
     left at its default or 'grey', qtables one table (or the first of two or three), not with `progressive`."""
-    subsampling = _grey_input(np.shape(unwrap(batch_x)), subsampling, 'encode_batch')           # (host checks first: nothing is uploaded
-    quality, qtables = _quality_or_tables(quality, qtables, grey=subsampling == 'grey')         # for a call that is refused)
+    shape = np.shape(unwrap(batch_x))
+    subsampling = _grey_input(shape, subsampling, 'encode_batch')                               # (host checks first: nothing is uploaded
+    quality, qtables = _quality_or_tables(quality, qtables, grey=_grey_shape(shape))            # for a call that is refused)
     ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=True)
     if x.dim() == 3:
@@ -442,7 +452,7 @@ def _header_lengths(h, w, quality, subsampling, n, tables, qtables, ri, progress
     if progressive:
         pieces = (jpeg_progressive_pieces(h, w, quality, subsampling, t, qtables=qtables, restart_interval=ri) for t in tables)
         return [sum(len(p) for p in front) for front in pieces]
-    grey = subsampling == 'grey'
+    grey = ops.jpeg_is_grey(*_factors(subsampling))
     head = _header_bytes(qtables, ri, grey)[0]
     annex_k = _GREY_ANNEX_K_SYMBOLS if grey else _ANNEX_K_SYMBOLS
     return [head] * n if tables is None else (head - annex_k + tables[..., :16].sum(axis=(-2, -1), dtype=np.int64)).tolist()
@@ -464,8 +474,9 @@ def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', 
     (h,w,1) or (n,h,w,1): the grey-scale codec - the image comes back with its one channel, the sizes are those of
     encode_batch's grey-scale files, `effective` from the first Huffman table on (offset 102); subsampling left at its default or
     'grey', not with `progressive`."""
-    subsampling = _grey_input(np.shape(unwrap(batch_x)), subsampling, 'compress_batch')
-    jpeg_quality, qtables = _quality_or_tables(jpeg_quality, qtables, grey=subsampling == 'grey')
+    grey = _grey_shape(np.shape(unwrap(batch_x)))
+    subsampling = _grey_input(np.shape(unwrap(batch_x)), subsampling, 'compress_batch')           # ('grey' for such a shape, or refused)
+    jpeg_quality, qtables = _quality_or_tables(jpeg_quality, qtables, grey=grey)
     ri = ops.jpeg_restart_interval(restart_interval)
     x = _device_batch(batch_x, keep_bytes=False)
     if x.dim() not in (3, 4):
@@ -474,7 +485,7 @@ def compress_batch(batch_x, jpeg_quality, effective=False, subsampling='4:4:4', 
     image, segments, tables = (device_codec(x[None] if single else x, jpeg_quality, subsampling, optimize=optimize, qtables=qtables,
                                             restart_interval=ri, progressive=progressive) + (None,))[:3]
     heads = _header_lengths(x.shape[-3], x.shape[-2], jpeg_quality, subsampling, len(segments), tables, qtables, ri, progressive)
-    dht = _header_bytes(qtables, ri, subsampling == 'grey')[1] if effective else 0
+    dht = _header_bytes(qtables, ri, grey)[1] if effective else 0
     sizes = [head + (sum(len(scan) for scan in s) if progressive else len(s)) + 2 - dht for head, s in zip(heads, segments)]
     image = image.cpu().numpy()
     if single:
@@ -712,6 +723,9 @@ class JPEGHeader(namedtuple('JPEGHeader', 'h w hs vs qtables huffman ecd_offset 
 # (16 counts, symbols) table of each component of the scan (empty for a DC refine scan, which has no symbols), and where its
 # entropy-coded segment stands in the file
 JPEGScan = namedtuple('JPEGScan', 'components ss se ah al huffman ecd_offset ecd_end')
+_NO_TABLE = (bytes(16), b'')          # the table of a scan that has no symbols, and of the slots of a scan that its components leave free
+# what a reader takes beyond baseline colour files of the three standard samplings: the allow_* answers of its caller, in parse_header's order
+_Accept = namedtuple('_Accept', 'restart progressive grey sampling')
 JPEG_SCANS_MAX = ops.JPEG_SCANS_MAX
 JPEG_STATUS_BITS = OrderedDict([(1, 'marker inside the entropy-coded segment'), (2, 'invalid Huffman code'), (4, 'zig-zag index past 63'),
                                 (8, 'coefficient category out of range'), (16, 'bits needed beyond the end of the stream'),
@@ -720,6 +734,7 @@ JPEG_STATUS_BITS = OrderedDict([(1, 'marker inside the entropy-coded segment'), 
                                 (512, 'restart markers missing, surplus or out of sequence'),
                                 (1024, 'end-of-band run beyond the blocks of the scan')])
 _MAX_SIDE = 4096
+_NATURAL = np.argsort(zigzag(8).ravel(), kind='stable')                  # scan position -> natural index, as a DQT segment is read
 _SOF_NAMES = {0xc1: 'extended sequential', 0xc2: 'progressive', 0xc3: 'lossless', 0xc5: 'differential sequential',
               0xc6: 'differential progressive', 0xc7: 'differential lossless', 0xc9: 'arithmetic-coded sequential',
               0xca: 'arithmetic-coded progressive', 0xcb: 'arithmetic-coded lossless', 0xcd: 'arithmetic-coded differential sequential',
@@ -749,10 +764,10 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
     named: chroma that is not 1x1, a factor of 3, and every pair whose ratios are not those (4x4, ...)."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise ValueError('JPEG data: bytes needed, got {}'.format(type(data).__name__))
+    accept = _Accept(allow_restart, allow_progressive, allow_grey, allow_sampling)
     data = bytes(data)
     if data[:2] != b'\xff\xd8':
         raise ValueError('not a JPEG file: no SOI marker')
-    order = np.argsort(zigzag(8).ravel(), kind='stable')                 # scan position -> natural index
     qt, huff, frame, pos, restart, progressive = {}, {}, None, 2, None, False
     while True:
         if pos + 4 > len(data):
@@ -767,10 +782,7 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
             raise ValueError('EOI before any scan')
         if marker == 0xd8 or marker == 0x01 or 0xd0 <= marker <= 0xd7:
             raise ValueError('unexpected marker FF{:02X} in the header'.format(marker))
-        size = struct.unpack_from('>H', data, pos + 2)[0]
-        if size < 2 or pos + 2 + size > len(data):
-            raise ValueError('truncated segment FF{:02X} at offset {}'.format(marker, pos))
-        body = data[pos + 4:pos + 2 + size]
+        marker, body, pos = _segment(data, pos)
         if marker == 0xdb:
             k = 0
             while k < len(body):
@@ -779,12 +791,12 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
                 if (body[k] & 15) > 3 or k + 65 > len(body):
                     raise ValueError('malformed DQT segment')
                 table = np.zeros(64, np.uint16)
-                table[order] = np.frombuffer(body[k + 1:k + 65], np.uint8)
+                table[_NATURAL] = np.frombuffer(body[k + 1:k + 65], np.uint8)
                 qt[body[k] & 15] = table
                 k += 65
         elif marker == 0xc4:
             huff.update(_dht_tables(body))
-        elif marker == 0xc0 or (marker == 0xc2 and allow_progressive):
+        elif marker == 0xc0 or (marker == 0xc2 and accept.progressive):
             progressive = marker == 0xc2
             if frame is not None:
                 raise ValueError('several frame headers')
@@ -793,7 +805,7 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
             if body[0] != 8:
                 raise ValueError('{}-bit samples (only 8-bit baseline files are read)'.format(body[0]))
             h, w, ncomp = struct.unpack_from('>HH', body, 1) + (body[5],)
-            if ncomp != 3 and not (ncomp == 1 and allow_grey):
+            if ncomp != 3 and not (ncomp == 1 and accept.grey):
                 raise ValueError('{} (3 components needed, the file has {})'.format(
                     {1: 'grey-scale file', 4: 'CMYK / four-component file'}.get(ncomp, 'unsupported number of components'), ncomp))
             if h < 1 or w < 1 or h > _MAX_SIDE or w > _MAX_SIDE:
@@ -803,23 +815,19 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
             if ncomp == 1:
                 if not (1 <= sampling[0][0] <= 4 and 1 <= sampling[0][1] <= 4):
                     raise ValueError('illegal sampling factors {}x{} of the one component (1..4 each)'.format(*sampling[0]))
-            elif sampling[0] not in ((1, 1), (2, 1), (2, 2)) or sampling[1:] != ((1, 1), (1, 1)):
-                if not allow_sampling:
-                    raise ValueError('unsupported sampling factors {} (luma 1x1, 2x1 or 2x2 over 1x1 chroma)'.format(
-                        ' '.join('{}x{}'.format(*f) for f in sampling)))
-                if sampling[1:] != ((1, 1), (1, 1)) or not ops.jpeg_is_wide(*sampling[0]):
-                    raise ValueError('unsupported sampling factors {} (luma 1x1, 2x1, 2x2, 1x2, 4x1, 4x2, 1x4 or 2x4 over 1x1 chroma)'.format(
-                        ' '.join('{}x{}'.format(*f) for f in sampling)))
+            elif sampling[1:] != ((1, 1), (1, 1)) or not (sampling[0] in ops.JPEG_SUBSAMPLING.values()
+                                                          or (accept.sampling and ops.jpeg_is_wide(*sampling[0]))):
+                raise ValueError('unsupported sampling factors {} (luma {} over 1x1 chroma)'.format(
+                    ' '.join('{}x{}'.format(*f) for f in sampling),
+                    '1x1, 2x1, 2x2, 1x2, 4x1, 4x2, 1x4 or 2x4' if accept.sampling else '1x1, 2x1 or 2x2'))
             frame = (h, w, comps)
         elif marker in _SOF_NAMES:
             raise ValueError('{} file (SOF{}): only baseline sequential files (SOF0) are read'.format(_SOF_NAMES[marker], marker - 0xc0))
         elif marker == 0xcc:
             raise ValueError('arithmetic-coded file (DAC segment)')
         elif marker == 0xdd:
-            if len(body) != 2:
-                raise ValueError('malformed DRI segment')
-            value = struct.unpack('>H', body)[0]
-            if value != 0 and not allow_restart:
+            value = _dri_value(body)
+            if value != 0 and not accept.restart:
                 raise ValueError('restart interval {} (DRI): files with restart markers are not read'.format(value))
             if restart is not None and restart != value:
                 raise ValueError('several DRI segments with different restart intervals ({} and {}; libjpeg lets the last one hold): '
@@ -829,82 +837,105 @@ def parse_header(data, allow_restart=False, allow_progressive=False, allow_grey=
             break
         elif not (0xe0 <= marker <= 0xef or marker == 0xfe or marker == 0xdc or 0xf0 <= marker <= 0xfd):
             raise ValueError('unsupported marker FF{:02X} in the header'.format(marker))
-        pos += 2 + size
     if frame is None:
         raise ValueError('no frame header (SOF0) before the scan')
-    h, w, comps = frame
-    if progressive:
-        return _parse_scans(data, pos, frame, qt, huff, restart or 0, allow_restart)
+    scans = _progressive_scans if progressive else _baseline_scan         # from the first SOS segment's body and the offset behind it
+    return scans(data, body, pos, frame, qt, huff, restart or 0, accept)
+
+
+def _segment(data, pos):
+    """The marker segment at pos -> (marker, body, the offset behind it).  That there are four bytes at pos is the caller's to see."""
+    marker, size = data[pos + 1], struct.unpack_from('>H', data, pos + 2)[0]
+    if size < 2 or pos + 2 + size > len(data):
+        raise ValueError('truncated segment FF{:02X} at offset {}'.format(marker, pos))
+    return marker, data[pos + 4:pos + 2 + size], pos + 2 + size
+
+
+def _sos_fields(body):
+    """The body of an SOS segment -> (component ids, their table selectors Td << 4 | Ta, Ss, Se, Ah, Al)."""
     if len(body) < 1 or len(body) != 4 + 2 * body[0]:
         raise ValueError('malformed SOS segment')
-    nc = len(comps)
-    if nc == 1 and body[0] != 1:
-        raise ValueError('the scan holds {} components, the frame of a grey-scale file one'.format(body[0]))
-    if body[0] != nc:
-        raise ValueError('non-interleaved file: the scan holds {} of 3 components'.format(body[0]))
-    if [body[1 + 2 * c] for c in range(nc)] != [c[0] for c in comps]:
-        raise ValueError('the scan does not list the components in frame order')
-    ss, se, ahal = body[1 + 2 * nc], body[2 + 2 * nc], body[3 + 2 * nc]
-    if (ss, se, ahal) != (0, 63, 0):
-        raise ValueError('not a baseline scan: Ss={} Se={} Ah/Al={:02x} (0, 63, 00 needed)'.format(ss, se, ahal))
-    tables, qtables = [], np.zeros((nc, 64), np.uint16)
-    for c in range(nc):
-        sel = body[2 + 2 * c]
-        if (sel >> 4) > 3 or (sel & 15) > 3:
-            raise ValueError('malformed SOS segment')
-        for cls, ident in ((0, sel >> 4), (1, sel & 15)):
-            if (cls << 4 | ident) not in huff:
-                raise ValueError('missing Huffman table: {} table {} of component {}'.format('AC' if cls else 'DC', ident, c))
-            tables.append(huff[cls << 4 | ident])
-        if comps[c][3] not in qt:
-            raise ValueError('missing quantisation table {} of component {}'.format(comps[c][3], c))
-        qtables[c] = qt[comps[c][3]]
-    ecd_offset = pos + 2 + size
-    k = ecd_offset
+    ns = body[0]
+    return list(body[1:1 + 2 * ns:2]), list(body[2:2 + 2 * ns:2]), body[1 + 2 * ns], body[2 + 2 * ns], body[3 + 2 * ns] >> 4, body[3 + 2 * ns] & 15
+
+
+def _dri_value(body):
+    if len(body) != 2:
+        raise ValueError('malformed DRI segment')
+    return struct.unpack('>H', body)[0]
+
+
+def _huffman_tables(huff, selector, c, classes, where=''):
+    """The tables of `classes` (0 DC, 1 AC) that a scan's selector names for component c, of the tables `huff` in force at its SOS."""
+    if (selector >> 4) > 3 or (selector & 15) > 3:
+        raise ValueError('malformed SOS segment')
+    keys = [cls << 4 | (selector & 15 if cls else selector >> 4) for cls in classes]
+    for key in keys:
+        if key not in huff:
+            raise ValueError('missing Huffman table: {} table {} of component {}{}'.format('AC' if key >> 4 else 'DC', key & 15, c, where))
+    return [huff[key] for key in keys]
+
+
+def _qtable(qt, comps, c):
+    if comps[c][3] not in qt:
+        raise ValueError('missing quantisation table {} of component {}'.format(comps[c][3], c))
+    return qt[comps[c][3]]
+
+
+def _header(frame, qtables, huffman, ecd_offset, ecd_end, restart, scans=()):
+    """parse_header's result.  The scans of one component are never interleaved, so its sampling factors change nothing: 1x1."""
+    h, w, comps = frame
+    hs, vs = (1, 1) if len(comps) == 1 else comps[0][1:3]
+    return JPEGHeader(h, w, hs, vs, np.stack(qtables), huffman, ecd_offset, ecd_end, restart).with_ncomp(len(comps)).with_scans(scans)
+
+
+_NOT_STUFFED = re.compile(b'\xff[^\\x00]')          # FF and a second byte that is not the 00 stuffed behind a data FF
+
+
+def _segment_end(data, k, restart, allow_restart, fill=True):
+    """The offset of the first marker behind the entropy-coded segment that starts at k; restart markers are stepped over.  So are,
+    with `fill`, the fill bytes in front of that marker (FF FF ..), which then count into the segment - as in the scans of a
+    progressive file; without it the segment ends at the first of them, for the caller to refuse."""
     while True:
-        k = data.find(b'\xff', k)
-        if k < 0 or k + 1 >= len(data):
+        found = _NOT_STUFFED.search(data, k)
+        if found is None:
             raise ValueError('no EOI marker behind the entropy-coded segment')
+        k = found.start()
         nxt = data[k + 1]
-        if nxt == 0:
-            k += 2
-            continue
-        if nxt == 0xd9:
-            break
         if 0xd0 <= nxt <= 0xd7:
             if not allow_restart:
                 raise ValueError('restart marker FF{:02X} in the entropy-coded segment: files with restart markers are not read'.format(nxt))
             if not restart:
                 raise ValueError('restart marker FF{:02X} in the entropy-coded segment of a file whose restart interval is 0'.format(nxt))
             k += 2
-            continue
-        if nxt in (0xda, 0xc4, 0xdb, 0xdd):
-            raise ValueError('several scans: marker FF{:02X} behind the first entropy-coded segment'.format(nxt))
-        raise ValueError('unexpected marker FF{:02X} in the entropy-coded segment'.format(nxt))
-    if nc == 1:
-        return JPEGHeader(h, w, 1, 1, qtables, tuple(tables), ecd_offset, k, restart or 0).with_ncomp(1)
-    return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, tuple(tables), ecd_offset, k, restart or 0)
-
-
-def _segment_end(data, k, restart, allow_restart):
-    """The offset of the first marker behind the entropy-coded segment that starts at k; restart markers are stepped over."""
-    while True:
-        k = data.find(b'\xff', k)
-        if k < 0 or k + 1 >= len(data):
-            raise ValueError('no EOI marker behind the entropy-coded segment')
-        nxt = data[k + 1]
-        if nxt == 0:
-            k += 2
-        elif 0xd0 <= nxt <= 0xd7:
-            if not allow_restart:
-                raise ValueError('restart marker FF{:02X} in the entropy-coded segment: files with restart markers are not read'.format(nxt))
-            if not restart:
-                raise ValueError('restart marker FF{:02X} in the entropy-coded segment of a file whose restart interval is 0'.format(nxt))
-            k += 2
-        elif nxt == 0xff:
+        elif nxt == 0xff and fill:
             k += 1
         else:
             return k
+
+
+def _baseline_scan(data, body, start, frame, qt, huff, restart, accept):
+    """The one scan of a baseline file, whose SOS body is `body` and whose entropy-coded segment starts at `start` -> its JPEGHeader."""
+    comps = frame[2]
+    ids, selectors, ss, se, ah, al = _sos_fields(body)
+    if len(comps) == 1 and len(ids) != 1:
+        raise ValueError('the scan holds {} components, the frame of a grey-scale file one'.format(len(ids)))
+    if len(ids) != len(comps):
+        raise ValueError('non-interleaved file: the scan holds {} of 3 components'.format(len(ids)))
+    if ids != [c[0] for c in comps]:
+        raise ValueError('the scan does not list the components in frame order')
+    if (ss, se, ah, al) != (0, 63, 0, 0):
+        raise ValueError('not a baseline scan: Ss={} Se={} Ah/Al={:02x} (0, 63, 00 needed)'.format(ss, se, ah << 4 | al))
+    tables, qtables = [], []
+    for c, selector in enumerate(selectors):                            # (a component's Huffman tables are missed before its quantisation table)
+        tables += _huffman_tables(huff, selector, c, (0, 1))
+        qtables.append(_qtable(qt, comps, c))
+    end = _segment_end(data, start, restart, accept.restart, fill=False)
+    if data[end + 1] in (0xda, 0xc4, 0xdb, 0xdd):
+        raise ValueError('several scans: marker FF{:02X} behind the first entropy-coded segment'.format(data[end + 1]))
+    if data[end + 1] != 0xd9:                                            # a fill byte (FFFF) too: the decoder is never given one
+        raise ValueError('unexpected marker FF{:02X} in the entropy-coded segment'.format(data[end + 1]))
+    return _header(frame, qtables, tuple(tables), start, end, restart)
 
 
 def jpeg_script_check(script, ncomp=3):
@@ -942,65 +973,41 @@ def jpeg_script_check(script, ncomp=3):
     return levels
 
 
-def _parse_scans(data, pos, frame, qt, huff, restart, allow_restart):
-    """The scans of a progressive file from its first SOS marker (at pos) on -> its JPEGHeader."""
-    h, w, comps = frame
-    huff, scans = dict(huff), []
-    ids = [c[0] for c in comps]
+def _progressive_scans(data, body, start, frame, qt, huff, restart, accept):
+    """The scans of a progressive file, the first with the SOS body `body` and its entropy-coded segment at `start` -> its JPEGHeader."""
+    comps = frame[2]
+    ids, huff, scans = [c[0] for c in comps], dict(huff), []
     while True:
-        size = struct.unpack_from('>H', data, pos + 2)[0]
-        body = data[pos + 4:pos + 2 + size]
-        if len(body) < 1 or len(body) != 4 + 2 * body[0]:
-            raise ValueError('malformed SOS segment')
+        listed, selectors, ss, se, ah, al = _sos_fields(body)
         if len(scans) == JPEG_SCANS_MAX:
             raise ValueError('progressive file with more than {} scans'.format(JPEG_SCANS_MAX))
-        ns = body[0]
-        if any(body[1 + 2 * c] not in ids for c in range(ns)):
+        if any(i not in ids for i in listed):
             raise ValueError('malformed SOS segment: unknown component')
-        cs = tuple(ids.index(body[1 + 2 * c]) for c in range(ns))
-        ss, se, ah, al = body[1 + 2 * ns], body[2 + 2 * ns], body[3 + 2 * ns] >> 4, body[3 + 2 * ns] & 15
-        tables = []
-        for c in range(ns):
-            sel = body[2 + 2 * c]
-            if (sel >> 4) > 3 or (sel & 15) > 3:
-                raise ValueError('malformed SOS segment')
-            if ss == 0 and ah:
-                tables.append((bytes(16), b''))
-                continue
-            key = (sel >> 4) if ss == 0 else (0x10 | (sel & 15))
-            if key not in huff:
-                raise ValueError('missing Huffman table: {} table {} of component {} in scan {}'.format(
-                    'AC' if ss else 'DC', key & 15, cs[c], len(scans)))
-            tables.append(huff[key])
-        start = pos + 2 + size
-        k = _segment_end(data, start, restart, allow_restart)
-        scans.append(JPEGScan(cs, ss, se, ah, al, tuple(tables), start, k))
-        pos = k
-        while True:                                                      # the markers between two scans
-            marker = data[pos + 1]
-            if marker == 0xd9:
-                break
+        cs = tuple(ids.index(i) for i in listed)
+        classes = () if ss == 0 and ah else (int(ss > 0),)             # a DC refine scan has no symbols; else the DC or the AC table
+        where = ' in scan {}'.format(len(scans))
+        tables = tuple(t for c, selector in zip(cs, selectors)
+                       for t in _huffman_tables(huff, selector, c, classes, where) or [_NO_TABLE])
+        pos = _segment_end(data, start, restart, accept.restart)
+        scans.append(JPEGScan(cs, ss, se, ah, al, tables, start, pos))
+        while data[pos + 1] != 0xd9:                                     # the markers between two scans
             if pos + 4 > len(data):
                 raise ValueError('truncated file behind scan {}'.format(len(scans) - 1))
-            size = struct.unpack_from('>H', data, pos + 2)[0]
-            if size < 2 or pos + 2 + size > len(data):
-                raise ValueError('truncated segment FF{:02X} at offset {}'.format(marker, pos))
-            body = data[pos + 4:pos + 2 + size]
+            marker, body, behind = _segment(data, pos)
             if marker == 0xda:
+                start = behind
                 break
             if marker == 0xc4:
                 huff.update(_dht_tables(body))
             elif marker == 0xdd:
-                if len(body) != 2:
-                    raise ValueError('malformed DRI segment')
-                value = struct.unpack('>H', body)[0]
+                value = _dri_value(body)
                 if value != restart:
                     raise ValueError('the restart interval changes between scans ({} then {}): not read'.format(restart, value))
             elif marker == 0xdc:
                 raise ValueError('DNL marker behind scan {}: not read'.format(len(scans) - 1))
             elif not (0xe0 <= marker <= 0xef or marker == 0xfe):
                 raise ValueError('unsupported marker FF{:02X} between the scans of a progressive file'.format(marker))
-            pos += 2 + size
+            pos = behind
             while pos + 1 < len(data) and data[pos] == 0xff and data[pos + 1] == 0xff:          # fill bytes
                 pos += 1
             if pos + 1 >= len(data):
@@ -1009,16 +1016,8 @@ def _parse_scans(data, pos, frame, qt, huff, restart, allow_restart):
                 raise ValueError('no marker at offset {}'.format(pos))
         if data[pos + 1] == 0xd9:
             break
-    nc = len(comps)
-    jpeg_script_check([s[:5] for s in scans], nc)
-    qtables = np.zeros((nc, 64), np.uint16)
-    for c in range(nc):
-        if comps[c][3] not in qt:
-            raise ValueError('missing quantisation table {} of component {}'.format(comps[c][3], c))
-        qtables[c] = qt[comps[c][3]]
-    if nc == 1:
-        return JPEGHeader(h, w, 1, 1, qtables, (), scans[0].ecd_offset, pos, restart).with_ncomp(1).with_scans(scans)
-    return JPEGHeader(h, w, comps[0][1], comps[0][2], qtables, (), scans[0].ecd_offset, pos, restart).with_scans(scans)
+    jpeg_script_check([s[:5] for s in scans], len(comps))
+    return _header(frame, [_qtable(qt, comps, c) for c in range(len(comps))], (), scans[0].ecd_offset, pos, restart, scans)
 
 
 def _dht_tables(body):
@@ -1039,12 +1038,21 @@ def _status_text(status):
     return ' | '.join(text for bit, text in JPEG_STATUS_BITS.items() if status & bit)
 
 
-def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progressive=False, allow_grey=False, allow_sampling=False):
+class _Group(namedtuple('_Group', 'indices h w hs vs restart_interval script coef status rounds qtabs')):
+    """The files of one decode call (_decode_groups): their indices in the input, what they share - (hs, vs) = ops.JPEG_GREY for
+    grey-scale files, script = () for baseline ones - and what is on the device for them; qtabs (n, 3 | 1, 64) went up with the files."""
+
+    @property
+    def geometry(self):
+        return self.h, self.w, self.hs, self.vs
+
+
+def _decode_groups(files, subseq_bits, device, accept):
     """Headers parsed, one upload, one nimg_jpeg_decode[_restart] per group of equal (h, w, hs, vs, restart interval) - for progressive
-    files (allow_progressive) one nimg_jpeg_decode_progressive per group of equal geometry, interval and scan script.  Returns
-    (headers, groups) with groups = [(indices, (h, w, hs, vs), coef, status, rounds, qtabs)] - device tensors, nothing read back.  The
-    (hs, vs) of a group of grey-scale files (allow_grey) is ops.JPEG_GREY: another geometry, so never in a group with colour files."""
-    headers = [parse_header(f, allow_restart, allow_progressive, allow_grey, allow_sampling) for f in files]
+    files (accept.progressive) one nimg_jpeg_decode_progressive per group of equal geometry, interval and scan script.  Returns
+    (headers, [_Group]) - device tensors, nothing read back.  The (hs, vs) of a group of grey-scale files (accept.grey) is
+    ops.JPEG_GREY: another geometry, so never in a group with colour files."""
+    headers = [parse_header(f, *accept) for f in files]
     if not headers:
         raise ValueError('no files to decode')
     keys = OrderedDict()
@@ -1052,48 +1060,55 @@ def _decode_groups(files, subseq_bits, device, allow_restart=False, allow_progre
         hs, vs = ops.JPEG_GREY if hd.ncomp == 1 else (hd.hs, hd.vs)
         keys.setdefault((hd.h, hd.w, hs, vs, hd.restart_interval, tuple(s[:5] for s in hd.scans)), []).append(i)
     dev = device if device is not None else default_device()
-    order = [i for idx in keys.values() for i in idx]                    # the segments back to back, group after group
-    spans = [[(s.ecd_offset, s.ecd_end) for s in headers[i].scans] or [(headers[i].ecd_offset, headers[i].ecd_end)] for i in order]
-    blob = b''.join(files[i][lo:hi] for i, sp in zip(order, spans) for lo, hi in sp)
-    tables = []                                                          # baseline: six per file (grey: two); progressive: three per scan
-    for i in order:
-        per = [headers[i].huffman] if not headers[i].scans else [s.huffman + ((bytes(16), b''),) * (3 - len(s.huffman))
-                                                                 for s in headers[i].scans]
-        tables += [t for group in per for t in group]
-    huff = np.zeros((len(tables), 272), np.uint8)
-    for j, (counts, symbols) in enumerate(tables):
+    # what goes up, per group and back to back in group order: the segments - one per file or one per scan, a header standing for its
+    # one scan -, their Huffman tables - six per file (grey: two), or three per scan - and three quantisation tables per file, or one
+    segments = [[files[i][s.ecd_offset:s.ecd_end] for i in idx for s in headers[i].scans or (headers[i],)] for idx in keys.values()]
+    tables = [[t for i in idx for s in headers[i].scans or (headers[i],)
+               for t in (s.huffman + (_NO_TABLE,) * (3 - len(s.huffman)) if headers[i].scans else s.huffman)] for idx in keys.values()]
+    qtabs = [np.stack([headers[i].qtables for i in idx]) for idx in keys.values()]
+    blob = b''.join(s for group in segments for s in group)
+    huff = np.zeros((sum(len(group) for group in tables), 272), np.uint8)
+    for j, (counts, symbols) in enumerate(t for group in tables for t in group):
         huff[j, :16] = np.frombuffer(counts, np.uint8)
         huff[j, 16:16 + len(symbols)] = np.frombuffer(symbols, np.uint8)
-    qt = np.concatenate([headers[i].qtables.reshape(-1) for i in order]).view(np.int16)        # three tables per file, or one
     ecd = torch.from_numpy(np.frombuffer(blob if blob else b'\0', np.uint8).copy()).to(dev)
-    huff, qt = torch.from_numpy(huff).to(dev), torch.from_numpy(qt).to(dev)
-    groups, j0, b0, t0, q0 = [], 0, 0, 0, 0
-    for (h, w, hs, vs, ri, script), idx in keys.items():
-        nc = 1 if ops.jpeg_is_grey(hs, vs) else 3
-        lengths = [hi - lo for sp in spans[j0:j0 + len(idx)] for lo, hi in sp]
-        off = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
-        part = ecd[b0:b0 + max(sum(lengths), 1)]
+    huff = torch.from_numpy(huff).to(dev)
+    qt = torch.from_numpy(np.concatenate([q.reshape(-1) for q in qtabs]).view(np.int16)).to(dev)
+    b, t, q = (np.concatenate([[0], np.cumsum(sizes)]) for sizes in ([sum(len(s) for s in group) for group in segments],
+                                                                   [len(group) for group in tables], [x.size for x in qtabs]))
+    groups = []
+    for g, ((h, w, hs, vs, ri, script), idx) in enumerate(keys.items()):
+        off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(s) for s in segments[g]])]).astype(np.int64)).to(dev)
+        part = ecd[b[g]:max(b[g + 1], b[g] + 1)]
         if script:
             rows = np.array([[sum(1 << c for c in cs), ss, se, ah, al, lv]
-                             for (cs, ss, se, ah, al), lv in zip(script, jpeg_script_check(script, nc))], np.int32)
-            count = len(idx) * len(script) * 3
-            coef, status, rounds = ops.jpeg_decode_progressive(part, off, huff[t0:t0 + count].view(len(idx), len(script), 3, 272), rows, h, w,
-                                                               hs, vs, subseq_bits=subseq_bits, restart_interval=ri)
+                             for (cs, ss, se, ah, al), lv in zip(script, jpeg_script_check(script, qtabs[g].shape[1]))], np.int32)
+            done = ops.jpeg_decode_progressive(part, off, huff[t[g]:t[g + 1]].view(len(idx), len(script), 3, 272), rows, h, w, hs, vs,
+                                               subseq_bits=subseq_bits, restart_interval=ri)
         else:
-            count = len(idx) * 2 * nc
-            coef, status, rounds = ops.jpeg_decode(part, off, huff[t0:t0 + count].view(len(idx), 2 * nc, 272), h, w, hs, vs,
-                                                   subseq_bits=subseq_bits, restart_interval=ri)
-        groups.append((idx, (h, w, hs, vs), coef, status, rounds, qt[q0:q0 + len(idx) * nc * 64].view(len(idx), nc, 64)))
-        j0, b0, t0, q0 = j0 + len(idx), b0 + sum(lengths), t0 + count, q0 + len(idx) * nc * 64
+            done = ops.jpeg_decode(part, off, huff[t[g]:t[g + 1]].view(len(idx), -1, 272), h, w, hs, vs, subseq_bits=subseq_bits,
+                                   restart_interval=ri)
+        groups.append(_Group(idx, h, w, hs, vs, ri, script, *done, qt[q[g]:q[g + 1]].view(qtabs[g].shape)))
     return headers, groups
 
 
 def _raise_on_status(groups, status):
     """status: numpy per group, in group order."""
-    bad = sorted((i, int(s)) for (idx, _, _, _, _, _), st in zip(groups, status) for i, s in zip(idx, st) if s)
+    bad = sorted((i, int(s)) for g, st in zip(groups, status) for i, s in zip(g.indices, st) if s)
     if bad:
         raise ValueError('damaged JPEG data in file(s) {}: {}'.format(
             [i for i, _ in bad], '; '.join('{}: status {} ({})'.format(i, s, _status_text(s)) for i, s in bad)))
+
+
+def _fetch_status(groups, more=()):
+    """The one download of a reader: the status words of every group and behind them the device tensors `more` (uint8 or float32), in a
+    single copy.  Damaged data raises (_raise_on_status); returns `more` as numpy arrays."""
+    words = [len(g.indices) for g in groups]
+    flat = torch.cat([g.status.view(torch.uint8) for g in groups] + [y.view(torch.uint8).reshape(-1) for y in more]).cpu().numpy()
+    ends = np.cumsum([4 * sum(words)] + [y.numel() * y.element_size() for y in more])
+    _raise_on_status(groups, np.split(flat[:ends[0]].view(np.int32), np.cumsum(words)[:-1]))
+    return [flat[lo:hi].view(np.float32 if y.dtype == torch.float32 else np.uint8).reshape(tuple(y.shape))
+            for y, lo, hi in zip(more, ends[:-1], ends[1:])]
 
 
 def _as_files(files):
@@ -1135,36 +1150,23 @@ def decode_batch(files, as_float=False, device_output=False, subseq_bits=0, devi
     list they were).  Any other scale is a ValueError before a byte goes to the device."""
     scale = ops.jpeg_scale(scale)
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey, allow_sampling)
+    _, groups = _decode_groups(files, subseq_bits, device, _Accept(allow_restart, allow_progressive, allow_grey, allow_sampling))
     if scale == 1:
-        images = [ops.jpeg_reconstruct_tables(coef, h, w, qt, hs, vs, out_u8=not as_float)
-                  for _, (h, w, hs, vs), coef, _, _, qt in groups]
+        images = [ops.jpeg_reconstruct_tables(g.coef, g.h, g.w, g.qtabs, g.hs, g.vs, out_u8=not as_float) for g in groups]
     else:
-        images = [ops.jpeg_reconstruct_scaled(coef, h, w, qt, scale, hs, vs, out_u8=not as_float)
-                  for _, (h, w, hs, vs), coef, _, _, qt in groups]
-    words = [len(g[0]) for g in groups]
-    parts = [g[3].view(torch.uint8) for g in groups]                    # one download: the status words, then the images
-    if not device_output:
-        parts += [y.view(torch.uint8).reshape(-1) for y in images]
-    flat = torch.cat(parts).cpu().numpy()
-    _raise_on_status(groups, np.split(flat[:4 * sum(words)].view(np.int32), np.cumsum(words)[:-1]))
-    if not device_output:
-        at, out = 4 * sum(words), []
-        for y in images:
-            size = y.numel() * y.element_size()
-            out.append(flat[at:at + size].view(np.float32 if as_float else np.uint8).reshape(tuple(y.shape)))
-            at += size
-        images = out
+        images = [ops.jpeg_reconstruct_scaled(g.coef, g.h, g.w, g.qtabs, scale, g.hs, g.vs, out_u8=not as_float) for g in groups]
+    fetched = _fetch_status(groups, () if device_output else images)    # one download: the status words, then the images
+    images = images if device_output else fetched
     if len(groups) == 1:
         return images[0]
-    if scale != 1 and len({g[1] for g in groups}) == 1:                 # one geometry, several intervals or scripts: one batch
-        order = np.argsort([i for g in groups for i in g[0]])
+    if scale != 1 and len({g.geometry for g in groups}) == 1:           # one geometry, several intervals or scripts: one batch
+        order = np.argsort([i for g in groups for i in g.indices])
         if device_output:
             return torch.cat(images)[torch.from_numpy(order).to(images[0].device)]
         return np.concatenate(images)[order]
     result = [None] * len(files)
-    for (idx, _, _, _, _, _), y in zip(groups, images):
-        for j, i in enumerate(idx):
+    for g, y in zip(groups, images):
+        for j, i in enumerate(g.indices):
             result[i] = y[j]
     return result
 
@@ -1179,12 +1181,13 @@ def decode_coefficients(files, device_output=False, subseq_bits=0, device=None, 
     - (n, blocks, 64) coefficients in raster order and (n, 1, 64) tables -, never in one call with colour files.  allow_sampling: as
     decode_batch's; the layout is the same, over the real blocks ops.jpeg_geometry names for the factors."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, subseq_bits, device, allow_restart, allow_progressive, allow_grey, allow_sampling)
+    headers, groups = _decode_groups(files, subseq_bits, device, _Accept(allow_restart, allow_progressive, allow_grey, allow_sampling))
     if len(groups) != 1:
         raise ValueError('decode_coefficients needs files of one geometry{}, got {}'.format(
-            (' and restart interval' if allow_restart else '') + (' and scan script' if allow_progressive else ''), [g[1] for g in groups]))
-    _, _, coef, status, _, _ = groups[0]
-    _raise_on_status(groups, [status.cpu().numpy()])
+            (' and restart interval' if allow_restart else '') + (' and scan script' if allow_progressive else ''),
+            [g.geometry for g in groups]))
+    _fetch_status(groups)
+    coef = groups[0].coef
     return (coef if device_output else coef.cpu().numpy()), np.stack([hd.qtables for hd in headers])
 
 
@@ -1217,27 +1220,22 @@ def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=Fa
     of the samplings 4:4:0, 4:1:1, 4:1:0, 1x4 and 2x4 are read too and written again as baseline files of the same
     sampling factors - not with `progressive`, which is a ValueError for them."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, 0, None, allow_restart, allow_progressive, allow_grey, allow_sampling)
-    _colour_only('progressive=True (writing the six scans libjpeg writes for one component)',
-                 progressive and any(hd.ncomp == 1 for hd in headers))
+    headers, groups = _decode_groups(files, 0, None, _Accept(allow_restart, allow_progressive, allow_grey, allow_sampling))
+    _colour_only(_PROGRESSIVE_GREY, progressive and any(hd.ncomp == 1 for hd in headers))
     wide = sorted({(hd.hs, hd.vs) for hd in headers if hd.ncomp == 3 and ops.jpeg_is_wide(hd.hs, hd.vs)})
     if progressive and wide:
         raise ValueError('progressive=True: progressive files are not written with the sampling factors {} (DESIGN.md section 8); they '
                          'are written again as baseline files'.format(', '.join('{}x{}'.format(*f) for f in wide)))
-    _raise_on_status(groups, np.split(torch.cat([g[3] for g in groups]).cpu().numpy(), np.cumsum([len(g[0]) for g in groups])[:-1]))
-    names = {v: k for k, v in ops.JPEG_SUBSAMPLING.items()}
-    names[ops.JPEG_GREY] = 'grey'
-    names.update({v: v for v in ops.JPEG_SAMPLING_WIDE.values()})           # (_jpeg_header takes their factors as they are)
+    _fetch_status(groups)
     result = [None] * len(files)
-    for idx, (h, w, hs, vs), coef, _, _, _ in groups:
-        ri = headers[idx[0]].restart_interval                               # the group's: files are grouped by it
+    for g in groups:
+        (h, w, hs, vs), ri = g.geometry, g.restart_interval
         coding = _annex_k_coding() if ops.jpeg_is_wide(hs, vs) and not optimize else _coding(optimize, progressive)
-        segments, tables = _device_segments(coding, coef, len(idx), h, w, hs, vs, restart_interval=ri)
-        for j, i in enumerate(idx):                                         # a file at a time: each keeps its quantisation tables
+        segments, tables = _device_segments(coding, g.coef, len(g.indices), h, w, hs, vs, restart_interval=ri)
+        for j, i in enumerate(g.indices):                                   # a file at a time: each keeps its quantisation tables
             qt = headers[i].qtables
             qt = qt if len(qt) == 1 else (qt[:2] if np.array_equal(qt[1], qt[2]) else qt)
-            result[i], = _jpeg_files(h, w, None, names[(hs, vs)], segments[j:j + 1], None if tables is None else tables[j:j + 1], qt, ri,
-                                     progressive)
+            result[i], = _jpeg_files(h, w, None, (hs, vs), segments[j:j + 1], None if tables is None else tables[j:j + 1], qt, ri, progressive)
     return result
 
 

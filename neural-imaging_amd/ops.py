@@ -2454,13 +2454,38 @@ JPEG_SUBSAMPLING = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
 JPEG_BLOCK_BITS_MAX = 1658       # DC 9 + 11 bits, 63 x (AC 16 + 10)
 JPEG_GREY = (0, 0)               # the factor form of a grey-scale file: one component, no chroma to sub-sample
 # The luma sampling factors (hs, vs) over 1x1 chroma that files are read with beyond the three above: 4:4:0, 4:1:1,
-# 4:1:0 and the two upright forms.  Only the ops that read a file or write its coefficients again take them (_JPEG_SAMPLING_ENTRIES).
+# 4:1:0 and the two upright forms.  Only the ops that read a file or write its coefficients again take them (_JPEG_ENTRIES).
 JPEG_SAMPLING_WIDE = {'4:4:0': (1, 2), '4:1:1': (4, 1), '4:1:0': (4, 2), '1x4': (1, 4), '2x4': (2, 4)}
-_JPEG_SAMPLING_ENTRIES = {name: name.replace('nimg_jpeg_', 'nimg_jpeg_sampling_').replace('_restart', '') for name in (
-    'nimg_jpeg_decode_restart', 'nimg_jpeg_decode_restart_workspace_bytes', 'nimg_jpeg_decode_progressive',
-    'nimg_jpeg_decode_progressive_workspace_bytes', 'nimg_jpeg_reconstruct_tables', 'nimg_jpeg_reconstruct_scaled',
-    'nimg_jpeg_reconstruct_scaled_workspace_bytes', 'nimg_jpeg_histogram_restart', 'nimg_jpeg_encode_tables_restart',
-    'nimg_jpeg_encode_tables_restart_workspace_bytes')}
+# Which entry point serves an operation.  An operation goes by the name of its entry for the three standard samplings, which takes
+# (hs, vs); its grey-scale form takes no factors and has no _restart twin; its form for the wide samplings
+# (section 4r) takes (hs, vs) and what the third column adds - the 1 of a reconstruction's workspace, which is the scaled one's at scale
+# 1.  None: the operation has no such form.
+_JPEG_ENTRIES = {
+    # operation: (grey-scale, wide samplings, further geometry arguments of the wide form)
+    'nimg_jpeg_workspace_bytes': ('nimg_jpeg_grey_workspace_bytes', 'nimg_jpeg_sampling_reconstruct_scaled_workspace_bytes', (1,)),
+    'nimg_jpeg_encode_restart_workspace_bytes': ('nimg_jpeg_grey_workspace_bytes', None, ()),     # one size: pixel stages, Annex K coder
+    'nimg_jpeg_transform': ('nimg_jpeg_grey_transform', None, ()),
+    'nimg_jpeg_transform_tables': ('nimg_jpeg_grey_transform_tables', None, ()),
+    'nimg_jpeg_encode_restart': ('nimg_jpeg_grey_encode', None, ()),
+    'nimg_jpeg_encode_tables_restart': ('nimg_jpeg_grey_encode_tables', 'nimg_jpeg_sampling_encode_tables', ()),
+    'nimg_jpeg_encode_tables_restart_workspace_bytes': ('nimg_jpeg_grey_encode_tables_workspace_bytes',
+                                                        'nimg_jpeg_sampling_encode_tables_workspace_bytes', ()),
+    'nimg_jpeg_histogram_restart': ('nimg_jpeg_grey_histogram', 'nimg_jpeg_sampling_histogram', ()),
+    'nimg_jpeg_decode_restart': ('nimg_jpeg_grey_decode', 'nimg_jpeg_sampling_decode', ()),
+    'nimg_jpeg_decode_restart_workspace_bytes': ('nimg_jpeg_grey_decode_workspace_bytes', 'nimg_jpeg_sampling_decode_workspace_bytes', ()),
+    'nimg_jpeg_decode_progressive': ('nimg_jpeg_grey_decode_progressive', 'nimg_jpeg_sampling_decode_progressive', ()),
+    'nimg_jpeg_decode_progressive_workspace_bytes': ('nimg_jpeg_grey_decode_progressive_workspace_bytes',
+                                                     'nimg_jpeg_sampling_decode_progressive_workspace_bytes', ()),
+    'nimg_jpeg_reconstruct_tables': ('nimg_jpeg_grey_reconstruct_tables', 'nimg_jpeg_sampling_reconstruct_tables', ()),
+    'nimg_jpeg_reconstruct_scaled': ('nimg_jpeg_reconstruct_scaled_grey', 'nimg_jpeg_sampling_reconstruct_scaled', ()),
+    'nimg_jpeg_reconstruct_scaled_workspace_bytes': ('nimg_jpeg_reconstruct_scaled_grey_workspace_bytes',
+                                                     'nimg_jpeg_sampling_reconstruct_scaled_workspace_bytes', ()),
+    'nimg_jpeg_encode_progressive': (None, None, ()),
+    'nimg_jpeg_progressive_workspace_bytes': (None, None, ()),
+    'nimg_jpeg_progressive_histogram': (None, None, ()),
+}
+# the wide-sampling entries that are namesakes of their operation - the same arguments, the same result
+_JPEG_SAMPLING_ENTRIES = {name: wide for name, (_, wide, more) in _JPEG_ENTRIES.items() if wide and not more}
 
 
 def jpeg_subsampling(subsampling):
@@ -2490,23 +2515,20 @@ def jpeg_mcu_blocks(hs, vs):
 
 
 def _jpeg_entry(name, hs, vs, *middle):
-    """(entry point, its geometry arguments) of an operation: the colour entry `name` with (hs, vs), or its grey-scale form
-    nimg_jpeg_grey_* - one per operation, without factors and without a _restart twin - with `middle`, the restart interval 0 of
-    an operation whose colour entry has none."""
-    if jpeg_is_wide(hs, vs):                                        # section 4r: nimg_jpeg_sampling_*, for the ops that have one
-        if name == 'nimg_jpeg_workspace_bytes':                     # a reconstruction's: the scaled one's at scale 1
-            return 'nimg_jpeg_sampling_reconstruct_scaled_workspace_bytes', (hs, vs, 1)
-        if name not in _JPEG_SAMPLING_ENTRIES:
+    """(entry point, its geometry arguments) of the operation `name` as _JPEG_ENTRIES has it: the colour entry with (hs, vs), the one of
+    the wide samplings with (hs, vs) and what the table adds, or the grey-scale one with `middle` - the restart interval 0 of an
+    operation whose colour entry has none."""
+    grey, wide, more = _JPEG_ENTRIES[name]
+    if jpeg_is_wide(hs, vs):
+        if wide is None:
             raise ValueError('{}: the sampling factors {}x{} are only read from files and written again with their coefficients '
-                             '(decode, reconstruct, histogram, encode_tables)'.format(name.replace('nimg_', ''), hs, vs))
-        return _JPEG_SAMPLING_ENTRIES[name], (hs, vs)
+                             '(decode, reconstruct, histogram, encode_tables)'.format(name[len('nimg_'):], hs, vs))
+        return wide, (hs, vs) + more
     if not jpeg_is_grey(hs, vs):
         return name, (hs, vs)
-    if name == 'nimg_jpeg_encode_restart_workspace_bytes':         # one size serves the pixel stages and the Annex K coder
-        return 'nimg_jpeg_grey_workspace_bytes', middle
-    if name.startswith('nimg_jpeg_reconstruct_scaled'):             # section 4q: nimg_jpeg_reconstruct_scaled_grey[_workspace_bytes]
-        return name.replace('reconstruct_scaled', 'reconstruct_scaled_grey'), middle
-    return name.replace('nimg_jpeg_', 'nimg_jpeg_grey_').replace('_restart', ''), middle
+    if grey is None:
+        _jpeg_colour_only(name[len('nimg_'):], hs, vs)
+    return grey, middle
 
 
 def _jpeg_colour_only(name, hs, vs):
@@ -2745,9 +2767,9 @@ def _jpeg_decode(name, entry, ecd, ecd_off, huffman, script, tables, h, w, hs, v
         raise RuntimeError('{}: Huffman tables {} {}, {} uint8 needed'.format(name, huffman.dtype, tuple(huffman.shape), shape))
     subseq_bits = int(subseq_bits)
     ri = jpeg_restart_interval(restart_interval)
+    size = getattr(_lib.load(), _jpeg_entry(entry + '_workspace_bytes', hs, vs)[0])
     entry, factors = _jpeg_entry(entry, hs, vs)
     batch = _jpeg_batch(n, h, w, hs, vs) + (' scans={}'.format(per) if scans else '')
-    size = getattr(_lib.load(), entry + '_workspace_bytes')
     workspace, _ = _jpeg_workspace(size(n, h, w, *factors, ri, *scans, ecd.numel(), subseq_bits),
                                    '{} subseq_bits={}'.format(batch, subseq_bits), ecd.device, workspace, name='JPEG decode workspace')
     coef = torch.empty((n, jpeg_geometry(h, w, hs, vs)[0], 64), dtype=torch.int16, device=ecd.device)
