@@ -1073,6 +1073,37 @@ int nimg_jpeg_sampling_encode_tables(const int16_t* coef, int n, int h, int w, i
                                      uint8_t* out, size_t out_capacity, uint32_t* lengths, uint32_t* status, void* workspace,
                                      size_t workspace_bytes, void* stream);
 
+/* Lossless transforms: the coefficients of n files of one geometry -> the coefficients of the files jpegtran
+ * makes of them by a flip, a transposition, a rotation or an aligned crop, in one launch that moves every block once.  (The name:
+ * nimg_jpeg_transform is the forward DCT.)
+ *   coef           (n, real blocks, 64) int16 as nimg_jpeg_transform / nimg_jpeg_decode leave them: [Y | Cb | Cr][block row][block col][zig-zag]
+ *   h, w, hs, vs   the source's geometry; nc = 3 with any of the eight luma samplings of the nimg_jpeg_sampling_* entries, or nc = 1, a
+ *                  grey-scale file, with hs = vs = 1 (its iMCU is 8 x 8 whatever the file declares)
+ *   op             0 none, 1 hflip, 2 vflip, 3 transpose, 4 transverse (the flip about the anti-diagonal), 5 rot90 (clockwise, jpegtran
+ *                  -rotate 90), 6 rot180, 7 rot270.  As jtransform.c does it: a horizontal mirroring reverses the block columns of every
+ *                  component and negates the coefficients of odd horizontal frequency, a vertical one the rows and odd vertical
+ *                  frequencies, a transposition swaps block rows with columns and transposes every block; the rotations and transverse
+ *                  are compositions of these, each carried out as one gather.  Negation is two's complement on 16 bits (-(-32768) stays);
+ *                  the DC is never negated.  The four transposing operations swap h with w and hs with vs, and the caller transposes
+ *                  every quantisation table.
+ *   crop_*         a region of the source, cut before the operation; crop_w == 0 (all four 0): none.  crop_x must be a multiple of
+ *                  8 hs and crop_y of 8 vs (jpegtran moves an unaligned origin silently: here it is refused), the region must lie inside
+ *                  the image with crop_w, crop_h >= 1; the blocks at a new right or bottom edge keep their contents, as jpegtran's do.
+ *   trim           a transform moves whole iMCUs, so (after the crop) hflip and rot270 need w % (8 hs) == 0, vflip and rot90
+ *                  h % (8 vs) == 0, rot180 and transverse both - jtransform.c's trim_right_edge / trim_bottom_edge, restated on the
+ *                  source.  0 (jpegtran -perfect): a file that does not is refused; 1 (-trim): that dimension is first cut down to the
+ *                  multiple below it.  jpegtran's third way, the strip left in place untransformed, is not offered.
+ *   out            (n, real blocks of the output geometry, 64) int16; out_h, out_w, out_hs, out_vs: that geometry (host ints)
+ * nimg_jpeg_lossless_geometry computes the four on the host alone; a caller sizes `out` by it.  NIMG_ERR_ARG before any launch, with
+ * `out` and the four untouched: an unknown op, factors outside the eight (or nc = 1 with others than 1 x 1), an unaligned crop or one
+ * outside the image, a partial iMCU with trim == 0, a result of no pixels, a null pointer, n outside 1..65535 (nc = 1 takes n == 0 as a
+ * no-op, as the nimg_jpeg_grey_* entries do).  No workspace, no allocation, no synchronisation, capturable.  Purely added:
+ * NIMG_ABI_VERSION stays. */
+int nimg_jpeg_lossless_geometry(int h, int w, int hs, int vs, int nc, int op, int crop_x, int crop_y, int crop_w, int crop_h, int trim,
+                                int* out_h, int* out_w, int* out_hs, int* out_vs);
+int nimg_jpeg_lossless(const int16_t* coef, int n, int h, int w, int hs, int vs, int nc, int op, int crop_x, int crop_y, int crop_w,
+                       int crop_h, int trim, int16_t* out, int* out_h, int* out_w, int* out_hs, int* out_vs, void* stream);
+
 /* Sign planes of the FAN's bf16-stored pooled activations: all that a layer's input gradient reads of the
  * activation in front of it is LeakyReLU', one bit per value.  A plane is (n, h, w, c / 8) bytes next to a bf16 tensor (n, h, w, c),
  * c % 8 == 0: bit e of byte c' / 8 is 1 iff the STORED bf16 value of channel c' + e is > 0 (-0, +0 and NaN give 0) - the predicate of

@@ -29,6 +29,8 @@ JPEG helpers with the reference's names (compression/jpeg_helpers.py).
   encode_batch, compress_batch), allow_grey=            for byte - written as baseline files and, asked for with allow_grey, read back,
   (parse_header, decode_batch, decode_coefficients,     baseline or progressive, next to colour files in one call
   transcode_batch)
+  lossless=, edge=, crop= (transcode_batch),           new: jpegtran's lossless transforms - flips, transposition, rotations, the aligned crop -
+  lossless_size                                         on the coefficients, one memory pass on the device
   JPEGMarkerStats (:133-250)                            host parsing of a file's segments
 
 JPEG 2000 sizes (jp2bytes :117-125) stay out of scope.
@@ -1047,12 +1049,13 @@ class _Group(namedtuple('_Group', 'indices h w hs vs restart_interval script coe
         return self.h, self.w, self.hs, self.vs
 
 
-def _decode_groups(files, subseq_bits, device, accept):
+def _decode_groups(files, subseq_bits, device, accept, headers=None):
     """Headers parsed, one upload, one nimg_jpeg_decode[_restart] per group of equal (h, w, hs, vs, restart interval) - for progressive
     files (accept.progressive) one nimg_jpeg_decode_progressive per group of equal geometry, interval and scan script.  Returns
     (headers, [_Group]) - device tensors, nothing read back.  The (hs, vs) of a group of grey-scale files (accept.grey) is
-    ops.JPEG_GREY: another geometry, so never in a group with colour files."""
-    headers = [parse_header(f, *accept) for f in files]
+    ops.JPEG_GREY: another geometry, so never in a group with colour files.  `headers`: the files' headers, where the caller has
+    parsed them already."""
+    headers = [parse_header(f, *accept) for f in files] if headers is None else headers
     if not headers:
         raise ValueError('no files to decode')
     keys = OrderedDict()
@@ -1204,8 +1207,50 @@ def _annex_k_coding():
     return None, encode, ops.jpeg_ecd_bound_tables
 
 
+def lossless_size(h, w, hs, vs, op, crop=None, edge='perfect'):
+    """(h', w', hs', vs') of the file transcode_batch(lossless=op, crop=crop, edge=edge) makes of an h x w file of the sampling factors
+    (hs, vs) - ops.JPEG_GREY for a grey-scale file.  Every refusal of the transform is raised here as the same ValueError, on the host
+    alone: no device is touched."""
+    return ops.jpeg_lossless_geometry(h, w, hs, vs, op, crop, edge)
+
+
+def _lossless_plan(headers, lossless, edge, crop):
+    """What transcode_batch's lossless=, edge= and crop= ask of each file -> ([operation name per file], [(h', w', hs', vs') per file]), or
+    (None, None) where nothing is asked: no operation (None or 'none' for every file) and no crop.  Host checks only; a refusal names
+    the file."""
+    n = len(headers)
+    if lossless is None or isinstance(lossless, str):
+        names = ['none' if lossless is None else lossless] * n
+    else:
+        names = list(lossless)
+        if len(names) != n:
+            raise ValueError('lossless: one operation for every file or one per file needed, got {} for {} files'.format(len(names), n))
+    bad = [name for name in names if not isinstance(name, str) or name not in ops.JPEG_LOSSLESS_OPS]
+    if bad:
+        raise ValueError('lossless: one of {} needed, got {!r}'.format(', '.join(ops.JPEG_LOSSLESS_OPS), bad[0]))
+    if edge not in ops.JPEG_LOSSLESS_EDGES:
+        raise ValueError("edge: 'perfect' (refuse a partial iMCU) or 'trim' (cut it off) needed, got {!r}".format(edge))
+    if crop is None and all(name == 'none' for name in names):
+        return None, None
+    sizes = []
+    for i, (hd, name) in enumerate(zip(headers, names)):
+        try:
+            sizes.append(lossless_size(hd.h, hd.w, *(ops.JPEG_GREY if hd.ncomp == 1 else (hd.hs, hd.vs)), name, crop, edge))
+        except ValueError as e:
+            raise ValueError('file {} ({} x {}, width x height): {}'.format(i, hd.w, hd.h, e)) from None
+    return names, sizes
+
+
+def _transposed_tables(qt):
+    """(T, 64) tables in natural order, each transposed: what a transposing operation makes of a file's quantisation tables."""
+    return np.ascontiguousarray(qt.reshape(-1, 8, 8).transpose(0, 2, 1)).reshape(-1, 64)
+
+
+_LOSSLESS_TRANSPOSING = ('transpose', 'transverse', 'rot90', 'rot270')
+
+
 def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=False, allow_progressive=False, allow_grey=False,
-                    allow_sampling=False):
+                    allow_sampling=False, lossless=None, edge='perfect', crop=None):
     """Baseline files written again with their coefficients and their quantisation tables untouched - a list of bytes in input order.
     The Huffman tables are the optimal ones of each image (what jpegtran -optimize does) or, with optimize=False, Annex K's.  Every
     file parse_header accepts is read; the header written is the one of encode_batch - JFIF APP0, two DQT segments where the file's Cb
@@ -1218,24 +1263,52 @@ def transcode_batch(files, optimize=True, *, allow_restart=False, progressive=Fa
     progression whatever script came in.  allow_grey: grey-scale files, baseline or with allow_progressive progressive, are read too and
     written again as grey-scale baseline files (one DQT segment, the DC and AC table 0) - not with `progressive`.  allow_sampling: files
     of the samplings 4:4:0, 4:1:1, 4:1:0, 1x4 and 2x4 are read too and written again as baseline files of the same
-    sampling factors - not with `progressive`, which is a ValueError for them."""
+    sampling factors - not with `progressive`, which is a ValueError for them.
+    lossless: jpegtran's lossless transforms on the way - a name of ops.JPEG_LOSSLESS_OPS ('hflip', 'vflip',
+    'transpose', 'transverse', 'rot90' - clockwise -, 'rot180', 'rot270', 'none') for every file, or a sequence of one name per file.
+    The coefficients are permuted and re-signed on the device (ops.jpeg_lossless, one call per decode group and operation; a file whose
+    operation is 'none' and that is not cropped takes none), the quantisation tables of a file are transposed by the transposing
+    operations, and everything behind runs at the geometry that results: the four transposing operations swap height with width and
+    the sampling factors hs with vs, so a 4:2:2 file comes out as 4:4:0 - written without allow_sampling, which reading it back needs.
+    A file keeps its restart interval as the same number of MCUs.  `optimize` composes; `progressive` where the OUTPUT factors are 1x1,
+    2x1 or 2x2.  crop (x, y, width, height): a region of every source file, cut before the operation (with 'none' too); x must be a
+    multiple of 8 hs and y of 8 vs (8 for grey-scale) - jpegtran moves an unaligned origin down silently, here it is a ValueError that
+    names the aligned value below; the blocks at a new right or bottom edge keep their contents, as jpegtran's do.  edge: a transform
+    moves whole iMCUs, so hflip and rot270 need the width to be a multiple of 8 hs, vflip and rot90 the height of 8 vs, rot180 and
+    transverse both; 'perfect' (jpegtran -perfect, the default) refuses a file where it is not, naming the file and the dimension,
+    'trim' (jpegtran -trim) cuts the partial iMCU off first.  lossless_size names the size that results.  Every refusal is raised before
+    a byte goes to the device.  None, or 'none' without a crop, is the call as it was."""
     files = _as_files(files)
-    headers, groups = _decode_groups(files, 0, None, _Accept(allow_restart, allow_progressive, allow_grey, allow_sampling))
+    accept = _Accept(allow_restart, allow_progressive, allow_grey, allow_sampling)
+    headers = [parse_header(f, *accept) for f in files]
+    names, sizes = _lossless_plan(headers, lossless, edge, crop)
     _colour_only(_PROGRESSIVE_GREY, progressive and any(hd.ncomp == 1 for hd in headers))
-    wide = sorted({(hd.hs, hd.vs) for hd in headers if hd.ncomp == 3 and ops.jpeg_is_wide(hd.hs, hd.vs)})
+    written = [(hd.hs, hd.vs) for hd in headers] if sizes is None else [s[2:] for s in sizes]       # the factors of the files written
+    wide = sorted({f for hd, f in zip(headers, written) if hd.ncomp == 3 and ops.jpeg_is_wide(*f)})
     if progressive and wide:
         raise ValueError('progressive=True: progressive files are not written with the sampling factors {} (DESIGN.md section 8); they '
                          'are written again as baseline files'.format(', '.join('{}x{}'.format(*f) for f in wide)))
+    headers, groups = _decode_groups(files, 0, None, accept, headers)
     _fetch_status(groups)
     result = [None] * len(files)
     for g in groups:
-        (h, w, hs, vs), ri = g.geometry, g.restart_interval
-        coding = _annex_k_coding() if ops.jpeg_is_wide(hs, vs) and not optimize else _coding(optimize, progressive)
-        segments, tables = _device_segments(coding, g.coef, len(g.indices), h, w, hs, vs, restart_interval=ri)
-        for j, i in enumerate(g.indices):                                   # a file at a time: each keeps its quantisation tables
-            qt = headers[i].qtables
-            qt = qt if len(qt) == 1 else (qt[:2] if np.array_equal(qt[1], qt[2]) else qt)
-            result[i], = _jpeg_files(h, w, None, (hs, vs), segments[j:j + 1], None if tables is None else tables[j:j + 1], qt, ri, progressive)
+        by_op = OrderedDict()                                               # the group splits by operation: positions in the group
+        for j, i in enumerate(g.indices):
+            by_op.setdefault('none' if names is None else names[i], []).append(j)
+        for name, at in by_op.items():
+            (h, w, hs, vs), ri, coef = g.geometry, g.restart_interval, g.coef
+            if len(at) != len(g.indices):
+                coef = coef[torch.as_tensor(at, device=coef.device)]
+            if name != 'none' or crop is not None:
+                coef, h, w, hs, vs = ops.jpeg_lossless(coef, h, w, hs, vs, name, crop, edge)
+            coding = _annex_k_coding() if ops.jpeg_is_wide(hs, vs) and not optimize else _coding(optimize, progressive)
+            segments, tables = _device_segments(coding, coef, len(at), h, w, hs, vs, restart_interval=ri)
+            for k, j in enumerate(at):                                      # a file at a time: each keeps its quantisation tables
+                i = g.indices[j]
+                qt = _transposed_tables(headers[i].qtables) if name in _LOSSLESS_TRANSPOSING else headers[i].qtables
+                qt = qt if len(qt) == 1 else (qt[:2] if np.array_equal(qt[1], qt[2]) else qt)
+                result[i], = _jpeg_files(h, w, None, (hs, vs), segments[k:k + 1], None if tables is None else tables[k:k + 1], qt, ri,
+                                         progressive)
     return result
 
 

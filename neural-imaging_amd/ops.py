@@ -5,6 +5,7 @@ CUDA(HIP) tensors in NHWC and raises otherwise - there is no CPU path.
 
 TF padding semantics live here (same_pads): SAME is asymmetric for strided convolutions (extra sample after).
 """
+import ctypes
 import math
 import os
 
@@ -2863,6 +2864,93 @@ def jpeg_reconstruct_scaled(coef, h, w, qtabs, scale, hs=1, vs=1, out_u8=False, 
     nimg_jpeg_reconstruct_scaled_workspace_bytes."""
     return _jpeg_reconstruct_tables('jpeg_reconstruct_scaled', 'nimg_jpeg_reconstruct_scaled', coef, h, w, qtabs, jpeg_scale(scale), hs, vs,
                                     out_u8, workspace, out)
+
+
+# lossless transforms (DESIGN.md section 4s): jpegtran's names, in the order of the C ABI's `op`
+JPEG_LOSSLESS_OPS = ('none', 'hflip', 'vflip', 'transpose', 'transverse', 'rot90', 'rot180', 'rot270')
+JPEG_LOSSLESS_EDGES = ('perfect', 'trim')
+# what each operation needs to be a whole number of source iMCUs (a transform moves whole iMCUs): (the width, the height)
+_JPEG_LOSSLESS_WHOLE = {'none': (False, False), 'transpose': (False, False), 'hflip': (True, False), 'rot270': (True, False),
+                        'vflip': (False, True), 'rot90': (False, True), 'rot180': (True, True), 'transverse': (True, True)}
+
+
+def _jpeg_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError('{}: an integer needed, got {!r}'.format(name, v))
+    return int(v)
+
+
+def _jpeg_lossless_args(h, w, hs, vs, op, crop, edge):
+    """The host checks of a lossless transform, every refusal a ValueError that names the dimension -> the arguments of the library's
+    entries behind (h, w): (hs, vs, nc, op, crop_x, crop_y, crop_w, crop_h, trim)."""
+    if not isinstance(op, str) or op not in JPEG_LOSSLESS_OPS:
+        raise ValueError('lossless: one of {} needed, got {!r}'.format(', '.join(JPEG_LOSSLESS_OPS), op))
+    if not isinstance(edge, str) or edge not in JPEG_LOSSLESS_EDGES:
+        raise ValueError("edge: 'perfect' (refuse a partial iMCU) or 'trim' (cut it off) needed, got {!r}".format(edge))
+    h, w = _jpeg_int('h', h), _jpeg_int('w', w)
+    grey = jpeg_is_grey(hs, vs)
+    if not grey and (hs, vs) not in JPEG_SUBSAMPLING.values() and not jpeg_is_wide(hs, vs):
+        raise ValueError('lossless: unsupported sampling factors {}x{}'.format(hs, vs))
+    mh, mw = (8, 8) if grey else (8 * vs, 8 * hs)                      # the iMCU; 8 x 8 in a grey-scale file whatever it declares
+    if h < 1 or w < 1:
+        raise ValueError('lossless: an image of {} x {} pixels'.format(h, w))
+    x, y, cw, ch = 0, 0, w, h
+    if crop is not None:
+        if isinstance(crop, (str, bytes)) or not hasattr(crop, '__len__') or len(crop) != 4:
+            raise ValueError('crop: (x, y, width, height) needed, got {!r}'.format(crop))
+        x, y, cw, ch = (_jpeg_int('crop', v) for v in crop)
+        if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h:
+            raise ValueError('crop: the region x={} y={} {} x {} (width x height, at least 1 x 1) does not lie inside the {} x {} image'
+                             .format(x, y, cw, ch, w, h))
+        for name, v, m in (('x', x, mw), ('y', y, mh)):
+            if v % m:
+                raise ValueError('crop: {}={} is not a multiple of the iMCU ({} for these sampling factors): the nearest aligned value '
+                                 'below is {} (jpegtran moves the origin there silently; here it is the caller who does)'
+                                 .format(name, v, m, v - v % m))
+    for name, v, m, whole in (('width', cw, mw, _JPEG_LOSSLESS_WHOLE[op][0]), ('height', ch, mh, _JPEG_LOSSLESS_WHOLE[op][1])):
+        if whole and v % m:
+            if edge == 'perfect':
+                raise ValueError("lossless {}: the {} {} is not a multiple of the iMCU ({}): the transform is not perfect - edge='trim' "
+                                 'cuts the last {} off'.format(op, name, v, m, v % m))
+            if v < m:
+                raise ValueError("lossless {}: nothing is left of the {} {} trimmed to a multiple of the iMCU ({})".format(op, name, v, m))
+    return ((1, 1, 1) if grey else (hs, vs, 3)) + (JPEG_LOSSLESS_OPS.index(op),) + \
+        ((0, 0, 0, 0) if crop is None else (x, y, cw, ch)) + (int(edge == 'trim'),)
+
+
+def jpeg_lossless_geometry(h, w, hs, vs, op, crop=None, edge='perfect'):
+    """(h', w', hs', vs') of the file jpeg_lossless makes of an h x w file of the factors (hs, vs) - JPEG_GREY: a grey-scale file, which
+    stays one.  The four transposing operations swap h with w and hs with vs; a crop and edge='trim' shrink the image.  Computed on the
+    host (nimg_jpeg_lossless_geometry) - no device is touched; what jpeg_lossless refuses is refused here by the same ValueError."""
+    args = _jpeg_lossless_args(h, w, hs, vs, op, crop, edge)
+    got = [ctypes.c_int() for _ in range(4)]
+    rc = _lib.load().nimg_jpeg_lossless_geometry(int(h), int(w), *args, *(ctypes.byref(v) for v in got))
+    if rc != 0:
+        raise ValueError('lossless {}: the library refuses {} x {}, factors {}x{}, crop {}, edge {!r}'.format(op, h, w, hs, vs, crop, edge))
+    oh, ow, ohs, ovs = (v.value for v in got)
+    return (oh, ow) + (JPEG_GREY if jpeg_is_grey(hs, vs) else (ohs, ovs))
+
+
+def jpeg_lossless(coef, h, w, hs, vs, op, crop=None, edge='perfect', out=None):
+    """A lossless transform of the coefficients of n files of one geometry (nimg_jpeg_lossless): coef (n, real
+    blocks, 64) int16 as jpeg_decode leaves them -> (coef' (n, real blocks of the new geometry, 64), h', w', hs', vs').  op: a name of
+    JPEG_LOSSLESS_OPS, jpegtran's - 'rot90' is clockwise, 'transverse' the flip about the anti-diagonal.  crop (x, y, width, height):
+    a region of the source cut before the operation, its origin a multiple of the iMCU (8 hs, 8 vs; 8 for grey-scale).  edge: 'perfect'
+    refuses a file whose mirrored dimension is no whole number of iMCUs, 'trim' cuts the partial one off.  For the four transposing
+    operations every quantisation table of the file is to be transposed too.  One launch, no workspace."""
+    oh, ow, ohs, ovs = jpeg_lossless_geometry(h, w, hs, vs, op, crop, edge)
+    _chk(coef)
+    n = _jpeg_coef('jpeg_lossless', coef, h, w, hs, vs)
+    shape = (n, jpeg_geometry(oh, ow, ohs, ovs)[0], 64)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=coef.device)
+    _chk(out)
+    if out.dtype != torch.int16 or tuple(out.shape) != shape:
+        raise RuntimeError('jpeg_lossless: output {} {}, {} int16 needed'.format(out.dtype, tuple(out.shape), shape))
+    got = [ctypes.c_int() for _ in range(4)]
+    _lib.call('nimg_jpeg_lossless', _p(coef), n, int(h), int(w), *_jpeg_lossless_args(h, w, hs, vs, op, crop, edge), _p(out),
+              *(ctypes.byref(v) for v in got), _stream())
+    return out, oh, ow, ohs, ovs
 
 
 # optimised Huffman tables (DESIGN.md section 4f): a table is 16 counts + 256 symbols in code order, an image has four of them in
